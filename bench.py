@@ -15,15 +15,20 @@ process per GPU, before anything in this process touches a GPU); under
 rank decodes its own 1024 streams (independent streams: no data-path
 collective, weak scaling); `value` is the whole-job Msamples/s.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) including
+A plain run stages the workload, warms up, times --steps launches, writes
+--dump-outputs DIR if asked and prints ONE JSON line on rank 0 (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...) including
   roofline     - achieved algorithmic HBM GB/s of the tile kernel
                  (4 B/sample: 2 B staged index in + 2 B PCM out) against 8 TB/s,
-                 from HIP events recorded on the launch stream
+                 from HIP events recorded on the launch stream.
+With --full the line carries everything else as well:
+  every stream of the workload compared with the CPU oracle (CRC of its PCM)
+  before the warm-up and again after the timed region, a long sustained run,
+  the other staged forms, power and clocks, copy ceilings, live PMC traffic,
+  other levels and configurations, end to end, the N > 1 gather leg, and
   cpu_baseline - the same decode on the host cores (the real reference if the
                  prebuilt oracle/_ref is present, else our oracle port), on a
                  bounded sample of the same workload, rank 0 / N=1 only.
-Every stream of the workload is compared with the CPU oracle (CRC of its PCM)
-before the warm-up and again after the timed region.
 """
 import argparse
 import ctypes as C
@@ -86,7 +91,21 @@ def parse_args():
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the PCM gather leg (C2) that is reported beside the headline")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even with one rank - exercises the N>1 code path on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU oracle check of every stream before and after timing, the "
+                         "sustained run, the other staged forms, power and clocks, copy ceilings, live PMC traffic, other levels and "
+                         "configurations, end to end, the N > 1 gather leg and the CPU baseline (--no-extra, --no-cpu, --no-packed, "
+                         "--no-gather and --no-verify trim it).  Without it a run only sets up, warms up, times --steps launches, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed launches, write the PCM the last one left (rank 0's streams) to DIR as float32 .npy files: "
+                         "a seeded sample of positions over the whole batch and the leading samples of the first and last stream")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:
+        a.no_extra = a.no_cpu = a.no_gather = True
+    a.verify = a.full and not a.no_verify
     if a.gpus is None:
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))      # torchrun --nproc-per-node N bench.py  ==  --gpus N
     if a.packed:
@@ -452,6 +471,45 @@ def precondition(dev, plan, bufs, seconds):
     return n
 
 
+DUMP_SAMPLE = 8 << 20       # --dump-outputs: PCM positions picked over the whole batch (32 MB as float32) ...
+DUMP_HEAD = 2 << 20         # ... and the leading samples of the first and the last stream (8 MB each)
+DUMP_SEED = 0xACD0
+
+
+def dump_outputs(path, dev, batch, d_pcm):
+    """What the last launch left in the PCM arena - the 16-bit samples a caller of the hot path receives - as float32 .npy files
+    (48 MB at most): pcm_sample.npy, a fixed seeded sample of positions over every emitted sample of the batch (stream by stream, in
+    order), and pcm_first_stream.npy / pcm_last_stream.npy, the leading samples of those streams.  Same arguments, same files."""
+    os.makedirs(path, exist_ok=True)
+    n_emit = np.array([d.n_emit for d in batch.descs], dtype=np.int64)
+    pcm_off = np.array([d.pcm_off for d in batch.descs], dtype=np.int64)
+    ends = np.cumsum(n_emit)
+    total = int(ends[-1])
+    if total <= DUMP_SAMPLE:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+    k = np.searchsorted(ends, pos, side="right")
+    word = pcm_off[k] + pos - (ends[k] - n_emit[k])            # arena word of every picked sample
+    order = np.argsort(word, kind="stable")
+    word_sorted = word[order]
+    sample = np.empty(pos.size, dtype=np.float32)
+    slab = 1 << 27
+    host = np.empty(min(slab, batch.pcm_words), dtype=np.uint16)
+    for lo in range(0, batch.pcm_words, slab):
+        i, j = np.searchsorted(word_sorted, [lo, lo + slab])
+        if i == j:
+            continue
+        n = min(slab, batch.pcm_words - lo)
+        dev.download(host[:n], d_pcm + 2 * lo)
+        sample[order[i:j]] = host[word_sorted[i:j] - lo].view(np.int16)
+    np.save(os.path.join(path, "pcm_sample.npy"), sample)
+    for name, d in (("pcm_first_stream", batch.descs[0]), ("pcm_last_stream", batch.descs[-1])):
+        head = np.empty(min(d.n_emit, DUMP_HEAD), dtype=np.uint16)
+        dev.download(head, d_pcm + 2 * d.pcm_off)
+        np.save(os.path.join(path, name + ".npy"), head.view(np.int16).astype(np.float32))
+
+
 def side_measure(dev, capi, workload, level, rows, blocks, streams, steps, verify=256, channels=1, packed=True, corpus_files=0):
     """kernel-only rate of another configuration (configs[1] is level 7; the stress config is level 11) on every staged form its
     level has: the byte-plane form where there is one (that is the entry's own rate), the int16 form, the packed form.  The PCM
@@ -582,7 +640,7 @@ def main():
     # file images are kept for the oracle check of EVERY stream (and, on rank 0 at N=1, for the CPU baseline)
     t0 = time.perf_counter()
     stage_threads = max(4, min(64, workload_cpus()))       # the rank's own slice of the host (pin_rank_cpus)
-    keep = 0 if args.no_verify and (args.no_cpu or world != 1) else 1 << 30
+    keep = 0 if not args.verify and (args.no_cpu or world != 1) else 1 << 30
     if args.workload == "corpus":
         # configs[2]/[3]: the SAME corpus whatever N; rank r decodes its longest-first shard of the file list
         from libacm_amd import batch as fe
@@ -637,9 +695,9 @@ def main():
     bind_headline_form()
     stats = plan.stats()
 
-    # setup-time check (untimed): every stream of the workload against the CPU oracle, CRC-32 of its PCM
+    # setup-time check (untimed, --full): every stream of the workload against the CPU oracle, CRC-32 of its PCM
     verified, n_verified, want = None, 0, None
-    if batch.files and not args.no_verify:
+    if batch.files and args.verify:
         want = oracle_crcs(batch, stage_threads)
         plan.launch(*bufs)
         dev.sync()
@@ -652,8 +710,10 @@ def main():
 
     pre = precondition(dev, plan, bufs, PRECONDITION_S)
     wall, ev_ms = time_plan(dev, plan, bufs, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dev, batch, bufs[2])
     sustained = None
-    if args.steps < SUSTAINED_STEPS:
+    if args.full and args.steps < SUSTAINED_STEPS:
         # the contract's K is short (tens of ms): the same loop again, long, right behind it
         swall, sev = time_plan(dev, plan, bufs, SUSTAINED_STEPS, 0, barrier)
         sustained = {"steps": SUSTAINED_STEPS, "ms_per_step": round(swall / SUSTAINED_STEPS * 1e3, 4),
@@ -833,7 +893,8 @@ def main():
         "value": round(value, 1), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": "strong" if args.workload == "corpus" else "weak", "vs_baseline": None,
-        "verified_vs_oracle": verified if not args.no_verify else "skipped (--no-verify)",
+        "verified_vs_oracle": verified if args.verify else "skipped (--no-verify)" if args.no_verify else
+                              "skipped (plain run: --full checks every stream against the CPU oracle)",
         "verified_streams": n_verified, "dtype": "int32", "data": "synthetic",
         "config": {"workload": ("BASELINE.json configs[2]: %d-file corpus, mixed mono/stereo, acm_level 7-9, 1-60 s at 22050 Hz, "
                                 "sharded by file" % args.files) if args.workload == "corpus" else

@@ -15,7 +15,7 @@ mkdir -p $OUT
 # what was profiled: hash of the kernel source and of the library on this box
 { echo "tag $TAG"; echo "args $*"; date -u +"utc %Y-%m-%dT%H:%M:%SZ"; sha256sum libacm_amd/csrc/acm_kernels.hip libacm_amd/csrc/acm_hip_api.cpp libacm_amd/lib/libacm_hip.so bench.py; } > $OUT/BUILD_STAMP.txt 2>&1
 export TMPDIR=/tmp
-ARGS="--steps 100 --warmup 20 --no-cpu --no-extra $*"
+ARGS="--steps 100 --warmup 20 --full --no-cpu --no-extra $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 python3 bench.py $ARGS > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err
 if [ -n "${PROFILE_LIGHT:-}" ]; then GROUPS_=("FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE"); else GROUPS_=(); fi

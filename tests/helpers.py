@@ -62,6 +62,40 @@ def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
 
 
+REF_ANSWERS = os.path.join(GOLDEN_DIR, "ref_answers.json")
+RECORDING = None            # a dict while tests/golden/make_golden_ref_answers.py records the live reference's answers into it
+_ref_answers = None
+
+
+class RefAnswers:
+    """The compiled reference's answers to one test's sequence of questions, in order.  Replayed from tests/golden/ref_answers.json,
+    so the test needs nothing outside the repository; tests/golden/make_golden_ref_answers.py runs the same tests against the live
+    reference (oracle/_ref) to record them.  ask(fn): fn() questions the live reference and returns a JSON value (digests in place
+    of PCM bytes); it is only called while recording."""
+
+    def __init__(self, key):
+        global _ref_answers
+        self.key, self.i = key, 0
+        self.live = RECORDING is not None
+        if self.live:
+            self.vals = RECORDING[key] = []
+        else:
+            if _ref_answers is None:
+                with open(REF_ANSWERS) as f:
+                    _ref_answers = json.load(f)
+            self.vals = _ref_answers[key]
+
+    def ask(self, fn):
+        if self.live:
+            self.vals.append(json.loads(json.dumps(fn())))
+        assert self.i < len(self.vals), "%s: more questions than recorded answers" % self.key
+        self.i += 1
+        return self.vals[self.i - 1]
+
+    def done(self):
+        assert self.i == len(self.vals), "%s: %d of %d recorded answers asked for" % (self.key, self.i, len(self.vals))
+
+
 def decode_record(stream_cls_factory, data, force_chans=0, be=0, sgned=1, step=8192, **io_kw):
     """Decode through any libacm.h-shaped stream wrapper and summarise like make_golden.ref_decode()."""
     s = stream_cls_factory(data, force_chans, **io_kw)

@@ -48,7 +48,7 @@ def test_two_rank_rehearsal_on_one_gpu():
     timing, `per_rank`, `imbalance`, `gather_c2` and the ONE JSON line from rank 0, with every stream of both ranks verified"""
     import json
     r = run_bench(["--gpus", "2", "--control", "gloo", "--share-device", "--streams", "48", "--blocks", "12", "--steps", "3", "--warmup", "1",
-                   "--no-extra", "--no-cpu"])
+                   "--full", "--no-extra", "--no-cpu"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -69,7 +69,7 @@ def test_two_rank_rehearsal_of_the_sharded_corpus():
     kernels decode"""
     import json
     r = run_bench(["--gpus", "2", "--control", "gloo", "--share-device", "--workload", "corpus", "--files", "120", "--steps", "3", "--warmup", "1",
-                   "--no-extra", "--no-cpu"])
+                   "--full", "--no-extra", "--no-cpu"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -82,3 +82,30 @@ def test_two_rank_rehearsal_of_the_sharded_corpus():
     ks = j["config"]["kernel_share"]
     assert set(ks["by_level"]) == {"7", "8", "9"} and ks["samples_from_byteplane_form"] > 0.9
     assert "rehearsal" in j
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_decoded_pcm(tmp_path):
+    """--dump-outputs DIR: after the timed launches the PCM of the last one lands in DIR as float32 .npy files (64 MB at most); a plain
+    run says it did not check against the oracle, the first stream's samples equal the oracle's and --steps is the timed count"""
+    import json
+    import numpy as np
+    import oracle_api as O
+    from libacm_amd import synth
+    r = run_bench(["--gpus", "1", "--streams", "8", "--blocks", "12", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 7 and j["ms_per_step"] > 0 and j["value"] > 0 and "cpu_baseline" not in j and "sustained" not in j
+    assert str(j["verified_vs_oracle"]).startswith("skipped")
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == ["pcm_first_stream.npy", "pcm_last_stream.npy", "pcm_sample.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    arrs = {n: np.load(str(tmp_path / n)) for n in names}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    n = 12 * 16 << 9                                          # one stream: 12 blocks of 16 rows at level 9
+    f = synth.generate(seed=synth.BASE_SEED, level=9, rows=16, nblocks=12, channels=1, total_values=n)
+    want = O.Oracle.decode_all(f)[0].view(np.int16).astype(np.float32)
+    assert np.array_equal(arrs["pcm_first_stream.npy"], want)
+    assert np.array_equal(arrs["pcm_sample.npy"][:n], want)  # a batch this small is dumped whole, stream by stream

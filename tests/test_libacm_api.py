@@ -7,7 +7,7 @@ import ctypes as C
 import pytest
 
 import oracle_api as O
-from helpers import decode_record, golden, golden_file, sha
+from helpers import RefAnswers, decode_record, golden, golden_file, sha
 from libacm_amd import capi
 
 
@@ -67,12 +67,12 @@ def test_seek_and_discard_bookkeeping():
     s.close()
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="needs the compiled reference (oracle/_ref)")
 @pytest.mark.parametrize("shape", [(5, 4, 60, 1, 0), (7, 16, 25, 2, 0), (3, 1, 90, 1, 0), (6, 5, 40, 2, 1), (0, 3, 50, 1, 0), (7, 16, 500, 1, 1)])
 def test_random_seek_walk_matches_reference(shape, monkeypatch):
     """a walk of forward/backward acm_seek_pcm / acm_seek_time calls and discard reads: return values, acm_pcm_tell,
     acm_raw_tell and acm_time_tell equal the reference's at every step - with the block index (backward seeks re-enter
-    the stream near the target) and without it (acmhip_set_seek_index(0): rewind and re-parse, as the reference does)"""
+    the stream near the target) and without it (acmhip_set_seek_index(0): rewind and re-parse, as the reference does).  The
+    reference's side is replayed from tests/golden/ref_answers.json (helpers.RefAnswers)"""
     import numpy as np
     from libacm_amd import synth
     level, rows, nb, ch, wavc = shape
@@ -84,21 +84,23 @@ def test_random_seek_walk_matches_reference(shape, monkeypatch):
         if no_index:
             seek_index(False, monkeypatch)
         rng = np.random.default_rng(level * 100 + rows)
-        r = O.LibacmStream(O.ref_lib(), f)
+        ans = RefAnswers("test_libacm_api::test_random_seek_walk_matches_reference[%s]%s" % (shape, " no_index" if no_index else ""))
+        r = O.LibacmStream(O.ref_lib(), f) if ans.live else None
         s = ours(f)
         for step in range(60):
             op = int(rng.integers(0, 3))
             if op == 0:
                 n = int(rng.integers(1, 4000)) * 2
-                got, want = s.read(n, discard=True)[0], r.read(n, discard=True)[0]
+                got, want = s.read(n, discard=True)[0], ans.ask(lambda: r.read(n, discard=True)[0])
             elif op == 1:
                 pos = int(rng.integers(0, total_pcm + 50))
-                got, want = s.seek_pcm(pos), r.seek_pcm(pos)
+                got, want = s.seek_pcm(pos), ans.ask(lambda: r.seek_pcm(pos))
             else:
                 ms = int(rng.integers(0, total_pcm * 1000 // 22050 + 20))
-                got, want = s.seek_time(ms), r.seek_time(ms)
-            state = [(x.getter("pcm_tell"), x.getter("raw_tell"), x.getter("time_tell")) for x in (s, r)]
-            assert got == want and state[0] == state[1], (shape, no_index, step, op, got, want, state)
+                got, want = s.seek_time(ms), ans.ask(lambda: r.seek_time(ms))
+            state = [s.getter("pcm_tell"), s.getter("raw_tell"), s.getter("time_tell")]
+            want_state = ans.ask(lambda: [r.getter("pcm_tell"), r.getter("raw_tell"), r.getter("time_tell")])
+            assert got == want and state == want_state, (shape, no_index, step, op, got, want, state, want_state)
         if no_index:
             # the index must have saved re-parsing: fewer refill calls than the rewind-and-re-parse flavour (long files)
             if len(f) > 200000:
@@ -106,7 +108,9 @@ def test_random_seek_walk_matches_reference(shape, monkeypatch):
         else:
             reads_with_index = len(s.io.read_calls)
         s.close()
-        r.close()
+        if r is not None:
+            r.close()
+        ans.done()
 
 
 def discard_all(s):
@@ -366,11 +370,15 @@ def test_interleaved_reads_on_two_streams(side):
     assert b"".join(ga) == wa and b"".join(gb) == wb
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="needs the compiled reference (oracle/_ref)")
+def read_digest(rc_bytes):
+    """(rc, PCM bytes) of one read -> [rc, sha256 of the bytes], the form the reference's recorded answers take"""
+    return [rc_bytes[0], sha(rc_bytes[1])]
+
+
 @pytest.mark.parametrize("shape", [(7, 16, 120, 1, 0), (5, 1, 300, 2, 1), (9, 16, 12, 2, 0), (6, 3, 80, 1, 0)])
 def test_random_seek_walk_pcm(side, shape):
     """seeks forward and backward (block index in use) followed by real reads: the PCM bytes and all positions equal
-    the reference's"""
+    the reference's (replayed from tests/golden/ref_answers.json)"""
     import numpy as np
     from libacm_amd import synth
     level, rows, nb, ch, wavc = shape
@@ -378,28 +386,30 @@ def test_random_seek_walk_pcm(side, shape):
     f = synth.generate(seed=synth.BASE_SEED + 4300 + level, level=level, rows=rows, nblocks=nb, channels=ch, wavc=wavc,
                        total_values=total)
     rng = np.random.default_rng(level * 7 + rows)
-    r = O.LibacmStream(O.ref_lib(), f)
+    ans = RefAnswers("test_libacm_api::test_random_seek_walk_pcm[%s]" % (shape,))
+    r = O.LibacmStream(O.ref_lib(), f) if ans.live else None
     s = ours(f)
     for step in range(50):
         if step % 2 == 0:
             pos = int(rng.integers(0, total // ch))
-            assert s.seek_pcm(pos) == r.seek_pcm(pos), (shape, step, pos)
+            assert s.seek_pcm(pos) == ans.ask(lambda: r.seek_pcm(pos)), (shape, step, pos)
         n = int(rng.integers(1, 3000)) * 2 * ch
         be, sg = int(rng.integers(0, 2)), int(rng.integers(0, 2))
-        got, want = s.read(n, be=be, sgned=sg), r.read(n, be=be, sgned=sg)
+        got, want = read_digest(s.read(n, be=be, sgned=sg)), ans.ask(lambda: read_digest(r.read(n, be=be, sgned=sg)))
         assert got == want, (shape, step, n)
-        assert [s.getter(k) for k in ("pcm_tell", "raw_tell")] == [r.getter(k) for k in ("pcm_tell", "raw_tell")]
+        assert [s.getter(k) for k in ("pcm_tell", "raw_tell")] == ans.ask(lambda: [r.getter(k) for k in ("pcm_tell", "raw_tell")])
     s.close()
-    r.close()
+    if r is not None:
+        r.close()
+    ans.done()
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="needs the compiled reference (oracle/_ref)")
 @pytest.mark.parametrize("no_index", [False, True])
 def test_seek_walk_on_a_stale_table_stream(side, no_index, monkeypatch):
     """hazard H1 plus seeks: out-of-range indices read table entries left by earlier blocks, the reference never clears its
     table (decode.c:809-810) and has only decoded what it served - our parser reads ahead of the caller, so a backward
     seek must continue from the table as the SERVED blocks left it.  prime_table makes block 0 write every
-    entry, so the reference's answer does not depend on heap garbage."""
+    entry, so the reference's answer does not depend on heap garbage.  Its answers are replayed from tests/golden/ref_answers.json."""
     import numpy as np
     from libacm_amd import synth
     if no_index:
@@ -409,15 +419,18 @@ def test_seek_walk_on_a_stale_table_stream(side, no_index, monkeypatch):
     f = synth.generate(seed=synth.BASE_SEED + 4400, level=level, rows=rows, nblocks=nb, total_values=total, mix=1,
                        allow_out_of_range=1, prime_table=1, pwr_min=0, pwr_max=7)
     rng = np.random.default_rng(99)
-    r = O.LibacmStream(O.ref_lib(), f)
+    ans = RefAnswers("test_libacm_api::test_seek_walk_on_a_stale_table_stream[%s]" % ("no_index" if no_index else "index"))
+    r = O.LibacmStream(O.ref_lib(), f) if ans.live else None
     s = ours(f)
     pos_list = [total // 2, 100, total // 3, 5000, total - 4000, 0, total // 4]
     for step, pos in enumerate(pos_list):
         # a short read first: our read-ahead window is far ahead of what has been served when the seek comes
         n = int(rng.integers(1, 400)) * 2
-        assert s.read(n) == r.read(n), ("pre", step)
-        assert s.seek_pcm(pos) == r.seek_pcm(pos), (step, pos)
+        assert read_digest(s.read(n)) == ans.ask(lambda: read_digest(r.read(n))), ("pre", step)
+        assert s.seek_pcm(pos) == ans.ask(lambda: r.seek_pcm(pos)), (step, pos)
         n = int(rng.integers(2000, 9000)) * 2
-        assert s.read(n) == r.read(n), (step, pos, n)
+        assert read_digest(s.read(n)) == ans.ask(lambda: read_digest(r.read(n))), (step, pos, n)
     s.close()
-    r.close()
+    if r is not None:
+        r.close()
+    ans.done()
