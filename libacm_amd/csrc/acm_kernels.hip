@@ -3802,6 +3802,14 @@ extern "C" int acmk_tile2m_run_waves(uint32_t level, int cus)
 	return (cus > 0 ? cus : 256) * e.wg_per_cu * (e.threads / 64);
 }
 
+/* workgroups of a launch of the byte-plane build at most (the same as acmk_tile2_grid except at level 13, whose tiles are half as tall) */
+extern "C" int acmk_tile2m_grid(uint32_t level, int cus)
+{
+	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
+		return 0;
+	return (cus > 0 ? cus : 256) * tile2m_entry(level).e.wg_per_cu;
+}
+
 extern "C" int acmk_tile2m_stages(uint32_t level)
 {
 	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
