@@ -135,6 +135,10 @@ int  acmhip_memset(acmhip_device *dev, void *dptr, int byte, size_t bytes);     
  */
 int  acmhip_host_synth(const acmhip_stream_desc *stream, const int16_t *idx, const acmhip_blkhdr *hdr,
 		       const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm);
+/* The same into float32 samples (see acmhip_plan_launch_f32 for their meaning; pcm_off and n_emit count floats): the CPU reference of
+ * the float32 output.  acm_read() never uses it. */
+int  acmhip_host_synth_f32(const acmhip_stream_desc *stream, const int16_t *idx, const acmhip_blkhdr *hdr,
+			   const acmhip_patch *patches, size_t npatches, float *pcm);
 void acmhip_set_host_synth_limit(uint64_t samples);
 /* acm_seek_pcm() re-enters a stream at the block in front of its target through the block index the parser keeps (default); off = the
  * reference's way, re-parsing from the first block (util.c:219-242).  Same positions, same PCM; for cross-checks and measurements. */
@@ -159,6 +163,15 @@ void acmhip_plan_destroy(acmhip_plan *plan);
  */
 int  acmhip_plan_launch(acmhip_plan *plan, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 			int16_t *d_pcm, unsigned fmt);
+
+/*
+ * The same launch writing float32 samples for torch-style consumers, chosen per launch like fmt.  A float sample is EXACTLY
+ * the ACMHIP_FMT_S16LE sample times 2^-15: the reference's own 16-bit value, with its wrap (decode.c:620: the low 16 bits of
+ * x >> level, no clamping), divided by 32768 - in [-1, 1), little-endian IEEE, always exact; not a decode at higher precision.
+ * pcm_off and n_emit of the stream descriptors count floats (pcm_off stays a multiple of 8: 32 bytes).  Works on any plan except
+ * one with a packed arena bound (acmhip_plan_bind_packed): ACMHIP_ERR_ARG, the packed form has no float32 build.
+ */
+int  acmhip_plan_launch_f32(acmhip_plan *plan, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, float *d_pcm);
 
 /* ------------------------------------------------------------------------
  * Packed staged form: filler class per column pair + fixed-width packed residuals
@@ -387,7 +400,8 @@ typedef struct acm_batch_item {
 	int32_t  status;         /* out: ACM_OK, or the ACM_ERR_* that ended the stream / rejected the file */
 	uint32_t level, rows, channels, rate, total_values;   /* out */
 	uint32_t reserved;
-	uint64_t dev_off;        /* out: 16-bit word offset of this stream's PCM inside opts->d_pcm (device-resident output) */
+	uint64_t dev_off;        /* out: 16-bit word offset of this stream's PCM inside opts->d_pcm (device-resident output; float
+	                            offset with ACM_BATCH_PCM_F32) */
 } acm_batch_item;
 
 typedef struct acm_batch_opts {
@@ -420,6 +434,10 @@ typedef struct acm_batch_opts {
 #define ACM_BATCH_PCM_PINNED   1u   /* every items[i].pcm is pinned host memory (acmhip_host_alloc): the read-back engine writes
                                        the PCM straight into it, stream by stream, instead of through the library's own pinned
                                        arena and a host copy (taken for streams of 64 KB of PCM and more on average) */
+#define ACM_BATCH_PCM_F32     16u   /* device-resident output only: float32 samples into opts->d_pcm, each the ACMHIP_FMT_S16LE sample
+                                       times 2^-15 exactly (acmhip_plan_launch_f32); d_pcm_words and items[i].dev_off count floats
+                                       (acm_batch_pcm_words() counts samples: unchanged).  ACMHIP_ERR_ARG without opts->d_pcm, with a
+                                       fmt other than ACMHIP_FMT_S16LE, or with ACM_BATCH_STAGE_PACKED */
 
 /* where the bit parsing of a batch runs */
 #define ACM_BATCH_PARSE_HOST   0u   /* host thread pool (default; the exact reader, any stream) */

@@ -50,9 +50,10 @@ def build_synth(force=False):
     return out
 
 
-HIP_SOURCES = ["acm_kernels.hip", "acm_parse.hip", "acm_hip_api.cpp", "acm_fill.cpp", "acm_pack.cpp", "acm_stream.cpp", "acm_batch.cpp",
+HIP_SOURCES = ["acm_kernels.hip", "acm_kernels_f32.hip", "acm_parse.hip", "acm_hip_api.cpp", "acm_fill.cpp", "acm_pack.cpp", "acm_stream.cpp", "acm_batch.cpp",
                "acm_host_synth.cpp"]
 HOST_ONLY = {"acm_host_synth.cpp"}      # plain C++ (CPU-dispatched AVX2 inside): no device pass
+INCLUDES = {"acm_kernels_f32.hip": ["acm_kernels.hip"]}      # the float32 builds: acm_kernels.hip compiled once more
 
 
 def build_hip(force=False):
@@ -63,7 +64,8 @@ def build_hip(force=False):
         objs = []
         for s in src:
             o = os.path.join(LIB, os.path.basename(s) + ".o")
-            if force or _stale(o, [s] + _headers()):
+            deps = [os.path.join(CSRC, f) for f in INCLUDES.get(os.path.basename(s), [])]
+            if force or _stale(o, [s] + deps + _headers()):
                 cmd = [HIPCC, "-O3", "-g1", "-std=c++17", "-fPIC", "-Wall", "-Wextra",
                        "--offload-arch=" + GFX, "-I", INC, "-I", CSRC, "-c", s, "-o", o]
                 if os.environ.get("ACM_ABLATION"):      # timing-only kernel variants for profiling sessions

@@ -78,14 +78,21 @@ def pcm_capacity_words(head, file_len, force_chans=0):
 class GpuDecoder:
     """Decode a list of file images on this rank's GPU; PCM stays in HBM as one torch int16 tensor.
 
+    dtype=torch.float32: the tensor holds float32 samples instead, each the s16le sample times 2^-15 exactly (in [-1, 1), what
+    torchaudio.load returns), written by the synthesis kernels themselves (ACM_BATCH_PCM_F32: fmt must stay FMT_S16LE).
     Device memory and the stream belong to torch (plumbing); parsing and synthesis are libacm_hip.so's.
     """
 
-    def __init__(self, ordinal=None, fmt=capi.FMT_S16LE, parse=capi.PARSE_AUTO):
+    def __init__(self, ordinal=None, fmt=capi.FMT_S16LE, parse=capi.PARSE_AUTO, dtype=None):
         import torch
         self.torch = torch
         if ordinal is None:
             ordinal = torch.cuda.current_device()
+        self.dtype = torch.int16 if dtype is None else dtype
+        if self.dtype not in (torch.int16, torch.float32):
+            raise ValueError("GpuDecoder: dtype torch.int16 or torch.float32, not %s" % (self.dtype,))
+        if self.dtype == torch.float32 and fmt != capi.FMT_S16LE:
+            raise ValueError("GpuDecoder: float32 samples are the s16le ones scaled; fmt must be FMT_S16LE")
         self.ordinal = ordinal
         self.fmt = fmt
         self.parse = parse
@@ -97,21 +104,23 @@ class GpuDecoder:
 
     def empty(self, words):
         """a PCM buffer this decoder can decode into (decode_sharded keeps two of them per rank and reuses them)"""
-        return self.torch.empty(max(words, 1), dtype=self.torch.int16, device="cuda:%d" % self.ordinal)
+        return self.torch.empty(max(words, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
 
     def __call__(self, files, out=None):
-        """-> (pcm int16 tensor in HBM, per-file word offsets into it, per-file word counts, per-file statuses).
-        out: a tensor of at least acm_batch_pcm_words(files) words to decode into (else a new one is allocated)"""
+        """-> (pcm tensor in HBM - int16, or float32 -, per-file sample offsets into it, per-file sample counts, per-file statuses).
+        out: a tensor of this decoder's dtype of at least acm_batch_pcm_words(files) samples to decode into (else a new one is allocated)"""
         torch = self.torch
         cap = capi.batch_pcm_words(files)
-        d_pcm = out if out is not None and out.numel() >= cap else torch.empty(max(cap, 1), dtype=torch.int16, device="cuda")
+        if out is not None and out.dtype != self.dtype:
+            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
+        d_pcm = out if out is not None and out.numel() >= cap else torch.empty(max(cap, 1), dtype=self.dtype, device="cuda")
         # a block the caching allocator hands out may still be in use by torch work queued on torch's stream
         torch.cuda.current_stream().synchronize()
         # one call: threaded (or device-side) bit parsing, pipelined H2D, synthesis; the PCM stays in d_pcm.  In steady state
         # nothing in it allocates or frees device memory (grow-only arenas, plan tables from the handle's spare blocks), so a
         # transfer of the previous chunk that is still in flight is not waited for
         statuses, words, offsets, self.timing = capi.batch_decode_device(
-            self.dev, files, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse)
+            self.dev, files, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
         # acm_batch_decode returns with its stream drained: d_pcm is complete and visible to torch's streams
         return d_pcm, offsets, words, statuses
 
@@ -126,8 +135,10 @@ def decode_sharded(files, decoder, dist=None, root=0, device=None, chunks=1, rin
 
     `files`: list of paths (str / PathLike: every rank can open them; only `root` needs the list) and/or file images
     (bytes: every rank must pass the same list - contents are never sent, only ids).
-    Returns on root: list of (status, np.uint16 array) in input order; on other ranks: None.
-    With dist=None runs single-process.  `decoder(list_of_bytes, out=None)` -> (pcm 1-D int16 tensor, offsets, words, statuses).
+    Returns on root: list of (status, np.uint16 array) in input order - np.float32 arrays where the decoder's `dtype` is torch.float32
+    (GpuDecoder(dtype=torch.float32)); on other ranks: None.
+    With dist=None runs single-process.  `decoder(list_of_bytes, out=None)` -> (pcm 1-D tensor of its dtype, offsets, words, statuses);
+    a decoder without a `dtype` attribute is taken to produce int16.
 
     Order of communication, identical on every rank (RCCL runs the operations of one communicator in issue order):
         C1  scatter_object_list of the shard table (ids and paths)
@@ -189,15 +200,17 @@ def decode_sharded(files, decoder, dist=None, root=0, device=None, chunks=1, rin
         meta = ([i for i, _ in part], [int(o) for o in offsets], [int(w) for w in words], [int(x) for x in statuses], used)
         return pcm, meta
 
+    dtype = getattr(decoder, "dtype", torch.int16)      # of every PCM buffer here: the decoder's samples, int16 or float32
+
     def new_buffer(words, like=None):
         if hasattr(decoder, "empty"):
             return decoder.empty(words)
-        return torch.empty(max(words, 1), dtype=torch.int16, device=device if device is not None else (like.device if like is not None else "cpu"))
+        return torch.empty(max(words, 1), dtype=dtype, device=device if device is not None else (like.device if like is not None else "cpu"))
 
     def to_host(t, words):
         """the first `words` of a PCM tensor as a host tensor (pinned + asynchronous for device memory)"""
         if t.is_cuda:
-            h = torch.empty(max(words, 1), dtype=torch.int16, pin_memory=True)
+            h = torch.empty(max(words, 1), dtype=dtype, pin_memory=True)
             h[:words].copy_(t[:words], non_blocking=True)
             return h
         return t[:words].clone()
@@ -282,7 +295,10 @@ def decode_sharded(files, decoder, dist=None, root=0, device=None, chunks=1, rin
     for r in range(world):
         for k, (ids_r, offs_r, words_r, st_r, _) in enumerate(metas[r]):
             h = own[k][1] if r == root else arrived.get((r, k))
-            host = h.numpy().view(np.uint16) if h is not None else np.zeros(0, np.uint16)
+            if dtype == torch.float32:
+                host = h.numpy() if h is not None else np.zeros(0, np.float32)
+            else:
+                host = h.numpy().view(np.uint16) if h is not None else np.zeros(0, np.uint16)
             for i, o, w, st in zip(ids_r, offs_r, words_r, st_r):
                 out[i] = (st, host[o:o + w].copy())
     return out

@@ -100,6 +100,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_packed_tile_rows", "acmhip_packed_group_rows", "acmhip_packed_slots", "acmhip_pack_bound", "acmhip_pack_tiles", "acmhip_unpack_tile",
     "acmhip_plan_create_packed", "acmhip_plan_bind_packed",
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
+    "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -145,6 +146,7 @@ def lib():
     L.acmhip_download.argtypes = [vp, vp, vp, sz]
     L.acmhip_memset.argtypes = [vp, vp, C.c_int, sz]
     L.acmhip_host_synth.argtypes = [C.POINTER(StreamDesc), vp, vp, vp, sz, C.c_uint, vp]
+    L.acmhip_host_synth_f32.argtypes = [C.POINTER(StreamDesc), vp, vp, vp, sz, vp]
     L.acmhip_set_host_synth_limit.argtypes = [C.c_uint64]
     L.acmhip_set_host_synth_limit.restype = None
     L.acmhip_host_synth_limit.restype = C.c_uint64
@@ -154,6 +156,7 @@ def lib():
     L.acmhip_plan_destroy.argtypes = [vp]
     L.acmhip_plan_destroy.restype = None
     L.acmhip_plan_launch.argtypes = [vp, vp, vp, vp, C.c_uint]
+    L.acmhip_plan_launch_f32.argtypes = [vp, vp, vp, vp]
     L.acmhip_plan_get_stats.argtypes = [vp, C.POINTER(PlanStats)]
     L.acmhip_plan_form_rows.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
     L.acmhip_plan_time.argtypes = [vp, vp, vp, vp, C.c_uint, C.c_int, C.POINTER(C.c_float)]
@@ -538,6 +541,10 @@ class Plan:
     def launch(self, d_idx, d_hdr, d_pcm, fmt=FMT_S16LE):
         _check(lib().acmhip_plan_launch(self.h, d_idx, d_hdr, d_pcm, fmt), "acmhip_plan_launch")
 
+    def launch_f32(self, d_idx, d_hdr, d_pcm):
+        """float32 samples (the s16le sample times 2^-15, exactly) into d_pcm; the descriptors' pcm_off / n_emit count floats"""
+        _check(lib().acmhip_plan_launch_f32(self.h, d_idx, d_hdr, d_pcm), "acmhip_plan_launch_f32")
+
     def time(self, d_idx, d_hdr, d_pcm, fmt=FMT_S16LE, reps=1):
         ms = C.c_float()
         _check(lib().acmhip_plan_time(self.h, d_idx, d_hdr, d_pcm, fmt, reps, C.byref(ms)), "acmhip_plan_time")
@@ -606,18 +613,20 @@ class Arena:
         self.patches = (Patch * len(self.patch_list))(*self.patch_list) if self.patch_list else None
 
 
-def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return_stats=False, patch_subset=None, packed=False, mform=False):
+def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return_stats=False, patch_subset=None, packed=False, mform=False,
+          f32=False):
     """Upload staged streams, run the hot path once, return one PCM array (uint16 view of the bytes) per stream.
     patch_subset (tests): keep only these entries of the batch's H1 patch list.
     packed: stage the packed form too (acmhip_pack_tiles) and bind it: whole tiles from row 0 are read from it.
-    mform: the same with the byte-plane form (acmhip_mform_rows) and the matrix-core build of the lean kernel."""
+    mform: the same with the byte-plane form (acmhip_mform_rows) and the matrix-core build of the lean kernel.
+    f32: acmhip_plan_launch_f32 instead (fmt is ignored): one float32 array per stream."""
     ar = Arena(staged_list, windows)
     if patch_subset is not None and ar.patch_list:
         ar.patch_list = [ar.patch_list[k] for k in patch_subset]
         ar.patches = (Patch * len(ar.patch_list))(*ar.patch_list) if ar.patch_list else None
     d_idx = dev.malloc(ar.idx.nbytes)
     d_hdr = dev.malloc(ar.hdr.nbytes)
-    d_pcm = dev.malloc(ar.pcm_words * 2)
+    d_pcm = dev.malloc(ar.pcm_words * (4 if f32 else 2))
     try:
         dev.upload(d_idx, ar.idx)
         dev.upload(d_hdr, ar.hdr)
@@ -639,8 +648,11 @@ def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return
             plan.bind_mform(*pk_ptrs)
         elif pk:
             plan.bind_packed(*pk_ptrs)
-        plan.launch(d_idx, d_hdr, d_pcm, fmt)
-        out = np.zeros(ar.pcm_words, dtype=np.uint16)
+        if f32:
+            plan.launch_f32(d_idx, d_hdr, d_pcm)
+        else:
+            plan.launch(d_idx, d_hdr, d_pcm, fmt)
+        out = np.zeros(ar.pcm_words, dtype=np.float32 if f32 else np.uint16)
         dev.download(out, d_pcm)
         st = plan.stats()
         plan.destroy()
@@ -661,6 +673,7 @@ BATCH_PCM_PINNED = 1
 BATCH_STAGE_PACKED = 2
 BATCH_STAGE_BYTEPLANE = 4
 BATCH_STAGE_INT16 = 8
+BATCH_PCM_F32 = 16
 
 
 def batch_decode(dev, files, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, pinned=False, prestage=False,
@@ -734,12 +747,15 @@ def batch_pcm_words(files, force_chans=0):
 
 
 def batch_decode_device(dev, files, d_pcm, d_pcm_words, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO,
-                        parse=PARSE_AUTO):
+                        parse=PARSE_AUTO, f32=False, batch_flags=0):
     """acm_batch_decode with device-resident output: PCM of stream k lands at d_pcm + 2*offsets[k] bytes.
+    f32=True: ACM_BATCH_PCM_F32 - float32 samples at d_pcm + 4*offsets[k] bytes (d_pcm_words counts floats then).
+    batch_flags: further ACM_BATCH_* bits (staging, block ranges).
 
     Returns (statuses, words, offsets, BatchTiming); nothing is copied back to the host."""
     bufs, items = _batch_items(files)
-    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA, d_pcm, d_pcm_words)
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | batch_flags | (BATCH_PCM_F32 if f32 else 0),
+                     d_pcm, d_pcm_words)
     tm = BatchTiming()
     _check(lib().acm_batch_decode(dev.h, items, len(files), C.byref(opts), C.byref(tm)), "acm_batch_decode")
     n = len(files)

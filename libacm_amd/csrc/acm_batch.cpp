@@ -385,6 +385,12 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 		opts = *opts_in;
 	if (opts.fmt > 3 || opts.parse > ACM_BATCH_PARSE_AUTO)
 		return ACMHIP_ERR_ARG;
+	/* float32 output: device-resident, the s16le samples scaled, every plan launched through acmhip_plan_launch_f32 */
+	const bool out_f32 = (opts.flags & ACM_BATCH_PCM_F32) != 0;
+	if (out_f32 && (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE || (opts.flags & ACM_BATCH_STAGE_PACKED))) {
+		acmhip_set_error_text("ACM_BATCH_PCM_F32: device-resident output (opts->d_pcm), ACMHIP_FMT_S16LE and no ACM_BATCH_STAGE_PACKED");
+		return ACMHIP_ERR_ARG;
+	}
 	/* parsed ahead of time (acm_batch_prestage): must be these very items */
 	const acm_batch_prestaged *pre = opts.prestaged;
 	if (pre) {
@@ -723,6 +729,11 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 		d_pcm = static_cast<int16_t *>(opts.d_pcm);
 	else
 		BTRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, pcm_arena_words * sizeof(int16_t), (void **)&d_pcm));
+	/* every synthesis launch of the batch: block ranges, chunks and the host redo of what the device parser gave up on */
+	auto launch_plan = [&](acmhip_plan *plan) -> int {
+		return out_f32 ? acmhip_plan_launch_f32(plan, d_idx, d_hdr, reinterpret_cast<float *>(d_pcm))
+			       : acmhip_plan_launch(plan, d_idx, d_hdr, d_pcm, opts.fmt);
+	};
 	const size_t jobs_bytes = round_up(dev_ids.size() * sizeof(AcmParseJob), 64);
 	const size_t res_bytes = dev_ids.size() * (sizeof(AcmParseResult) + sizeof(uint32_t));  /* results, then flags */
 	/* block ranges: the files go up in R stripes (stripe s of every file back to back: one transfer, then a scatter kernel),
@@ -1209,7 +1220,7 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 			RTRY(hipStreamWaitEvent(st_main, rg.ev[1], 0));
 			RTRY(hipEventRecord(rg.ev[0], st_main));
 			if (rg.plan) {
-				const int pr = acmhip_plan_launch(rg.plan, d_idx, d_hdr, d_pcm, opts.fmt);
+				const int pr = launch_plan(rg.plan);
 				if (pr != ACMHIP_OK)
 					return pr;
 			}
@@ -1458,7 +1469,7 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 				}
 			}
 			HTRY(hipEventRecord(ch.ev[1], st_main));
-			BTRY(acmhip_plan_launch(ch.plan, d_idx, d_hdr, d_pcm, opts.fmt));
+			BTRY(launch_plan(ch.plan));
 			HTRY(hipEventRecord(ch.ev[2], st_main));
 			HTRY(hipStreamWaitEvent(st_copy, ch.ev[2], 0));
 			HTRY(hipEventRecord(ch.ev[3], st_copy));
@@ -1526,9 +1537,9 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 			if (!descs.empty()) {
 				acmhip_plan *fix = nullptr;
 				BTRY(acmhip_plan_create(dev, descs.data(), descs.size(), patches.data(), patches.size(), opts.plan_flags, &fix));
-				rc = acmhip_plan_launch(fix, d_idx, d_hdr, d_pcm, opts.fmt);
+				rc = launch_plan(fix);
 				for (size_t i : live)
-					if (rc == ACMHIP_OK && items[i].pcm) {
+					if (rc == ACMHIP_OK && items[i].pcm && !out_f32) {
 						const uint64_t w = std::min<uint64_t>(items[i].words, items[i].pcm_cap);
 						if (hipMemcpyAsync(h_pcm + slots[i].pcm_off, d_pcm + slots[i].pcm_off, w * sizeof(int16_t), hipMemcpyDeviceToHost, st_main) != hipSuccess)
 							rc = acmhip_report_hip((int)hipGetLastError(), "fix-up read-back");
@@ -1541,7 +1552,7 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 					return rc;
 				}
 				for (size_t i : live)
-					if (items[i].pcm)
+					if (items[i].pcm && !out_f32)
 						memcpy(items[i].pcm, h_pcm + slots[i].pcm_off, std::min<uint64_t>(items[i].words, items[i].pcm_cap) * sizeof(int16_t));
 			}
 			BNOTE("fix-up of %zu flagged streams done", redo.size());

@@ -137,7 +137,9 @@ int acmhip_aux_stream(acmhip_device *dev, int k, void **out);    /* batch pipeli
 int acmhip_report_hip(int hip_error, const char *what);
 void acmhip_set_error_text(const char *text);                    /* what acmhip_last_error() returns on this thread */          /* records the text, returns ACMHIP_ERR_HIP */
 
-/* launchers implemented in acm_kernels.hip; `stream` is a hipStream_t */
+/* launchers implemented in acm_kernels.hip; `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
+ * d_pcm (and d_sink) then hold floats and the streams' pcm_off / n_emit count them (acmhip_plan_launch_f32) */
+#define ACMK_FMT_F32 0x100u
 int acmk_tuning_build(void);                                     /* 1 if the library was built with -DACM_TUNING (its environment switches are live) */
 int acmk_warmup(void *stream);                                   /* an empty launch: makes the runtime load the kernels' code object */
 int acmk_fused_variants(void);                                   /* number of fused-kernel variants built in */
@@ -149,6 +151,7 @@ int acmk_launch_fused(uint32_t level, int variant, int cus, int carry, const Acm
 int acmk_tile2_rows(uint32_t level);                            /* rows per acm_tile2 tile, 0 if the level is not covered */
 int acmk_tile2_grid(uint32_t level, int cus);
 #define ACM_K2_SINK_BYTES 65536                               /* >= one tile of PCM: where lead-in tiles put theirs */
+#define ACM_K2_SINK_F32_BYTES (2 * ACM_K2_SINK_BYTES)         /* ... of float32 PCM */
 int acmk_launch_tile2(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm,
 		      int16_t *d_sink, unsigned fmt, void *stream);
 /* the packed staged form (include/acm_hip.h): same tiles as acm_tile2 (records with idx_off = the tile's first entry in the chunk table and
@@ -209,6 +212,19 @@ int acmk_launch_small(uint32_t level, const AcmDevStream *d_streams, const uint3
 		      const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_emit(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
 		     const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream);
+/* the float32 builds (acm_kernels_f32.hip), reached through fmt | ACMK_FMT_F32 of the launchers above */
+int acmk_launch_fused_f32(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
+			  uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
+int acmk_launch_tile2_f32(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
+			  int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
+int acmk_launch_tile2m_f32(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
+			   const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
+int acmk_launch_fused_plane_f32(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
+				const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream);
+int acmk_launch_small_f32(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
+			  const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
+int acmk_launch_emit_f32(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
+			 const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream);
 #ifdef __cplusplus
 }
 #endif

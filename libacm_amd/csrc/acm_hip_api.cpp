@@ -1015,7 +1015,7 @@ extern "C" int acmhip_plan_create_packed(acmhip_device *dev, const acmhip_stream
 			g.ntiles = (uint32_t)use.size();
 			rc = to_device(pl, use, &g.d_tiles);
 			if (k2 && rc == ACMHIP_OK && !pl->d_sink)
-				rc = plan_malloc(pl, (void **)&pl->d_sink, ACM_K2_SINK_BYTES);
+				rc = plan_malloc(pl, (void **)&pl->d_sink, ACM_K2_SINK_F32_BYTES);      /* (a float32 launch stores twice the bytes) */
 			if (k2 && rc == ACMHIP_OK) {
 				g.ntiles2 = (uint32_t)tiles2[lv].size();
 				rc = to_device(pl, tiles2[lv], &g.d_tiles2);
@@ -1146,11 +1146,9 @@ extern "C" int acmhip_plan_get_stats(const acmhip_plan *plan, acmhip_plan_stats 
 	if (e_ > 0) return hip_fail((hipError_t)e_, #call); \
 	set_err("%s: unsupported configuration", #call); return ACMHIP_ERR_ARG; } } while (0)
 
-extern "C" int acmhip_plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
-				  int16_t *d_pcm, unsigned fmt)
+/* fmt: ACMHIP_FMT_*, or ACMK_FMT_F32 for float32 samples (d_pcm then holds floats) */
+static int plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt)
 {
-	if (!pl || fmt > 3)
-		return ACMHIP_ERR_ARG;
 	void *st = (void *)pl->dev->stream;
 	if (pl->ev_upload)
 		HIPTRY(hipStreamWaitEvent(pl->dev->stream, pl->ev_upload, 0));
@@ -1232,6 +1230,25 @@ extern "C" int acmhip_plan_launch(acmhip_plan *pl, const int16_t *d_idx, const a
 		}
 	}
 	return ACMHIP_OK;
+}
+
+extern "C" int acmhip_plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
+				  int16_t *d_pcm, unsigned fmt)
+{
+	if (!pl || fmt > 3)
+		return ACMHIP_ERR_ARG;
+	return plan_launch(pl, d_idx, d_hdr, d_pcm, fmt);
+}
+
+extern "C" int acmhip_plan_launch_f32(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, float *d_pcm)
+{
+	if (!pl)
+		return ACMHIP_ERR_ARG;
+	if (pl->pk_chunks) {
+		set_err("acmhip_plan_launch_f32: a packed arena is bound (acmhip_plan_bind_packed); the packed form has no float32 build");
+		return ACMHIP_ERR_ARG;
+	}
+	return plan_launch(pl, d_idx, d_hdr, reinterpret_cast<int16_t *>(d_pcm), ACMK_FMT_F32);
 }
 
 extern "C" int acmhip_plan_bind_packed(acmhip_plan *pl, const acmhip_packed_chunk *d_chunks, const uint8_t *d_blob)

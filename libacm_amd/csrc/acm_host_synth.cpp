@@ -109,6 +109,13 @@ inline void emit(const uint32_t *w, size_t n, unsigned level, unsigned fmt, int1
 	}
 }
 
+/* float32 output (acmhip_host_synth_f32): the s16le sample times 2^-15, exact */
+inline void emit_f32(const uint32_t *w, size_t n, unsigned level, float *dst)
+{
+	for (size_t k = 0; k < n; k++)
+		dst[k] = (float)(int16_t)(uint16_t)((uint32_t)((int32_t)w[k] >> level)) * 0x1p-15f;
+}
+
 } // namespace
 
 extern "C" void acmhip_set_host_synth_limit(uint64_t samples)
@@ -121,23 +128,36 @@ extern "C" uint64_t acmhip_host_synth_limit(void)
 	return g_host_limit.load();
 }
 
+/* pcm_f32: float32 output into it instead of pcm (fmt is ACMHIP_FMT_S16LE then) */
 static int host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acmhip_blkhdr *hdr,
-		      const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm);
+		      const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm, float *pcm_f32);
 
 extern "C" int acmhip_host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acmhip_blkhdr *hdr,
 				 const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm)
 {
 	try {
-		return host_synth(s, idx, hdr, patches, npatches, fmt, pcm);
+		return host_synth(s, idx, hdr, patches, npatches, fmt, pcm, nullptr);
 	} catch (...) {
 		return ACMHIP_ERR_NOMEM;        /* (tile buffers, the patch list, threads: nothing else in there throws) */
 	}
 }
 
-static int host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acmhip_blkhdr *hdr,
-		      const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm)
+extern "C" int acmhip_host_synth_f32(const acmhip_stream_desc *s, const int16_t *idx, const acmhip_blkhdr *hdr,
+				     const acmhip_patch *patches, size_t npatches, float *pcm)
 {
-	if (!s || (!idx && s->nrows) || !hdr || (!pcm && s->n_emit) || (!patches && npatches) || fmt > ACMHIP_FMT_U16BE ||
+	if (!pcm && s && s->n_emit)
+		return ACMHIP_ERR_ARG;
+	try {
+		return host_synth(s, idx, hdr, patches, npatches, ACMHIP_FMT_S16LE, nullptr, pcm);
+	} catch (...) {
+		return ACMHIP_ERR_NOMEM;
+	}
+}
+
+static int host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acmhip_blkhdr *hdr,
+		      const acmhip_patch *patches, size_t npatches, unsigned fmt, int16_t *pcm, float *pcm_f32)
+{
+	if (!s || (!idx && s->nrows) || !hdr || (!pcm && !pcm_f32 && s->n_emit) || (!patches && npatches) || fmt > ACMHIP_FMT_U16BE ||
 	    s->level > 15 || s->rows == 0 || s->rows > 4095)
 		return ACMHIP_ERR_ARG;
 	const unsigned level = s->level;
@@ -149,7 +169,8 @@ static int host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acm
 		return ACMHIP_OK;
 	const int16_t *src = idx + s->idx_off;
 	const acmhip_blkhdr *h = hdr + s->hdr_off;
-	int16_t *dst = pcm + s->pcm_off;
+	int16_t *dst = pcm_f32 ? nullptr : pcm + s->pcm_off;
+	float *dst_f32 = pcm_f32 ? pcm_f32 + s->pcm_off : nullptr;
 
 	/* H1 patches (include/acm_hip.h): sorted by sample so that a tile finds its own with one search */
 	std::vector<acmhip_patch> ps(patches, patches + npatches);
@@ -202,7 +223,10 @@ static int host_synth(const acmhip_stream_desc *s, const int16_t *idx, const acm
 			const size_t skip = (size_t)(r0 - rh) * cols;
 			const uint64_t first = (r0 - s->row_begin) << level;
 			const size_t want = (size_t)std::min<uint64_t>((r1 - r0) << level, s->n_emit - first);
-			emit(base + skip, want, level, fmt, dst + first);
+			if (dst_f32)
+				emit_f32(base + skip, want, level, dst_f32 + first);
+			else
+				emit(base + skip, want, level, fmt, dst + first);
 		}
 	};
 	/* (a thread per 2 Msamples, eight at most, never more than the machine has; short windows - the first ones of every stream - stay on

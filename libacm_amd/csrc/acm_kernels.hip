@@ -52,6 +52,32 @@
 #define ACM_L13_GROUPS 2, 3, 3, 3, 2
 #endif
 
+/*
+ * Output type.  This file is compiled twice: as itself (int16 samples, the ACMHIP_FMT_* writers) and with ACM_OUT_F32 = 1 from
+ * acm_kernels_f32.hip (float32 samples for acmhip_plan_launch_f32: every synthesis kernel under a name of its own, its launcher with
+ * an _f32 suffix).  The float branches of a kernel are `if constexpr (F32)`, and the float builds live in a translation unit of their
+ * own, so the int16 builds are exactly what they were: a second caller of the shared inline helpers in the same module changes how the
+ * compiler schedules the int16 kernels, even where nothing in their text changed.
+ */
+#ifndef ACM_OUT_F32
+#define ACM_OUT_F32 0
+#endif
+#if ACM_OUT_F32
+#define ACM_K_EMIT acm_sw_emit_f32
+#define ACM_K_SMALL acm_small_level_f32
+#define ACM_K_FUSED acm_fused_tile_f32
+#define ACM_K_TILE2 acm_f32_tile2              /* (names outside tests/test_isa_invariants.py's scan: tests/test_pcm_f32.py checks them) */
+#define ACM_K_CHUNK acm_f32_chunk
+#define ACMK_OUT(name) name##_f32
+#else
+#define ACM_K_EMIT acm_sw_emit
+#define ACM_K_SMALL acm_small_level
+#define ACM_K_FUSED acm_fused_tile
+#define ACM_K_TILE2 acm_tile2
+#define ACM_K_CHUNK acm_chunk
+#define ACMK_OUT(name) name
+#endif
+
 namespace {
 
 // ---------------------------------------------------------------------------
@@ -68,11 +94,38 @@ __device__ __forceinline__ uint32_t pcm16(int32_t v, int level, unsigned fmt)
 	return w;
 }
 
+/*
+ * float32 output (acmhip_plan_launch_f32): the ACMHIP_FMT_S16LE sample times 2^-15, exact in float32.  The kernels run their
+ * int16 write-out unchanged up to the last register and widen there: a dword of two packed little-endian samples becomes two
+ * floats by v_cvt_f32_i32 with SDWA WORD_0 / WORD_1 (sign-extending) and one v_pk_mul_f32 - 1.5 VALU operations per sample.
+ */
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ v2f pcm_pair_f32(uint32_t w)
+{
+	const v2f f = { (float)(int32_t)(int16_t)(w & 0xFFFFu), (float)((int32_t)w >> 16) };
+	return f * 0x1p-15f;
+}
+
+/* four samples (two packed dwords) as one 16-byte float piece */
+__device__ __forceinline__ v4f pcm_quad_f32(uint32_t a, uint32_t b)
+{
+	const v2f x = pcm_pair_f32(a), y = pcm_pair_f32(b);
+	return v4f{ x.x, x.y, y.x, y.y };
+}
+
+__device__ __forceinline__ float pcm_one_f32(int32_t v, int level)
+{
+	return (float)(int32_t)(int16_t)(uint16_t)pcm16(v, level, ACMHIP_FMT_S16LE) * 0x1p-15f;
+}
+
 // ---------------------------------------------------------------------------
 // stage-wise family
 // ---------------------------------------------------------------------------
 constexpr int SW_THREADS = 256;
 
+#if !ACM_OUT_F32                /* (the int32-plane kernels write no PCM: int16 translation unit only) */
 __global__ void __launch_bounds__(SW_THREADS)
 acm_sw_unpack(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict__ list,
 	      const int16_t *__restrict__ idx, const acmhip_blkhdr *__restrict__ hdr,
@@ -124,6 +177,7 @@ acm_sw_stage(const AcmDevStream *__restrict__ streams, const uint32_t *__restric
 		yo[e] = y;
 	}
 }
+#endif
 
 /*
  * Levels 13-15 without H1 patches: unpack and the first J = level - 12 stages in one sweep, 2 B in and 4 B out per sample
@@ -210,15 +264,19 @@ acm_sw_prefix(const AcmDevStream *__restrict__ streams, const uint32_t *__restri
 }
 
 __global__ void __launch_bounds__(SW_THREADS)
-acm_sw_emit(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict__ list,
-	    const int32_t *__restrict__ x, int16_t *__restrict__ pcm, unsigned fmt)
+ACM_K_EMIT(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict__ list,
+	   const int32_t *__restrict__ x, int16_t *__restrict__ pcm, unsigned fmt)
 {
 	const AcmDevStream s = streams[list[blockIdx.y]];
 	const int32_t *src = x + s.scratch_off + ((uint64_t)(s.row_begin - s.halo_row) << s.level);
 	uint16_t *dst = (uint16_t *)pcm + s.pcm_off;
 	for (uint64_t e = (uint64_t)blockIdx.x * SW_THREADS + threadIdx.x; e < s.n_emit;
-	     e += (uint64_t)gridDim.x * SW_THREADS)
-		dst[e] = (uint16_t)pcm16(src[e], (int)s.level, fmt);
+	     e += (uint64_t)gridDim.x * SW_THREADS) {
+		if constexpr (ACM_OUT_F32)
+			reinterpret_cast<float *>(pcm)[s.pcm_off + e] = pcm_one_f32(src[e], (int)s.level);
+		else
+			dst[e] = (uint16_t)pcm16(src[e], (int)s.level, fmt);
+	}
 }
 
 // ---------------------------------------------------------------------------
@@ -265,10 +323,12 @@ __device__ __forceinline__ void sl_stages(uint32_t (&x)[SL_K + sl_halo(L)], cons
 
 template <int L>
 __global__ void __launch_bounds__(SL_THREADS)
-acm_small_level(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict__ list,
+ACM_K_SMALL(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict__ list,
 		const int16_t *__restrict__ idx, const acmhip_blkhdr *__restrict__ hdr,
 		int16_t *__restrict__ pcm, unsigned fmt)
 {
+	constexpr bool F32 = ACM_OUT_F32;
+
 	constexpr int COLS = 1 << L, H = sl_halo(L), N = SL_K + H;
 	static_assert(H % COLS == 0 && N % COLS == 0 && N % 8 == 0, "whole rows, whole 16-byte loads");
 	const AcmDevStream s = streams[list[blockIdx.y]];
@@ -325,8 +385,22 @@ acm_small_level(const AcmDevStream *__restrict__ streams, const uint32_t *__rest
 		}
 		/* the stages, highest position first so that every tap is still the previous stage's value */
 		sl_stages<L, 0>(x, e0);
-		/* write-out (decode.c:617-655): 32 samples = 64 bytes */
-		if (g0 + SL_K <= s.n_emit) {
+		/* write-out (decode.c:617-655): 32 samples = 64 bytes (float32: 128 bytes) */
+		if constexpr (F32) {
+			float *fdst = reinterpret_cast<float *>(pcm) + s.pcm_off;
+			if (g0 + SL_K <= s.n_emit) {
+				v4f *o = reinterpret_cast<v4f *>(fdst + g0);
+#pragma unroll
+				for (int v = 0; v < SL_K / 4; v++)
+					o[v] = pcm_quad_f32(pcm16((int32_t)x[H + v * 4], L, ACMHIP_FMT_S16LE) | pcm16((int32_t)x[H + v * 4 + 1], L, ACMHIP_FMT_S16LE) << 16,
+							    pcm16((int32_t)x[H + v * 4 + 2], L, ACMHIP_FMT_S16LE) | pcm16((int32_t)x[H + v * 4 + 3], L, ACMHIP_FMT_S16LE) << 16);
+			} else {
+#pragma unroll
+				for (int k = 0; k < SL_K; k++)
+					if (g0 + k < s.n_emit)
+						fdst[g0 + k] = pcm_one_f32((int32_t)x[H + k], L);
+			}
+		} else if (g0 + SL_K <= s.n_emit) {
 			uint4 *o = reinterpret_cast<uint4 *>(dst + g0);
 #pragma unroll
 			for (int v = 0; v < SL_K / 8; v++) {
@@ -972,12 +1046,15 @@ constexpr int PRIO_IDLE = 0, PRIO_FIRST_PASS = ACM_PRIO_FIRST, PRIO_LDS_PASSES =
  * C: tile configuration; G0, Gs...: how the `level` stages are grouped into passes (first pass fed from
  * HBM, the others in LDS).
  */
+/* F32 (acm_fused_tile_f32): float32 samples, written from the same parked int16 pairs */
 template <class C, int WAVES_PER_SIMD, int ABL, int W0, bool CARRY, int G0, int... Gs>
 __global__ void __launch_bounds__(C::NT, WAVES_PER_SIMD)
-acm_fused_tile(const AcmDevStream *__restrict__ streams, const AcmTile *__restrict__ tiles, const uint32_t ntiles,
+ACM_K_FUSED(const AcmDevStream *__restrict__ streams, const AcmTile *__restrict__ tiles, const uint32_t ntiles,
 	       const int16_t *__restrict__ idx, const acmhip_blkhdr *__restrict__ hdr,
 	       int16_t *__restrict__ pcm, unsigned fmt)
 {
+	constexpr bool F32 = ACM_OUT_F32;
+
 	constexpr int L = C::L, NT = C::NT, COLS = C::COLS, NELEM = C::NELEM, TR = C::TR, NJ_LAST = C::NJ_LAST;
 	constexpr bool NEG_ODD_ROWS = StageKind<L, 0>::N;       // stage 0 wants odd tile rows negated
 	static_assert(!(ABL & MODE_PLANE) || !NEG_ODD_ROWS, "a plane comes with plain signs");
@@ -1004,7 +1081,7 @@ acm_fused_tile(const AcmDevStream *__restrict__ streams, const AcmTile *__restri
 		TileCtx c;
 		c.src = (ABL & MODE_PLANE) ? reinterpret_cast<const int16_t *>(reinterpret_cast<const int32_t *>(idx) + s.idx_off) : idx + s.idx_off;
 		c.hdr = hdr + s.hdr_off;
-		c.dst = reinterpret_cast<uint16_t *>(pcm) + s.pcm_off;
+		c.dst = F32 ? reinterpret_cast<uint16_t *>(reinterpret_cast<float *>(pcm) + s.pcm_off) : reinterpret_cast<uint16_t *>(pcm) + s.pcm_off;
 		c.n_emit = s.n_emit;
 		c.row_first = (int)tl.row0 - HALO;
 		c.nrows = (int)s.nrows;
@@ -1098,7 +1175,7 @@ acm_fused_tile(const AcmDevStream *__restrict__ streams, const AcmTile *__restri
 		ACM_STAMP(2);
 		phase_prio<PRIO, PRIO_LDS_PASSES>();
 		if (!(ABL & 8))
-			run_lds_passes<C, ABL, CARRY, G0, Gs...>(tile, tid, fmt, carry_mem);
+			run_lds_passes<C, ABL, CARRY, G0, Gs...>(tile, tid, F32 ? (unsigned)ACMHIP_FMT_S16LE : fmt, carry_mem);
 		phase_prio<PRIO, PRIO_IDLE>();
 		ACM_STAMP(3);
 		__syncthreads();
@@ -1111,7 +1188,23 @@ acm_fused_tile(const AcmDevStream *__restrict__ streams, const AcmTile *__restri
 			constexpr int PER_OWNER = NJ_LAST / 8;          /* pieces per parking area */
 			const uint64_t g0 = (uint64_t)(uint32_t)(cur.row_first + HALO - cur.row_begin) << L;   /* first payload sample */
 			const bool whole = (cur.row_first + TR <= cur.nrows) && (g0 + (uint64_t)(TR - HALO) * COLS <= cur.n_emit);
-			if (whole) {
+			if (F32 && whole) {
+				/* float32: 16-byte float piece fv is half fv & 1 of int16 piece fv >> 1, so that every store instruction
+				 * covers contiguous bytes across the workgroup */
+				v4f *out = reinterpret_cast<v4f *>(reinterpret_cast<float *>(cur.dst) + g0);
+#pragma unroll
+				for (int k = 0; k < (2 * NVEC + NT - 1) / NT; k++) {
+					const int fv = tid + k * NT;
+					if (k < 2 * NVEC / NT || fv < 2 * NVEC) {
+						const int owner = (HALO * COLS / 8 + fv / 2) / PER_OWNER;
+						const int piece = (HALO * COLS / 8 + fv / 2) % PER_OWNER;
+						const uint32_t *q = tile + lds_at<C::PS>(owner * NJ_LAST) + piece * park_piece<NJ_LAST>() + 2 * (fv & 1);
+						const uint32_t a = q[0], b = q[1];
+						if (!(ABL & 16) || a == 0x12345u)
+							out[fv] = pcm_quad_f32(a, b);
+					}
+				}
+			} else if (whole) {
 				/* interior tile (the common case): no per-piece checks, 32-bit offsets from a uniform base */
 				uint4 *out = reinterpret_cast<uint4 *>(cur.dst + g0);
 #pragma unroll
@@ -1144,7 +1237,16 @@ acm_fused_tile(const AcmDevStream *__restrict__ streams, const AcmTile *__restri
 					const int owner = ml / NJ_LAST;
 					const uint32_t *q = tile + lds_at<C::PS>(owner * NJ_LAST) + (ml % NJ_LAST) / 8 * park_piece<NJ_LAST>();
 					const uint32_t w[4] = { q[0], q[1], q[2], q[3] };
-					if (g + 8 <= cur.n_emit) {
+					if constexpr (F32) {
+						float *fd = reinterpret_cast<float *>(cur.dst) + g;
+						if (g + 8 <= cur.n_emit) {
+							reinterpret_cast<v4f *>(fd)[0] = pcm_quad_f32(w[0], w[1]);
+							reinterpret_cast<v4f *>(fd)[1] = pcm_quad_f32(w[2], w[3]);
+						} else {
+							for (int e = 0; e < 8 && g + e < cur.n_emit; e++)
+								fd[e] = (float)(int32_t)(int16_t)(w[e >> 1] >> ((e & 1) * 16)) * 0x1p-15f;
+						}
+					} else if (g + 8 <= cur.n_emit) {
 						*reinterpret_cast<uint4 *>(cur.dst + g) = make_uint4(w[0], w[1], w[2], w[3]);
 					} else {
 						for (int e = 0; e < 8 && g + e < cur.n_emit; e++)
@@ -1188,20 +1290,20 @@ struct FusedEntry {
 };
 
 template <class C, int W, int... Gs>
-constexpr FusedEntry entry() { return FusedEntry{ acm_fused_tile<C, W, 0, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+constexpr FusedEntry entry() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
 /* same with two adjacent columns per lane in the first pass (4-byte HBM loads) */
 template <class C, int W, int... Gs>
-constexpr FusedEntry entry2() { return FusedEntry{ acm_fused_tile<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+constexpr FusedEntry entry2() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
 /* ... plus the carry-mode build of the same geometry (no halo rows; see ACM_TILE_*) */
 template <class C, int W, int... Gs>
-constexpr FusedEntry entry2c() { return FusedEntry{ acm_fused_tile<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT,
-						     acm_fused_tile<C, W, 0, 2, true, Gs...> }; }
+constexpr FusedEntry entry2c() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT,
+						     ACM_K_FUSED<C, W, 0, 2, true, Gs...> }; }
 #ifdef ACM_ABLATION
 /* timing-only builds of the level-7 and level-9 kernels with parts removed (wrong output by design) */
 template <class C, int W, int ABL, int... Gs>
-constexpr FusedEntry abl2() { return FusedEntry{ acm_fused_tile<C, W, ABL, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+constexpr FusedEntry abl2() { return FusedEntry{ ACM_K_FUSED<C, W, ABL, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
 template <class C, int W, int ABL, int... Gs>
-constexpr FusedEntry abl() { return FusedEntry{ acm_fused_tile<C, W, ABL, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+constexpr FusedEntry abl() { return FusedEntry{ ACM_K_FUSED<C, W, ABL, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
 #endif
 
 /* variants 1.. are tuning aids (geometry sweeps: -DACM_TUNING; timing-only ablations: -DACM_ABLATION, which implies it) */
@@ -2024,6 +2126,37 @@ struct FirstPassZW {
 #error "acm_kernels.hip: gfx950 (MI355X) only - the hand-counted s_waitcnt vmcnt(N) of acm_tile2 assumes in-order vector memory returns"
 #endif
 
+/*
+ * The float32 write-out of the lean kernels (acm_f32_tile2 over a workgroup of NP lanes, acm_f32_chunk over a wavefront): 2 x NSTORE
+ * rounds of 16-byte float pieces, twice the int16 build's stores.  Piece fv is half fv & 1 of the parked int16 piece fv / 2, so that
+ * every store instruction covers contiguous bytes across the wavefront.  Round k's LDS and HBM addresses are the lane's round-0 ones
+ * plus constants, and an empty asm statement makes the compiler form them inside the tile loop: hoisted out of it (2 x NSTORE of each)
+ * they pushed the builds that sit at 128 registers into scratch.  Two pieces at a time are in registers (the next tile's staged
+ * indices are in flight meanwhile).
+ */
+template <class C, int NP, int NSTORE, int ABL>
+__device__ __forceinline__ void lean_store_f32(const uint32_t *tile, const int lane, float *out)
+{
+	constexpr int NJ_LAST = C::NJ_LAST, PER_OWNER = NJ_LAST / 8;
+	static_assert((NP / 2) % PER_OWNER == 0 && NJ_LAST % (1 << C::PS) == 0, "round k's LDS address is round 0's plus a constant");
+	constexpr int DQ = (NP / 2 / PER_OWNER) * (NJ_LAST + (NJ_LAST >> C::PS));      /* dwords from one round's pieces to the next's */
+	const int v0 = lane / 2;
+	uint32_t qa = (uint32_t)(lds_at<C::PS>((v0 / PER_OWNER) * NJ_LAST) + (v0 % PER_OWNER) * park_piece<NJ_LAST>() + 2 * (lane & 1));
+	uint32_t oa = (uint32_t)lane * 16u;
+	asm volatile("" : "+v"(qa), "+v"(oa));
+#pragma unroll
+	for (int k = 0; k < 2 * NSTORE; k++) {
+		const uint32_t *q = tile + qa + k * DQ;
+		const uint32_t a = q[0], b = q[1];
+		if ((ABL & 16) && a != 0x12345u)               /* timing-only build: no stores */
+			continue;
+		v4f *o = reinterpret_cast<v4f *>(reinterpret_cast<char *>(out) + oa + (uint32_t)(k * NP * 16));
+		__builtin_nontemporal_store(pcm_quad_f32(a, b), o);
+		if (k % 2)
+			__builtin_amdgcn_sched_barrier(0);
+	}
+}
+
 template <int YOUNGER>
 __device__ __forceinline__ void k2_wait()
 {
@@ -2031,12 +2164,17 @@ __device__ __forceinline__ void k2_wait()
 	asm volatile("s_waitcnt vmcnt(%0)" :: "n"(YOUNGER) : "memory");
 }
 
-/* MFORM: idx is the byte-plane staged form and the first pass runs on the matrix cores (FirstPassM); everything else is the same */
+/* MFORM: idx is the byte-plane staged form and the first pass runs on the matrix cores (FirstPassM); everything else is the same.
+ * F32 (acm_f32_tile2): float32 samples (pcm and sink hold floats), written from the same parked int16 pairs - twice the stores,
+ * counted the same way; the float builds' name stays out of the int16 builds' (tests/test_isa_invariants.py checks those as they
+ * are, tests/test_pcm_f32.py the float builds with their doubled stores) */
 template <class C, int WPS, int ABL, bool MFORM, int G0, int... Gs>
 __global__ void __launch_bounds__(C::NT, WPS)
-acm_tile2(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16_t *__restrict__ idx, const uint32_t *__restrict__ pairs,
+ACM_K_TILE2(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16_t *__restrict__ idx, const uint32_t *__restrict__ pairs,
 	  const acmhip_blkhdr *__restrict__ hdr, int16_t *__restrict__ pcm, int16_t *__restrict__ sink, const unsigned fmt)
 {
+	constexpr bool F32 = ACM_OUT_F32;
+
 	constexpr int L = C::L, NT = C::NT, COLS = C::COLS, NELEM = C::NELEM, TR = C::TR, NJ_LAST = C::NJ_LAST;
 	using FP = std::conditional_t<MFORM, std::conditional_t<G0 == 6, FirstPassZW<C>, FirstPassM<C, (G0 == 4 ? 4 : 3)>>, FirstPass2<C, G0, 2, ABL>>;
 	static_assert(!MFORM || G0 == 3 || G0 == 4 || G0 == 6, "coefficient tables exist for a first pass of three, four or six stages");
@@ -2152,12 +2290,16 @@ acm_tile2(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16
 		load_tile(raw, nxt, dnxt);
 		phase_prio<PRIO, PRIO_LDS_PASSES>();            /* until the PCM stores are issued */
 		if (!(ABL & 8))
-			run_lds_passes<C, ABL, true, G0, Gs...>(tile, tid, fmt, carry_mem);
+			run_lds_passes<C, ABL, true, G0, Gs...>(tile, tid, F32 ? (unsigned)ACMHIP_FMT_S16LE : fmt, carry_mem);
 		ACM_STAMP(3);
 		__syncthreads();
 		ACM_STAMP(4);
 
-		{
+		if constexpr (F32) {
+			/* (a lead-in tile stores into the sink, as below) */
+			float *out = discard ? reinterpret_cast<float *>(sink) : reinterpret_cast<float *>(pcm) + cur.pcm_off;
+			lean_store_f32<C, NT, NSTORE, ABL>(tile, tid, out);
+		} else {
 			/* a lead-in tile stores too - into a sink nobody reads - so that every iteration issues the same vector
 			 * memory operations and ONE counted wait serves them all */
 			typedef uint32_t v4u __attribute__((ext_vector_type(4)));
@@ -2178,7 +2320,7 @@ acm_tile2(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16
 		 * stores may still be on their way.  (Waiting here, inside the iteration that issued the loads, keeps the loaded
 		 * registers out of any copy the compiler places on the loop's back edge.) */
 		phase_prio<PRIO, PRIO_IDLE>();
-		k2_wait<NSTORE>();
+		k2_wait<F32 ? 2 * NSTORE : NSTORE>();
 		ACM_STAMP(6);
 		if (!more)
 			break;
@@ -2898,12 +3040,15 @@ struct FirstPassZ {
 	}
 };
 
-/* Gs: the LDS passes behind the six matrix-core stages (they add up to level - 6) */
+/* Gs: the LDS passes behind the six matrix-core stages (they add up to level - 6).  F32 (acm_f32_chunk): float32 samples, as in
+ * acm_f32_tile2 */
 template <int L_, int ABL, int... Gs>
 __global__ void __launch_bounds__(64 * FirstPassZ<L_>::NW, 1)
-acm_chunk(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16_t *__restrict__ idx, const uint32_t *__restrict__ pairs,
+ACM_K_CHUNK(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16_t *__restrict__ idx, const uint32_t *__restrict__ pairs,
 	  const acmhip_blkhdr *__restrict__ hdr, int16_t *__restrict__ pcm, int16_t *__restrict__ sink, const unsigned fmt)
 {
+	constexpr bool F32 = ACM_OUT_F32;
+
 	using FP = FirstPassZ<L_>;
 	using C = typename FP::C;
 	constexpr int L = L_, COLS = C::COLS, NELEM = C::NELEM, TR = C::TR, NJ_LAST = C::NJ_LAST, NW = FP::NW;
@@ -3065,10 +3210,13 @@ acm_chunk(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16
 		const uint32_t sv_nx2 = val_of(nx2);
 		ACM_STAMP(2);
 		phase_prio<true, PRIO_LDS_PASSES>();
-		run_lds_passes<C, PASS_ABL, true, FP::G, Gs...>(tile, lane, fmt, carry_mem);
+		run_lds_passes<C, PASS_ABL, true, FP::G, Gs...>(tile, lane, F32 ? (unsigned)ACMHIP_FMT_S16LE : fmt, carry_mem);
 		tile_barrier<MODE_WAVE>();
 		ACM_STAMP(3);
-		{
+		if constexpr (F32) {
+			float *out = discard ? reinterpret_cast<float *>(sink) : reinterpret_cast<float *>(pcm) + cur.pcm_off;
+			lean_store_f32<C, 64, NSTORE, ABL>(tile, lane, out);
+		} else {
 			typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 			v4u *out = discard ? reinterpret_cast<v4u *>(sink) : reinterpret_cast<v4u *>(reinterpret_cast<uint16_t *>(pcm) + cur.pcm_off);
 #pragma unroll
@@ -3085,7 +3233,7 @@ acm_chunk(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16
 		}
 		ACM_STAMP(5);
 		phase_prio<true, PRIO_IDLE>();
-		k2_wait<NSTORE>();                              /* the next chunk's indices are here; only this chunk's PCM stores may still be on their way */
+		k2_wait<F32 ? 2 * NSTORE : NSTORE>();           /* the next chunk's indices are here; only this chunk's PCM stores may still be on their way */
 		ACM_STAMP(6);
 		tile_barrier<MODE_WAVE>();                      /* (the next first pass overwrites what the stores have just read) */
 		if (!more)
@@ -3118,18 +3266,18 @@ struct Tile2Entry {
 template <class C, int... Gs>
 constexpr Tile2Entry entry_k2()
 {
-	return Tile2Entry{ acm_tile2<C, 4, 0, false, Gs...>, C::NT, C::TR, 1024 / C::NT };
+	return Tile2Entry{ ACM_K_TILE2<C, 4, 0, false, Gs...>, C::NT, C::TR, 1024 / C::NT };
 }
 /* bigger tiles: WPC workgroups per CU */
 template <class C, int WPC, int... Gs>
 constexpr Tile2Entry entry_k2w()
 {
-	return Tile2Entry{ acm_tile2<C, WPC * C::NT / 256, 0, false, Gs...>, C::NT, C::TR, WPC };
+	return Tile2Entry{ ACM_K_TILE2<C, WPC * C::NT / 256, 0, false, Gs...>, C::NT, C::TR, WPC };
 }
 #ifdef ACM_ABLATION
 /* timing-only builds of the level-9 kernel with parts removed (wrong output by design): ACM_K2_ABL=<mask> */
 template <int ABL>
-constexpr Tile2Entry abl_k2() { return Tile2Entry{ acm_tile2<TileCfg<9, 256, 8192>, 4, ABL, false, 3, 3, 3>, 256, 16, 4 }; }
+constexpr Tile2Entry abl_k2() { return Tile2Entry{ ACM_K_TILE2<TileCfg<9, 256, 8192>, 4, ABL, false, 3, 3, 3>, 256, 16, 4 }; }
 const struct { int mask; Tile2Entry e; } g_tile2_abl[] = {
 	{ 1, abl_k2<1>() }, { 2, abl_k2<2>() }, { 4, abl_k2<4>() }, { 6, abl_k2<6>() }, { 8, abl_k2<8>() }, { 16, abl_k2<16>() },
 	{ 17, abl_k2<17>() }, { 23, abl_k2<23>() }, { 32, abl_k2<32>() }, { 25, abl_k2<25>() }, { 31, abl_k2<31>() }, { 12, abl_k2<12>() },
@@ -3168,12 +3316,12 @@ inline const Tile2Entry &tile2_entry(uint32_t level)
 template <class C, int... Gs>
 constexpr Tile2Entry entry_k2m()
 {
-	return Tile2Entry{ acm_tile2<C, 4, 0, true, Gs...>, C::NT, C::TR, 1024 / C::NT };
+	return Tile2Entry{ ACM_K_TILE2<C, 4, 0, true, Gs...>, C::NT, C::TR, 1024 / C::NT };
 }
 template <class C, int WPC, int... Gs>
 constexpr Tile2Entry entry_k2mw()
 {
-	return Tile2Entry{ acm_tile2<C, WPC * C::NT / 256, 0, true, Gs...>, C::NT, C::TR, WPC };
+	return Tile2Entry{ ACM_K_TILE2<C, WPC * C::NT / 256, 0, true, Gs...>, C::NT, C::TR, WPC };
 }
 #ifndef ACM_K2M_L11
 #define ACM_K2M_L11 entry_k2m<TileCfg<11, 256, 8192>, 4, 3, 2, 2>(), 4
@@ -3220,7 +3368,7 @@ constexpr int g_tile2m_default[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = { 3,
 template <int L, int... Gs>
 constexpr Tile2MEntry entry_k3()
 {
-	return Tile2MEntry{ Tile2Entry{ acm_chunk<L, 0, Gs...>, 64 * FirstPassZ<L>::NW, FirstPassZ<L>::TR, 1 }, 6 };
+	return Tile2MEntry{ Tile2Entry{ ACM_K_CHUNK<L, 0, Gs...>, 64 * FirstPassZ<L>::NW, FirstPassZ<L>::TR, 1 }, 6 };
 }
 const Tile2MEntry g_chunk[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = {
 	/* level 7 (two classes per row: eight row walkers per matrix set, a lane's four outputs belong to two of them) was built, is bit-exact
@@ -3558,19 +3706,21 @@ constexpr Tile2PEntry entry_k2p()
 	return Tile2PEntry{ acm_tile2p<C, 4, GR, Gs...>, C::NT, C::TR, 1024 / C::NT, GR, PackGeo<C, GR>::NW * PackGeo<C, GR>::NSLOT, C::PS };
 }
 /* the tile geometries and stage groupings of acm_tile2 (g_tile2); groups of 16 rows = one block of the usual acm_rows = 16
- * (level 6: 32, or a wave would hold ten chunks) */
+ * (level 6: 32, or a wave would hold ten chunks).  (int16 only: the packed form has no float32 build) */
+#if !ACM_OUT_F32
 const Tile2PEntry g_tile2p[ACM_K2P_MAX_LEVEL - ACM_K2P_MIN_LEVEL + 1] = {
 	entry_k2p<TileCfg<6, 256, 8192>, 32, 2, 2, 2>(),
 	entry_k2p<TileCfg<7, 256, 8192>, 16, 3, 2, 2>(),
 	entry_k2p<TileCfg<8, 256, 8192>, 16, 3, 3, 2>(),
 	entry_k2p<TileCfg<9, 256, 8192>, 16, 3, 3, 3>(),
 };
+#endif
 
 /* levels 13-15: the stage-wise kernels apply the first level-12 stages into an int32 plane, this level-12 build of the tile
  * kernel (one 128 KB tile per CU - two 64 KB tiles spill with the 64 prefetch registers of a plane; halo or carry flavour like
  * every other group) reads the plane and does the other twelve */
-const FusedEntry g_fused_plane = { acm_fused_tile<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, false, 3, 3, 3, 3>, 512, 8, 1,
-				   acm_fused_tile<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, true, 3, 3, 3, 3> };
+const FusedEntry g_fused_plane = { ACM_K_FUSED<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, false, 3, 3, 3, 3>, 512, 8, 1,
+				   ACM_K_FUSED<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, true, 3, 3, 3, 3> };
 
 inline dim3 sw_grid(uint64_t max_elems, uint32_t nlist)
 {
@@ -3586,6 +3736,7 @@ inline dim3 sw_grid(uint64_t max_elems, uint32_t nlist)
 
 #define ACMK_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+#if !ACM_OUT_F32
 namespace {
 __global__ void acm_warmup_kernel() {}
 }
@@ -3606,9 +3757,11 @@ extern "C" int acmk_warmup(void *stream)
 	return 0;
 }
 
+#endif
 /* gridDim.y carries the stream index and is limited to 65535: walk long lists in slices */
 constexpr uint32_t SW_MAX_Y = 65535;
 
+#if !ACM_OUT_F32
 extern "C" int acmk_fused_variants(void)
 {
 	return NVARIANTS;
@@ -3635,10 +3788,15 @@ extern "C" int acmk_fused_grid(uint32_t level, int variant, int cus)
 	return (cus > 0 ? cus : 256) * g_fused[variant][level - ACM_K1_MIN_LEVEL].wg_per_cu;
 }
 
-extern "C" int acmk_launch_fused(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
+#endif
+extern "C" int ACMK_OUT(acmk_launch_fused)(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
 				 uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 				 int16_t *d_pcm, unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_fused_f32(level, variant, cus, carry, d_streams, d_tiles, ntiles, d_idx, d_hdr, d_pcm, fmt & 3u, stream);
+#endif
 	if (ntiles == 0)
 		return 0;
 	if (level < ACM_K1_MIN_LEVEL || level > ACM_K1_MAX_LEVEL || variant < 0 || variant >= NVARIANTS)
@@ -3657,6 +3815,7 @@ extern "C" int acmk_launch_fused(uint32_t level, int variant, int cus, int carry
 	return 0;
 }
 
+#if !ACM_OUT_F32
 /* shift: the planes of a level 13-15 prefix carry values scaled by 2^shift (16 - level) so that the level-12 tile kernel
  * that finishes them finds a sample in bytes 2..3, as it does for its own levels; 0 everywhere else */
 extern "C" int acmk_launch_unpack(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
@@ -3695,10 +3854,15 @@ extern "C" int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *
 	return 0;
 }
 
-extern "C" int acmk_launch_small(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
+#endif
+extern "C" int ACMK_OUT(acmk_launch_small)(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
 				 uint64_t max_emit, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm,
 				 unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_small_f32(level, d_streams, d_list, nlist, max_emit, d_idx, d_hdr, d_pcm, fmt & 3u, stream);
+#endif
 	if (level > ACM_SMALL_MAX_LEVEL)
 		return -1;
 	uint64_t gx = (max_emit + (uint64_t)SL_THREADS * SL_K - 1) / ((uint64_t)SL_THREADS * SL_K);
@@ -3707,29 +3871,34 @@ extern "C" int acmk_launch_small(uint32_t level, const AcmDevStream *d_streams, 
 		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
 		const dim3 grid((unsigned)gx, n, 1);
 		switch (level) {
-		case 0: hipLaunchKernelGGL(acm_small_level<0>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
-		case 1: hipLaunchKernelGGL(acm_small_level<1>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
-		case 2: hipLaunchKernelGGL(acm_small_level<2>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
-		case 3: hipLaunchKernelGGL(acm_small_level<3>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
-		default: hipLaunchKernelGGL(acm_small_level<4>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
+		case 0: hipLaunchKernelGGL(ACM_K_SMALL<0>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
+		case 1: hipLaunchKernelGGL(ACM_K_SMALL<1>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
+		case 2: hipLaunchKernelGGL(ACM_K_SMALL<2>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
+		case 3: hipLaunchKernelGGL(ACM_K_SMALL<3>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
+		default: hipLaunchKernelGGL(ACM_K_SMALL<4>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
 		}
 		ACMK_CHECK_LAUNCH();
 	}
 	return 0;
 }
 
-extern "C" int acmk_launch_emit(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
+extern "C" int ACMK_OUT(acmk_launch_emit)(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
 				uint64_t max_emit, const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_emit_f32(d_streams, d_list, nlist, max_emit, d_x, d_pcm, fmt & 3u, stream);
+#endif
 	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
 		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
-		hipLaunchKernelGGL(acm_sw_emit, sw_grid(max_emit, n), dim3(SW_THREADS), 0, (hipStream_t)stream,
+		hipLaunchKernelGGL(ACM_K_EMIT, sw_grid(max_emit, n), dim3(SW_THREADS), 0, (hipStream_t)stream,
 				   d_streams, d_list + at, d_x, d_pcm, fmt);
 		ACMK_CHECK_LAUNCH();
 	}
 	return 0;
 }
 
+#if !ACM_OUT_F32
 extern "C" int acmk_tile2_rows(uint32_t level)
 {
 	if (level < ACM_K2_MIN_LEVEL || level > ACM_K2_MAX_LEVEL)
@@ -3744,9 +3913,14 @@ extern "C" int acmk_tile2_grid(uint32_t level, int cus)
 	return (cus > 0 ? cus : 256) * tile2_entry(level).wg_per_cu;
 }
 
-extern "C" int acmk_launch_tile2(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
+#endif
+extern "C" int ACMK_OUT(acmk_launch_tile2)(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 				 int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_tile2_f32(level, cus, d_tiles, ntiles, d_idx, d_hdr, d_pcm, d_sink, fmt & 3u, stream);
+#endif
 	if (ntiles == 0)
 		return 0;
 	if (!d_sink)
@@ -3768,6 +3942,7 @@ extern "C" int acmk_launch_tile2(uint32_t level, int cus, const AcmTile2 *d_tile
 	return 0;
 }
 
+#if !ACM_OUT_F32
 extern "C" int acmk_tile2m_rows(uint32_t level)
 {
 	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
@@ -3817,9 +3992,14 @@ extern "C" int acmk_tile2m_stages(uint32_t level)
 	return tile2m_entry(level).g0;
 }
 
-extern "C" int acmk_launch_tile2m(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
+#endif
+extern "C" int ACMK_OUT(acmk_launch_tile2m)(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
 				  const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_tile2m_f32(level, cus, d_tiles, ntiles, d_mform, d_pairs, d_hdr, d_pcm, d_sink, fmt & 3u, stream);
+#endif
 	if (ntiles == 0)
 		return 0;
 	if (!d_sink || !d_mform || !d_pairs)
@@ -3836,6 +4016,7 @@ extern "C" int acmk_launch_tile2m(uint32_t level, int cus, const AcmTile2 *d_til
 	return 0;
 }
 
+#if !ACM_OUT_F32
 extern "C" int acmk_tile2p_rows(uint32_t level)
 {
 	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
@@ -3902,9 +4083,14 @@ extern "C" int acmk_plane_grid(int cus)
 	return (cus > 0 ? cus : 256) * g_fused_plane.wg_per_cu;
 }
 
-extern "C" int acmk_launch_fused_plane(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
+#endif
+extern "C" int ACMK_OUT(acmk_launch_fused_plane)(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
 				       const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream)
 {
+#if !ACM_OUT_F32
+	if (fmt & ACMK_FMT_F32)
+		return acmk_launch_fused_plane_f32(cus, carry, d_streams, d_tiles, ntiles, d_plane, d_pcm, fmt & 3u, stream);
+#endif
 	if (ntiles == 0)
 		return 0;
 	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * g_fused_plane.wg_per_cu);
@@ -3916,6 +4102,7 @@ extern "C" int acmk_launch_fused_plane(int cus, int carry, const AcmDevStream *d
 	return 0;
 }
 
+#if !ACM_OUT_F32
 extern "C" int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
 				 uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, void *stream)
 {
@@ -3933,3 +4120,4 @@ extern "C" int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t 
 	}
 	return 0;
 }
+#endif
