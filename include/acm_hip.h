@@ -340,7 +340,9 @@ int  acmhip_plan_time(acmhip_plan *plan, const int16_t *d_idx, const acmhip_blkh
 /* ------------------------------------------------------------------------
  * Host half of the path: bit parsing into staged form.
  * Replaces decode.c:41-163 (bit reader), :181-502 (fillers, fill_block),
- * :586-589 (block header), :687-752 (headers) for whole in-memory files.
+ * :586-589 (block header), :687-752 (headers) for in-memory files: whole
+ * (acm_stage_file), or a run of blocks entered through a block index
+ * (acm_index_file, acm_stage_window).
  * ---------------------------------------------------------------------- */
 typedef struct acm_stage_info {
 	uint32_t level, rows, cols;
@@ -384,6 +386,42 @@ int  acm_stage_file(const uint8_t *data, size_t len, int force_chans,
 int  acm_stage_file_mform(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
 			  acm_stage_info *info, uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows,
 			  uint64_t *mf_bytes);
+
+/* ------------------------------------------------------------------------
+ * Block index (csrc/acm_index.cpp; no reference counterpart - the reference re-parses a stream from its first block to seek,
+ * util.c:219-242).  A block depends on the blocks in front of it in two ways only: where it starts, and what they left in the
+ * never-cleared amplitude table (hazard H1), which their (val, pwr) headers determine.  With one mark per block a reader enters
+ * the stream at any block and stages exactly what a reader that came from the header would.
+ * ---------------------------------------------------------------------- */
+typedef struct acm_block_mark {  /* 16 bytes, plain data: callers may write it to disk and read it back */
+	uint64_t bit;            /* file bit offset of the block's first bit (its 20-bit header) */
+	uint32_t val, pwr;       /* the block's header: all the stale-table history (H1) needs */
+} acm_block_mark;
+
+/*
+ * Parses like acm_stage_file and stores no indices: marks[b] for every block acm_stage_file would stage, b < info->blocks, and
+ * one entry more - marks[info->blocks].bit = the bit behind the last whole block, val = pwr = 0.  marks has room for
+ * max_blocks + 1 entries.  *info is what acm_stage_file reports for the same bytes.  No device involved.
+ */
+int  acm_index_file(const uint8_t *data, size_t len, int force_chans,
+		    acm_block_mark *marks, size_t max_blocks, acm_stage_info *info);
+
+/*
+ * Host staging of blocks [block_first, block_first + block_count) entered through the index marks[0 .. nblocks_indexed] of this
+ * very file: idx, hdr and the patches are that slice of what acm_stage_file writes (patch.sample counted from the first staged
+ * sample of block_first; values resolved against the table history of the blocks in front, taken from the marks).
+ * info->blocks = blocks staged here, info->end_status = what stopped it (0: block_count reached, or the stream's clean end).
+ * The index is checked before use - bits strictly increasing, behind the header, inside the file, block_first <=
+ * nblocks_indexed: ACMHIP_ERR_ARG - and while parsing: an indexed block that does not have the header its mark names, does not
+ * end where the next mark says or is not whole ends the window with ACM_ERR_CORRUPT.  A wrong index never reads out of bounds.
+ * (What nothing in a window can contradict is the (val, pwr) of the marks in FRONT of it: they are only the table history that H1
+ * patch values are resolved against.)
+ */
+int  acm_stage_window(const uint8_t *data, size_t len, int force_chans,
+		      const acm_block_mark *marks, size_t nblocks_indexed,
+		      uint32_t block_first, uint32_t block_count,
+		      int16_t *idx, acmhip_blkhdr *hdr,
+		      acmhip_patch *patches, size_t max_patches, acm_stage_info *info);
 
 /* ------------------------------------------------------------------------
  * Batch front end (no reference counterpart; BASELINE.json "batch-of-files").
@@ -485,6 +523,76 @@ void acmhip_prewarm(void);
 /* 16-bit words of device memory acm_batch_decode needs for the PCM of these files (headers only are read;
  * every stream is padded to a multiple of 64 words) - the size of opts->d_pcm for device-resident output */
 uint64_t acm_batch_pcm_words(const acm_batch_item *items, size_t n, int force_chans);
+
+/* ------------------------------------------------------------------------
+ * Windowed batch decode (csrc/acm_batch_windows.cpp): random-access crops out of many files in one call, at a cost proportional
+ * to the windows - bit parsing, PCIe, synthesis and stores - not to the files.  Needs the block index of every item.
+ *
+ * Let `whole` be the items[i].words samples acm_batch_decode delivers for item i.  A window's PCM is
+ * whole[first_word : first_word + max_words] clipped to the end of whole, bit for bit; `words` its length (0 for a window that
+ * starts behind the end, and for max_words == 0); `status` ACM_OK when the slice has all max_words, else the item's own end
+ * status (index[i].end_status: ACM_OK for a stream that simply ended, the parse error of a corrupt or truncated one;
+ * ACM_ERR_NOT_ACM for a file that is not ACM, ACMHIP_ERR_ARG for an index the file cannot have).  Windows may overlap, repeat an
+ * item and come in any order.
+ *
+ * A window stages the blocks from the one that holds row max(first_word / cols - 2, 0) - the two rows of synthesis history, see
+ * acmhip_stream_desc - to the one that holds its last sample, and is synthesised as a window of that run of blocks which starts
+ * with the ROW of its first sample: the up to cols - 1 samples in front of first_word land in the slot in front of dev_off.
+ * One plan over int16 rows for all windows of the call.
+ *
+ * opts: fmt, force_chans, threads, plan_flags, d_pcm / d_pcm_words (>= acm_batch_window_pcm_words()), ACM_BATCH_PCM_F32 (with
+ * d_pcm; offsets count floats) as in acm_batch_decode.  prestaged and ACM_BATCH_STAGE_PACKED: ACMHIP_ERR_ARG.  opts->parse:
+ *   ACM_BATCH_PARSE_HOST    a thread pool runs acm_stage_window per window into a pinned arena; one upload, one plan, one launch.
+ *   ACM_BATCH_PARSE_DEVICE  only the byte span of every window's blocks (from the marks) is uploaded; acm_parse_scan_blocks walks
+ *                           every (window, block) as a wavefront of its own - with the index blocks are independent jobs, there is
+ *                           no sequential walk of a stream left - and checks the block against its marks, acm_parse_columns
+ *                           decodes the columns.  A window the device is not sure about (H1, a bad code, data running out, a block
+ *                           that disagrees with its marks, a span of 256 MiB) is staged again by the host; it never fails the call.
+ *   ACM_BATCH_PARSE_AUTO    HOST for calls that stage fewer than 256 blocks in all, DEVICE from there on.  Measured on an MI355X with
+ *                           16 host threads (profiles/window_decode_notes.txt): the device path costs a second round trip per call
+ *                           (the walk's results come back before the plan is cut) and less per block; the two meet between 58
+ *                           blocks (16 windows: HOST ahead) and 970 blocks (256 windows: DEVICE ahead).
+ * dev == NULL: ACMHIP_ERR_NO_DEVICE.
+ * ---------------------------------------------------------------------- */
+typedef struct acm_batch_index {         /* one per item */
+	const acm_block_mark *marks;     /* blocks + 1 entries, as acm_index_file wrote them (may be NULL for a file that is not ACM) */
+	uint32_t blocks;                 /* acm_stage_info.blocks of acm_index_file */
+	int32_t  end_status;             /* acm_stage_info.end_status of acm_index_file */
+} acm_batch_index;
+
+typedef struct acm_batch_window {
+	uint32_t item;           /* in:  which items[] entry */
+	uint32_t reserved;
+	uint64_t first_word;     /* in:  first interleaved 16-bit sample wanted */
+	uint64_t max_words;      /* in */
+	int16_t *pcm;            /* in:  host output for min(words, pcm_cap) samples (ignored with opts->d_pcm; may be NULL) */
+	size_t   pcm_cap;
+	uint64_t words;          /* out */
+	int32_t  status;         /* out */
+	uint32_t reserved2;
+	uint64_t dev_off;        /* out: where the window's FIRST REQUESTED sample is in opts->d_pcm (samples) */
+	uint64_t slot_off, slot_words;   /* out: the region of opts->d_pcm the library may have written for this window */
+} acm_batch_window;
+
+typedef struct acm_window_timing {
+	double stage_s;          /* wall clock until every window was bit-parsed (host pool, or device walk + host re-staging) */
+	double h2d_s, kernel_s, d2h_s;   /* device-side durations: uploads, synthesis launch, read-back */
+	double total_s;          /* wall clock of the whole call */
+	uint64_t samples;        /* samples delivered (sum of words) */
+	double alloc_s;          /* pinned + device arena allocation */
+	uint64_t device_parsed;  /* windows staged by the device parser ... */
+	uint64_t host_parsed;    /* ... and windows (re)staged by the host reader */
+	uint64_t h2d_bytes;      /* bytes sent to the device: staged indices and headers, or byte spans and job tables */
+	uint64_t blocks_parsed;  /* blocks bit-parsed by anyone, host or device: the sum of the windows' block ranges (+ the ranges the host
+	                            staged again) - nothing in front of a window is parsed */
+} acm_window_timing;
+
+/* samples of device memory acm_batch_decode_windows needs for these windows at most (headers only are read; every window's slot
+ * is padded to a multiple of 64) - the size of opts->d_pcm for device-resident output */
+uint64_t acm_batch_window_pcm_words(const acm_batch_item *items, size_t n, const acm_batch_window *wins, size_t nwin, int force_chans);
+/* items: data / len are read, nothing is written.  index[i] belongs to items[i]. */
+int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+			      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, acm_window_timing *timing);
 
 #ifdef __cplusplus
 }

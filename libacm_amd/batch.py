@@ -75,6 +75,23 @@ def pcm_capacity_words(head, file_len, force_chans=0):
     return (blocks * bl + 63) // 64 * 64
 
 
+def build_index(files, threads=0):
+    """The block index of every file (capi.index_file: start bit, val and pwr of each block - 16 bytes per block), built once on the
+    host and kept: GpuDecoder.crop() takes it back on every call.  files: paths or file images.  Returns a list of numpy record arrays
+    (capi.BlockIndex: capi.BLOCK_MARK_DT records that also remember how the stream ends; np.save / np.load keep the records), an empty
+    one for a file that is not ACM.  threads: 0 = one per CPU, at most 64."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(f):
+        try:
+            return capi.index_file(_load(f))[0]
+        except ValueError:
+            return np.zeros(0, dtype=capi.BLOCK_MARK_DT)
+    workers = threads if threads > 0 else min(64, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+    with ThreadPoolExecutor(max_workers=max(1, workers)) as ex:         # (the parsing runs inside the library: the GIL is released)
+        return list(ex.map(one, files))
+
+
 class GpuDecoder:
     """Decode a list of file images on this rank's GPU; PCM stays in HBM as one torch int16 tensor.
 
@@ -122,6 +139,24 @@ class GpuDecoder:
         statuses, words, offsets, self.timing = capi.batch_decode_device(
             self.dev, files, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
         # acm_batch_decode returns with its stream drained: d_pcm is complete and visible to torch's streams
+        return d_pcm, offsets, words, statuses
+
+
+    def crop(self, files, windows, index, out=None):
+        """Random-access crops: windows = (file_no, first_sample, n_samples) triples over interleaved samples, index = build_index(files).
+        Only the blocks a window needs are parsed, uploaded and synthesised.
+        -> (pcm tensor in HBM of this decoder's dtype, per-window offsets of the first requested sample, per-window sample counts,
+        per-window statuses).  Window k is pcm[offsets[k] : offsets[k] + counts[k]] = the whole decode's [first : first + n], clipped to
+        the end of the stream."""
+        torch = self.torch
+        files = [_load(f) for f in files]
+        cap = capi.batch_window_pcm_words(files, windows)
+        if out is not None and out.dtype != self.dtype:
+            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
+        d_pcm = out if out is not None and out.numel() >= cap else torch.empty(max(cap, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
+        torch.cuda.current_stream().synchronize()
+        statuses, words, offsets, _, self.timing = capi.batch_decode_windows_device(
+            self.dev, files, index, windows, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
         return d_pcm, offsets, words, statuses
 
 

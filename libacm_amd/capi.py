@@ -90,6 +90,45 @@ class BatchTiming(C.Structure):
                 ("device_parsed", C.c_uint64), ("host_parsed", C.c_uint64), ("packed_streams", C.c_uint64), ("h2d_bytes", C.c_uint64)]
 
 
+class BlockMark(C.Structure):
+    _fields_ = [("bit", C.c_uint64), ("val", C.c_uint32), ("pwr", C.c_uint32)]
+
+
+BLOCK_MARK_DT = np.dtype([("bit", "<u8"), ("val", "<u4"), ("pwr", "<u4")])      # acm_block_mark as a numpy record: np.save / np.load keep an index
+
+
+class BlockIndex(np.ndarray):
+    """BLOCK_MARK_DT records that remember how their stream ends (acm_stage_info.end_status of acm_index_file): what a window that
+    reaches the end of the stream reports.  A slice, a copy or an array read back from disk has forgotten it (end_status None): the
+    window calls then ask the host stager, one block past the index, per call."""
+    end_status = None
+
+    def __array_finalize__(self, obj):
+        self.end_status = None
+
+
+def as_index(marks, end_status):
+    ix = np.ascontiguousarray(marks, dtype=BLOCK_MARK_DT).view(BlockIndex)
+    ix.end_status = None if end_status is None else int(end_status)
+    return ix
+
+
+class BatchIndex(C.Structure):
+    _fields_ = [("marks", C.c_void_p), ("blocks", C.c_uint32), ("end_status", C.c_int32)]
+
+
+class BatchWindow(C.Structure):
+    _fields_ = [("item", C.c_uint32), ("reserved", C.c_uint32), ("first_word", C.c_uint64), ("max_words", C.c_uint64),
+                ("pcm", C.c_void_p), ("pcm_cap", C.c_size_t), ("words", C.c_uint64), ("status", C.c_int32), ("reserved2", C.c_uint32),
+                ("dev_off", C.c_uint64), ("slot_off", C.c_uint64), ("slot_words", C.c_uint64)]
+
+
+class WindowTiming(C.Structure):
+    _fields_ = [("stage_s", C.c_double), ("h2d_s", C.c_double), ("kernel_s", C.c_double), ("d2h_s", C.c_double), ("total_s", C.c_double),
+                ("samples", C.c_uint64), ("alloc_s", C.c_double), ("device_parsed", C.c_uint64), ("host_parsed", C.c_uint64),
+                ("h2d_bytes", C.c_uint64), ("blocks_parsed", C.c_uint64)]
+
+
 # every symbol include/acm_hip.h declares (checked by tests/test_abi.py)
 ACMHIP_SYMBOLS = [
     "acmhip_last_error", "acmhip_device_count", "acmhip_device_open", "acmhip_device_close",
@@ -101,6 +140,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_plan_create_packed", "acmhip_plan_bind_packed",
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
+    "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -186,6 +226,12 @@ def lib():
     L.acmhip_mform_rows.argtypes = [C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
     L.acmhip_mform_unrows.argtypes = [C.c_uint32, vp, vp, C.c_uint64, vp]
     L.acmhip_plan_bind_mform.argtypes = [vp, vp, vp]
+    L.acm_index_file.argtypes = [vp, sz, C.c_int, vp, sz, C.POINTER(StageInfo)]
+    L.acm_stage_window.argtypes = [vp, sz, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, sz, C.POINTER(StageInfo)]
+    L.acm_batch_window_pcm_words.argtypes = [C.POINTER(BatchItem), sz, C.POINTER(BatchWindow), sz, C.c_int]
+    L.acm_batch_window_pcm_words.restype = C.c_uint64
+    L.acm_batch_decode_windows.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                           C.POINTER(BatchOpts), C.POINTER(WindowTiming)]
     _lib = L
     return L
 
@@ -288,6 +334,52 @@ def stage_file_mform(data, force_chans=0, mf_base=0):
     if rc != 0:
         raise ValueError("acm_stage_file_mform failed (%d)" % rc)
     return info2, idx, hdr, blob, pairs, rows.value, nbytes.value
+
+
+# --------------------------------------------------------------------------- block index
+def index_file(data, force_chans=0):
+    """acm_index_file: the block index of a file image -> (marks, info).  marks: BLOCK_MARK_DT records, info.blocks + 1 of them (the
+    last one: the bit behind the last whole block); info: what acm_stage_file reports for the same bytes.  Raises on a non-ACM file."""
+    a = _as_u8(data)
+    rc, info = probe(a, force_chans)
+    if rc != 0:
+        raise ValueError("not an ACM stream (%d)" % rc)
+    bl = info.rows * info.cols
+    need = (info.total_values + bl - 1) // bl
+    # (the header may promise far more blocks than the bytes can hold: a block costs at least its header and a code per column)
+    need = min(need, (max(0, a.size - info.header_bytes) * 8 + 8) // (20 + 5 * info.cols) + 1)
+    marks = np.zeros(need + 1, dtype=BLOCK_MARK_DT)
+    info2 = StageInfo()
+    rc = lib().acm_index_file(a.ctypes.data, a.size, force_chans, marks.ctypes.data, need, C.byref(info2))
+    if rc != 0:
+        raise ValueError("acm_index_file failed (%d)" % rc)
+    return as_index(marks[:info2.blocks + 1].copy(), info2.end_status), info2
+
+
+def stage_window(data, marks, block_first, block_count, force_chans=0, nblocks_indexed=None):
+    """acm_stage_window: blocks [block_first, block_first + block_count) of a file entered through its index ->
+    (rc, Staged or None).  Staged.info.blocks = blocks staged, .info.end_status = what stopped it; patch samples count from the first
+    staged sample."""
+    a = _as_u8(data)
+    rc, info = probe(a, force_chans)
+    if rc != 0:
+        return rc, None
+    marks = np.ascontiguousarray(marks, dtype=BLOCK_MARK_DT)
+    nidx = marks.size - 1 if nblocks_indexed is None else nblocks_indexed
+    bl = info.rows * info.cols
+    idx = np.zeros(max(block_count, 1) * bl, dtype=np.int16)
+    hdr = np.zeros((max(block_count, 1), 2), dtype=np.uint32)
+    info2 = StageInfo()
+    rc = lib().acm_stage_window(a.ctypes.data, a.size, force_chans, marks.ctypes.data, nidx, block_first, block_count,
+                                idx.ctypes.data, hdr.ctypes.data, None, 0, C.byref(info2))
+    if rc != 0:
+        return rc, None
+    patches = None
+    if info2.npatches:
+        patches = (Patch * info2.npatches)()
+        rc = lib().acm_stage_window(a.ctypes.data, a.size, force_chans, marks.ctypes.data, nidx, block_first, block_count,
+                                    idx.ctypes.data, hdr.ctypes.data, patches, info2.npatches, C.byref(info2))
+    return rc, Staged(idx[:info2.blocks * bl], hdr[:info2.blocks], patches, info2)
 
 
 # --------------------------------------------------------------------------- host staging, packed half
@@ -761,3 +853,83 @@ def batch_decode_device(dev, files, d_pcm, d_pcm_words, force_chans=0, fmt=FMT_S
     n = len(files)
     return ([int(items[k].status) for k in range(n)], [int(items[k].words) for k in range(n)],
             [int(items[k].dev_off) for k in range(n)], tm)
+
+
+# --------------------------------------------------------------------------- windows through a block index
+def _window_tables(files, index, windows, force_chans=0):
+    """items / index / window tables of acm_batch_decode_windows.  index[i]: the marks of files[i] as index_file returns them (an
+    empty array or None for a file that is not ACM), or a pair (marks, end_status).  With the marks alone the end status of the
+    stream is asked of the host stager: one block past the index.  windows: (file_no, first_word, max_words) triples."""
+    bufs, items = _batch_items(files)
+    n = len(files)
+    keep = []
+    ix = (BatchIndex * max(n, 1))()
+    for i in range(n):
+        e = index[i]
+        end = None
+        if isinstance(e, tuple):
+            e, end = e
+        elif isinstance(e, BlockIndex):
+            end = e.end_status
+        if e is None or len(e) == 0:
+            continue
+        m = np.ascontiguousarray(np.asarray(e), dtype=BLOCK_MARK_DT)
+        keep.append(m)
+        if end is None:
+            end = _end_status(bufs[i], m, force_chans)
+        ix[i].marks = m.ctypes.data
+        ix[i].blocks = m.size - 1
+        ix[i].end_status = end
+    wins = (BatchWindow * max(len(windows), 1))()
+    for k, (f, first, count) in enumerate(windows):
+        wins[k].item = f
+        wins[k].first_word = first
+        wins[k].max_words = count
+    return bufs, items, ix, wins, keep
+
+
+def _end_status(buf, marks, force_chans=0):
+    """what ends the stream behind its last indexed block (acm_stage_info.end_status of acm_index_file), from the index alone"""
+    rc, st = stage_window(buf, marks, marks.size - 1, 1, force_chans)
+    return rc if rc != 0 else st.info.end_status
+
+
+def batch_window_pcm_words(files, windows, force_chans=0):
+    """samples of device memory batch_decode_windows_device needs for these windows at most"""
+    bufs, items = _batch_items(files)
+    wins = (BatchWindow * max(len(windows), 1))()
+    for k, (f, first, count) in enumerate(windows):
+        wins[k].item, wins[k].first_word, wins[k].max_words = f, first, count
+    return int(lib().acm_batch_window_pcm_words(items, len(files), wins, len(windows), force_chans))
+
+
+def batch_decode_windows(dev, files, index, windows, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, caps=None):
+    """acm_batch_decode_windows with host output -> (list of (status, words, uint16 array), WindowTiming).
+    caps: per-window capacity of the host buffer (default: max_words); the array holds min(words, cap) samples."""
+    bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
+    nw = len(windows)
+    outs = []
+    for k in range(nw):
+        cap = windows[k][2] if caps is None else caps[k]
+        o = np.zeros(max(cap, 1), dtype=np.uint16)
+        outs.append(o)
+        wins[k].pcm = o.ctypes.data
+        wins[k].pcm_cap = cap
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, 0)
+    tm = WindowTiming()
+    _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
+    return [(int(wins[k].status), int(wins[k].words), outs[k][:min(int(wins[k].words), int(wins[k].pcm_cap))]) for k in range(nw)], tm
+
+
+def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO,
+                                parse=PARSE_HOST, f32=False):
+    """acm_batch_decode_windows with device-resident output: the first requested sample of window k lands at sample offsets[k] of d_pcm
+    (int16, or float32 with f32=True).  Returns (statuses, words, offsets, slots, WindowTiming); slots[k] = (slot_off, slot_words), the
+    region of d_pcm the call may have written for window k."""
+    bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
+    nw = len(windows)
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_PCM_F32 if f32 else 0, d_pcm, d_pcm_words)
+    tm = WindowTiming()
+    _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
+    return ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], [int(wins[k].dev_off) for k in range(nw)],
+            [(int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)], tm)

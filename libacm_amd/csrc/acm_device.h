@@ -88,6 +88,18 @@ struct AcmParseResult {
 	uint32_t mf_at;        /* ... and where its next block starts in the stream's byte-plane region, in 64-byte units (width from pwr) */
 };
 
+/* indexed input (acm_parse_scan_blocks): block `block` of job `job` is a walk of its own - from `bit` (relative to the job's file_off),
+ * where its 20-bit header must read h20 (val << 4 | pwr, as the bitstream holds it), to exactly end_bit.  Written by the host from a
+ * block index it has checked: bit + 20 <= end_bit <= 8 * the job's file_len */
+struct AcmBlockJob {
+	uint32_t job;
+	uint32_t block;
+	uint32_t bit;
+	uint32_t end_bit;
+	uint32_t h20;
+	uint32_t pad;
+};
+
 /* levels the fused tile kernel covers; its tile geometry is owned by acm_kernels.hip (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
 #define ACM_K1_MAX_LEVEL 12
@@ -198,6 +210,13 @@ int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uin
 int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
 			       acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t r, uint32_t R,
 			       uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, void *stream);
+/* Indexed input: njobs jobs (here: windows into streams; a job's file is the byte span of its blocks, data_start unused) whose blocks are
+ * the nblock walks of d_bjobs, one wavefront each; then the column kernel over every job, in one piece, int16 rows only.  d_res and d_flags
+ * [njobs] must be zero on entry; afterwards job j is clean iff d_res[j].status == 0 && d_res[j].blocks_done == its blocks && d_flags[j] == 0
+ * (a walk that fails - data running out, a bad code, a header or an end that disagrees with the index - raises status) */
+int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock, const uint8_t *d_files,
+			     uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags,
+			     uint64_t max_columns, void *stream);
 /* Striped upload of a block-range batch: every file's arena slot (the file padded to 16 bytes + 16 zero bytes) is cut into R
  * stripes at acmk_stripe_bound(len, s, R); stripe s of all files travels as ONE transfer into a staging arena and a scatter
  * kernel puts the pieces in place, so the first ranges are walked, synthesised and read back while the later stripes are

@@ -539,6 +539,87 @@ out:
 		res[jobno] = AcmParseResult{ done, status, bit, mf_at };
 }
 
+/*
+ * Indexed input: one BLOCK per wavefront.
+ *
+ * The walk above is sequential per stream only because nobody tells it where blocks start.  With a block index (include/acm_hip.h:
+ * acm_index_file) the host knows the first bit of every block, so every (job, block) pair is a walk of its own - cols columns, a few
+ * microseconds - and a batch of windows fills the chip however few streams it has.  The wavefront is the same register file as in
+ * acm_parse_scan_wave (window, code tables, column offsets through v_writelane), the same fixed-length fast loop and k-column descent.
+ * The index is not trusted: the block's header must read what its mark says and the walk must end exactly at the next mark, or the job
+ * is flagged and the host stages it again.  `safe` is the block's own end: a walk cannot leave its block, let alone its span.
+ */
+__global__ void __launch_bounds__(64 * WAVE_SCAN_WAVES)
+acm_parse_scan_blocks(const AcmParseJob *__restrict__ jobs, const AcmBlockJob *__restrict__ bjobs, const uint32_t nblock,
+		      const uint8_t *__restrict__ files, uint32_t *__restrict__ colpos, acmhip_blkhdr *__restrict__ hdr,
+		      AcmParseResult *__restrict__ res)
+{
+	const uint32_t no = blockIdx.x * WAVE_SCAN_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	if (no >= nblock)
+		return;
+	const uint32_t lane = threadIdx.x & 63u;
+	const AcmBlockJob me = bjobs[no];
+	const AcmParseJob job = jobs[me.job];
+	const uint32_t rows = job.rows, cols = 1u << job.level;
+	const uint32_t safe = min(me.end_bit, job.file_len * 8u);
+	const uint32_t code_len = column_bits(lane & 31u, rows);
+	const uint32_t code_tab = k_table_for(lane & 31u);
+	WaveWindow ww;
+	ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
+	ww.maxdw = (job.file_len + 15u) / 4u;
+	ww.lane = lane;
+	uint32_t bit = me.bit;
+	uint32_t *cp = colpos + job.col_off + (uint64_t)me.block * cols;
+	bool ok = false;
+	if (me.block < job.blocks && bit + 20 <= safe) {
+		ww.load(bit >> 5);
+		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
+		bit += 20;
+		if (h20 != me.h20)
+			goto out;
+		for (uint32_t c0 = 0; c0 < cols; c0 += 64) {
+			const uint32_t n = __builtin_amdgcn_readfirstlane(min(64u, cols - c0));
+			uint32_t cpv = 0, k = 0;
+			for (;;) {
+				uint32_t code, len;
+				bool fixed;
+				do {
+					/* cpv[lane k] = bit: the lane select goes through m0 (see acm_parse_scan_wave) */
+					asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(cpv) : "s"(bit), "s"(k) : "m0");
+					code = (uint32_t)ww.peek64(bit) & 31u;
+					len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
+					fixed = len < K_WALK;
+					bit += 5 + (fixed ? len : 0u);
+					k++;
+				} while (fixed & (bit <= safe) & (k < n));
+				if (!fixed) {
+					if (len != K_WALK)
+						goto out;
+					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
+					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
+				}
+				if (bit > safe)                                 /* the column must end inside the block */
+					goto out;
+				if (k >= n)
+					break;
+			}
+			if (lane < n)
+				cp[c0 + lane] = cpv;
+		}
+		ok = bit == me.end_bit;
+		if (ok && lane == 0)
+			hdr[job.hdr_off + me.block] = acmhip_blkhdr{ h20 >> 4, h20 & 15u };
+	}
+out:
+	/* (vector atomics from one lane: the job's record is shared by the wavefronts of its blocks) */
+	if (lane == 0) {
+		if (ok)
+			atomicAdd(&res[me.job].blocks_done, 1u);
+		else
+			atomicOr(&res[me.job].status, 1u);
+	}
+}
+
 /* ---- kernel 2: decode the columns ---- */
 
 /* One look-up entry per (k/t filler, next 7 bits): the symbol at the head of those bits.
@@ -907,6 +988,27 @@ extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t nj
 		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
 				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, range, nranges, mf ? d_mf : nullptr,
 				   mf ? d_pairs : nullptr, mf ? d_blkoff : nullptr);
+		ACMP_CHECK();
+	}
+	return 0;
+}
+
+extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock,
+					const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr, AcmParseResult *d_res,
+					uint32_t *d_flags, uint64_t max_columns, void *stream)
+{
+	if (njobs == 0 || nblock == 0)
+		return 0;
+	hipStream_t st = (hipStream_t)stream;
+	hipLaunchKernelGGL(acm_parse_scan_blocks, dim3((nblock + WAVE_SCAN_WAVES - 1) / WAVE_SCAN_WAVES), dim3(64 * WAVE_SCAN_WAVES), 0, st,
+			   d_jobs, d_bjobs, nblock, d_files, d_colpos, d_hdr, d_res);
+	ACMP_CHECK();
+	uint64_t gx = (max_columns + COL_THREADS - 1) / COL_THREADS;
+	gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
+	for (uint32_t at = 0; at < njobs; at += 65535) {
+		const uint32_t n = njobs - at < 65535 ? njobs - at : 65535;
+		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
+				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, 0u, 1u, nullptr, nullptr, nullptr);
 		ACMP_CHECK();
 	}
 	return 0;

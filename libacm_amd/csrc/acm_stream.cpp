@@ -405,6 +405,10 @@ int mem_read(void *ptr, int size, int n, void *arg)
 	return size ? (int)(want / (size_t)size) : 0;
 }
 
+} // namespace
+
+namespace acmfill {
+
 /* header parse + channel forcing + derived sizes, shared by open and staging (decode.c:783-804) */
 int open_common(ACMStream *a, int force_chans)
 {
@@ -433,7 +437,10 @@ void fill_stage_info(const ACMStream *a, acm_stage_info *info)
 	info->header_bytes = a->wavc_file ? 42 : 14;
 }
 
-} // namespace
+} // namespace acmfill
+
+using acmfill::fill_stage_info;
+using acmfill::open_common;
 
 /* ======================================================================== */
 /* core API                                                                  */
