@@ -1,13 +1,17 @@
 /*
  * acm_batch_common.h - what the batch front ends (acm_batch.cpp: whole files; acm_batch_windows.cpp: windows through a block index)
- * share: the worker pool, the arena arithmetic, the delivery rule of acm_read_loop().  Internal.
+ * share: the worker pool, the arena arithmetic and the delivery rule of acm_read_loop() (acm_batch_layout.h), and the handful of
+ * steps both take on the device - a call's hold on the arenas, its events, a plan's descriptors, the verdict on the device parser's
+ * results, the file arena's zero tails, the launch.  Internal.
  */
 #ifndef ACM_BATCH_COMMON_H
 #define ACM_BATCH_COMMON_H
 
+#include <hip/hip_runtime.h>
 #include <sched.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 #include <atomic>
@@ -18,30 +22,18 @@
 #include <thread>
 #include <vector>
 
+#include "acm_batch_layout.h"
+#include "acm_device.h"
 #include "acm_hip.h"
+
+/* inside a function that returns an ACMHIP_* code: pass a failure on (its cleanup is the destructors') */
+#define ACM_TRY(call) do { const int rc_ = (call); if (rc_ != ACMHIP_OK) return rc_; } while (0)
+#define ACM_HIP_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return acmhip_report_hip((int)e_, #call); } while (0)
 
 namespace acmbatch {
 
 using clk = std::chrono::steady_clock;
 inline double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
-
-/* How many words a caller looping over acm_read_loop() (acmtool.c:274-291)
- * gets out of `blocks` decodable blocks: blocks are drained whole except where
- * the per-call rounding to a multiple of `channels` (decode.c:856-857) or the
- * total_values cut (decode.c:853-854) stops the stream for good. */
-inline uint64_t deliverable_words(uint64_t total_values, uint64_t block_len, unsigned channels, uint64_t blocks)
-{
-	uint64_t pos = 0;
-	for (uint64_t b = 0; b < blocks && pos < total_values; b++) {
-		uint64_t take = std::min(block_len, total_values - pos);
-		if (channels > 1)
-			take -= take % channels;
-		pos += take;
-		if (take != block_len)
-			break;
-	}
-	return pos;
-}
 
 /* Default size of the parser pool.  Streams are independent and the parser is compute bound, so more threads
  * help up to the core count; past ~64 the returns vanish (and boxes with a cgroup CPU quota time-slice the
@@ -138,17 +130,85 @@ private:
 	bool quit_ = false;
 };
 
-inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+/* A call's hold on a device handle's arenas (they live in the handle and are reused by the next batch).  First member of a front end's
+ * state object: whatever that object's destructor drains and destroys, the arenas are unlocked after it */
+struct ArenaLock {
+	acmhip_device *dev;
+	explicit ArenaLock(acmhip_device *d) : dev(d) { acmhip_arena_lock(dev); }
+	~ArenaLock() { acmhip_arena_unlock(dev); }
+	ArenaLock(const ArenaLock &) = delete;
+	ArenaLock &operator=(const ArenaLock &) = delete;
+};
 
-/* Blocks a file can possibly hold: the header promises total_values, but arenas are sized by this - a block costs at
- * least its 20-bit header and a 5-bit filler code per column (decode.c:491-502, 586-589), and the reader appends one
- * virtual zero byte (decode.c:57-61).  A 19-byte file that claims 2^32-1 samples gets one block, not 8 GB. */
-inline uint64_t blocks_possible(const acm_stage_info &info, size_t len)
+/* the events of one unit of work (a chunk, a range, a parse group, a call) ... */
+inline int make_events(hipEvent_t *ev, size_t n)
 {
-	const uint64_t bl = (uint64_t)info.rows * info.cols;
-	const uint64_t promised = ((uint64_t)info.total_values + bl - 1) / bl;
-	const uint64_t bits = (len > info.header_bytes ? (uint64_t)(len - info.header_bytes) * 8 : 0) + 8;
-	return std::min<uint64_t>(promised, bits / (20 + 5 * (uint64_t)info.cols) + 1);
+	for (size_t k = 0; k < n; k++)
+		ACM_HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventBlockingSync));
+	return ACMHIP_OK;
+}
+/* ... and their end, with the unit's plan (either may be null).  The streams that use them are idle by then */
+inline void drop_unit(acmhip_plan *plan, hipEvent_t *ev, size_t n)
+{
+	acmhip_plan_destroy(plan);
+	for (size_t k = 0; k < n; k++)
+		if (ev[k])
+			(void)hipEventDestroy(ev[k]);
+}
+
+/* The host staging arenas, fetched when the first stream needs the exact host reader (with device parsing: perhaps never) */
+inline int host_arenas(acmhip_device *dev, uint64_t idx_total, uint64_t hdr_total, int16_t **h_idx, acmhip_blkhdr **h_hdr)
+{
+	if (*h_idx)
+		return ACMHIP_OK;
+	ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_IDX, idx_total * sizeof(int16_t), (void **)h_idx));
+	return acmhip_arena_get(dev, ACM_ARENA_H_HDR, hdr_total * sizeof(acmhip_blkhdr), (void **)h_hdr);
+}
+
+/* `have` bytes of a file into a slot of the pinned file arena, zeros behind them to the slot's end (a whole file's slot is
+ * file_slot_bytes(): the device readers load whole dwords) */
+inline void copy_zero_tail(uint8_t *dst, const uint8_t *src, uint64_t have, uint64_t slot)
+{
+	if (have)
+		memcpy(dst, src, have);
+	memset(dst + have, 0, slot - have);
+}
+
+/* did the device parser leave this job clean?  Anything else goes to the exact host reader: H1, bad symbols, data running out */
+inline bool parse_clean(const AcmParseResult &res, uint32_t flags, uint64_t blocks)
+{
+	return res.status == 0 && res.blocks_done == blocks && flags == 0;
+}
+
+/* The streams of a plan as a front end collects them: descriptors, and every stream's H1 patches re-indexed to its descriptor */
+struct PlanStreams {
+	std::vector<acmhip_stream_desc> descs;
+	std::vector<acmhip_patch> patches;
+	/* rows [0, nrows) of a stream of `info`'s level and block height staged at idx_off / hdr_off; n_emit samples from row_begin on go to pcm_off */
+	void add(const acm_stage_info &info, uint64_t idx_off, uint64_t hdr_off, uint64_t pcm_off, uint32_t nrows, uint32_t row_begin, uint64_t n_emit,
+		 const std::vector<acmhip_patch> &stream_patches)
+	{
+		acmhip_stream_desc d{};
+		d.idx_off = idx_off;
+		d.hdr_off = hdr_off;
+		d.pcm_off = pcm_off;
+		d.level = info.level;
+		d.rows = info.rows;
+		d.nrows = nrows;
+		d.row_begin = row_begin;
+		d.n_emit = n_emit;
+		for (acmhip_patch p : stream_patches) {
+			p.stream = (uint32_t)descs.size();
+			patches.push_back(p);
+		}
+		descs.push_back(d);
+	}
+};
+
+/* every synthesis launch of a front end: int16 PCM in opts.fmt, or float32 (ACM_BATCH_PCM_F32: d_pcm holds floats) */
+inline int launch_plan(acmhip_plan *plan, bool out_f32, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt)
+{
+	return out_f32 ? acmhip_plan_launch_f32(plan, d_idx, d_hdr, reinterpret_cast<float *>(d_pcm)) : acmhip_plan_launch(plan, d_idx, d_hdr, d_pcm, fmt);
 }
 
 } // namespace acmbatch

@@ -46,6 +46,20 @@ struct Win {
 	std::vector<acmhip_patch> patches;
 };
 
+/* what a call holds behind the arena lock; its end is every return's cleanup */
+struct WinRun {
+	ArenaLock lock;
+	hipStream_t st;
+	acmhip_plan *plan = nullptr;
+	hipEvent_t ev[6] = {};
+	WinRun(acmhip_device *dev, hipStream_t st_) : lock(dev), st(st_) {}
+	~WinRun()
+	{
+		(void)hipStreamSynchronize(st);
+		drop_unit(plan, ev, 6);
+	}
+};
+
 constexpr uint64_t ACM_WINDOWS_AUTO_BLOCKS = 256;       /* ACM_BATCH_PARSE_AUTO: device parsing from this many staged blocks per call on */
 
 /* samples in front of the first one wanted + the samples wanted, given how many the stream has */
@@ -76,8 +90,9 @@ extern "C" uint64_t acm_batch_window_pcm_words(const acm_batch_item *items, size
 	return total;
 }
 
-extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
-					acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, acm_window_timing *timing)
+/* the call without its wall clock: the caller reads that once everything held here is released */
+static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
+			  size_t nwin, const acm_batch_opts *opts_in, acm_window_timing &tm)
 {
 	if (!dev)
 		return ACMHIP_ERR_NO_DEVICE;
@@ -94,8 +109,6 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 		return ACMHIP_ERR_ARG;
 	}
 	const bool keep_on_device = opts.d_pcm != nullptr;
-	acm_window_timing tm{};
-	const auto t0 = clk::now();
 	const int threads_wanted = opts.threads > 0 ? opts.threads : default_threads();
 	Pool pool((int)std::min<size_t>((size_t)threads_wanted, std::max<size_t>(1, std::max(n, nwin))));
 
@@ -174,7 +187,7 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 			s.on_device = true;
 			s.file_off = files_total;
 			s.col_off = cols_total;
-			files_total += round_up(s.span_len, 16) + 16;
+			files_total += file_slot_bytes(s.span_len);
 			cols_total += (uint64_t)s.nb * it.info.cols;
 			max_columns = std::max(max_columns, (uint64_t)s.nb * it.info.cols);
 			dev_ids.push_back(k);
@@ -191,20 +204,8 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 	acmhip_blkhdr *h_hdr = nullptr, *d_hdr = nullptr;
 	uint8_t *h_files = nullptr, *d_files = nullptr, *h_jobs = nullptr, *d_jobs = nullptr;
 	uint32_t *d_colpos = nullptr;
-	acmhip_plan *plan = nullptr;
-	hipEvent_t ev[6] = {};
-	int rc = ACMHIP_OK;
-	acmhip_arena_lock(dev);
-	auto cleanup = [&]() {
-		(void)hipStreamSynchronize(st);
-		acmhip_plan_destroy(plan);
-		for (hipEvent_t e : ev)
-			if (e)
-				(void)hipEventDestroy(e);
-		acmhip_arena_unlock(dev);
-	};
-#define WTRY(call) do { rc = (call); if (rc != ACMHIP_OK) { cleanup(); return rc; } } while (0)
-#define WHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = acmhip_report_hip((int)e_, #call); cleanup(); return rc; } } while (0)
+	WinRun run(dev, st);
+	hipEvent_t *const ev = run.ev;
 	const size_t pcm_unit = out_f32 ? sizeof(float) : sizeof(int16_t);
 	const size_t nd = dev_ids.size();
 	uint64_t nbj = 0;
@@ -214,27 +215,24 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 	const size_t res_bytes = nd * (sizeof(AcmParseResult) + sizeof(uint32_t));      /* results, then flags */
 	const bool host_arena = nd < act.size();                                        /* some window is staged by the host from the start */
 	if (!act.empty()) {
-		WTRY(acmhip_arena_get(dev, ACM_ARENA_D_IDX, idx_total * sizeof(int16_t), (void **)&d_idx));
-		WTRY(acmhip_arena_get(dev, ACM_ARENA_D_HDR, hdr_total * sizeof(acmhip_blkhdr), (void **)&d_hdr));
-		if (host_arena) {
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_H_IDX, idx_total * sizeof(int16_t), (void **)&h_idx));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_H_HDR, hdr_total * sizeof(acmhip_blkhdr), (void **)&h_hdr));
-		}
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_IDX, idx_total * sizeof(int16_t), (void **)&d_idx));
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_HDR, hdr_total * sizeof(acmhip_blkhdr), (void **)&d_hdr));
+		if (host_arena)
+			ACM_TRY(host_arenas(dev, idx_total, hdr_total, &h_idx, &h_hdr));
 		if (keep_on_device) {
 			d_pcm = static_cast<int16_t *>(opts.d_pcm);
 		} else {
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, pcm_total * pcm_unit, (void **)&d_pcm));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_H_PCM, pcm_total * pcm_unit, (void **)&h_pcm));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, pcm_total * pcm_unit, (void **)&d_pcm));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_PCM, pcm_total * pcm_unit, (void **)&h_pcm));
 		}
 		if (nd) {
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_H_FILES, files_total, (void **)&h_files));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_D_FILES, files_total, (void **)&d_files));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_D_COLPOS, cols_total * sizeof(uint32_t), (void **)&d_colpos));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes + bjobs_bytes + res_bytes, (void **)&h_jobs));
-			WTRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes + bjobs_bytes + res_bytes, (void **)&d_jobs));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_FILES, files_total, (void **)&h_files));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_FILES, files_total, (void **)&d_files));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_COLPOS, cols_total * sizeof(uint32_t), (void **)&d_colpos));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes + bjobs_bytes + res_bytes, (void **)&h_jobs));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes + bjobs_bytes + res_bytes, (void **)&d_jobs));
 		}
-		for (hipEvent_t &e : ev)
-			WHIP(hipEventCreateWithFlags(&e, hipEventBlockingSync));
+		ACM_TRY(make_events(ev, 6));
 	}
 	const auto t_alloc = clk::now();
 	tm.alloc_s = secs(t_hdr, t_alloc);
@@ -261,10 +259,10 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 		pool.run(act.size(), [&](size_t a) { host_stage(act[a]); });
 		tm.host_parsed = act.size();
 		tm.stage_s = secs(t_alloc, clk::now());
-		WHIP(hipEventRecord(ev[0], st));
-		WHIP(hipMemcpyAsync(d_idx, h_idx, idx_total * sizeof(int16_t), hipMemcpyHostToDevice, st));
-		WHIP(hipMemcpyAsync(d_hdr, h_hdr, hdr_total * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
-		WHIP(hipEventRecord(ev[1], st));
+		ACM_HIP_TRY(hipEventRecord(ev[0], st));
+		ACM_HIP_TRY(hipMemcpyAsync(d_idx, h_idx, idx_total * sizeof(int16_t), hipMemcpyHostToDevice, st));
+		ACM_HIP_TRY(hipMemcpyAsync(d_hdr, h_hdr, hdr_total * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
+		ACM_HIP_TRY(hipEventRecord(ev[1], st));
 		timed_h2d = true;
 		tm.h2d_bytes += idx_total * sizeof(int16_t) + hdr_total * sizeof(acmhip_blkhdr);
 	} else if (!act.empty()) {
@@ -279,9 +277,7 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 			const acm_batch_item &f = items[wins[k].item];
 			const Item &it = its[wins[k].item];
 			const acm_block_mark *mk = index[wins[k].item].marks + s.b0;
-			const uint64_t slot = round_up(s.span_len, 16) + 16;
-			memcpy(h_files + s.file_off, f.data + s.span_lo, s.span_len);
-			memset(h_files + s.file_off + s.span_len, 0, slot - s.span_len);       /* the device readers load whole dwords */
+			copy_zero_tail(h_files + s.file_off, f.data + s.span_lo, s.span_len, file_slot_bytes(s.span_len));
 			AcmParseJob j{};
 			j.file_off = s.file_off;
 			j.idx_off = s.idx_off;
@@ -308,44 +304,38 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 			for (size_t k : host_ids) {
 				const Win &s = ws[k];
 				const uint64_t words = (uint64_t)s.nb * its[wins[k].item].info.rows * its[wins[k].item].info.cols;
-				WHIP(hipMemcpyAsync(d_idx + s.idx_off, h_idx + s.idx_off, words * sizeof(int16_t), hipMemcpyHostToDevice, st));
-				WHIP(hipMemcpyAsync(d_hdr + s.hdr_off, h_hdr + s.hdr_off, s.nb * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
+				ACM_HIP_TRY(hipMemcpyAsync(d_idx + s.idx_off, h_idx + s.idx_off, words * sizeof(int16_t), hipMemcpyHostToDevice, st));
+				ACM_HIP_TRY(hipMemcpyAsync(d_hdr + s.hdr_off, h_hdr + s.hdr_off, s.nb * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
 				tm.h2d_bytes += words * sizeof(int16_t) + s.nb * sizeof(acmhip_blkhdr);
 			}
 		}
 		if (nd) {
 			AcmParseResult *d_res = reinterpret_cast<AcmParseResult *>(d_jobs + jobs_bytes + bjobs_bytes);
 			uint32_t *d_flags = reinterpret_cast<uint32_t *>(d_res + nd);
-			WHIP(hipEventRecord(ev[0], st));
-			WHIP(hipMemcpyAsync(d_files, h_files, files_total, hipMemcpyHostToDevice, st));
-			WHIP(hipMemcpyAsync(d_jobs, h_jobs, jobs_bytes + bjobs_bytes, hipMemcpyHostToDevice, st));
-			WHIP(hipEventRecord(ev[1], st));
+			ACM_HIP_TRY(hipEventRecord(ev[0], st));
+			ACM_HIP_TRY(hipMemcpyAsync(d_files, h_files, files_total, hipMemcpyHostToDevice, st));
+			ACM_HIP_TRY(hipMemcpyAsync(d_jobs, h_jobs, jobs_bytes + bjobs_bytes, hipMemcpyHostToDevice, st));
+			ACM_HIP_TRY(hipEventRecord(ev[1], st));
 			timed_h2d = true;
 			tm.h2d_bytes += files_total + jobs_bytes + bjobs_bytes;
-			WHIP(hipMemsetAsync(d_res, 0, res_bytes, st));
-			rc = acmk_launch_parse_blocks(reinterpret_cast<const AcmParseJob *>(d_jobs), (uint32_t)nd,
-						      reinterpret_cast<const AcmBlockJob *>(d_jobs + jobs_bytes), (uint32_t)nbj, d_files, d_colpos, d_idx, d_hdr,
-						      d_res, d_flags, max_columns, st);
-			if (rc != 0) {
-				rc = acmhip_report_hip(rc, "acmk_launch_parse_blocks");
-				cleanup();
-				return rc;
-			}
-			WHIP(hipMemcpyAsync(h_jobs + jobs_bytes + bjobs_bytes, d_res, res_bytes, hipMemcpyDeviceToHost, st));
-			WHIP(hipStreamSynchronize(st));
+			ACM_HIP_TRY(hipMemsetAsync(d_res, 0, res_bytes, st));
+			const int e = acmk_launch_parse_blocks(reinterpret_cast<const AcmParseJob *>(d_jobs), (uint32_t)nd,
+							       reinterpret_cast<const AcmBlockJob *>(d_jobs + jobs_bytes), (uint32_t)nbj, d_files, d_colpos, d_idx,
+							       d_hdr, d_res, d_flags, max_columns, st);
+			if (e != 0)
+				return acmhip_report_hip(e, "acmk_launch_parse_blocks");
+			ACM_HIP_TRY(hipMemcpyAsync(h_jobs + jobs_bytes + bjobs_bytes, d_res, res_bytes, hipMemcpyDeviceToHost, st));
+			ACM_HIP_TRY(hipStreamSynchronize(st));
 			const AcmParseResult *res = reinterpret_cast<const AcmParseResult *>(h_jobs + jobs_bytes + bjobs_bytes);
 			const uint32_t *flags = reinterpret_cast<const uint32_t *>(res + nd);
 			/* what the device is not sure about goes to the exact reader: H1, bad symbols, a block that is not what its marks say */
 			std::vector<size_t> redo;
 			for (size_t a = 0; a < nd; a++)
-				if (res[a].status != 0 || res[a].blocks_done != ws[dev_ids[a]].nb || flags[a] != 0)
+				if (!parse_clean(res[a], flags[a], ws[dev_ids[a]].nb))
 					redo.push_back(dev_ids[a]);
 			tm.device_parsed = nd - redo.size();
 			if (!redo.empty()) {
-				if (!h_idx) {
-					WTRY(acmhip_arena_get(dev, ACM_ARENA_H_IDX, idx_total * sizeof(int16_t), (void **)&h_idx));
-					WTRY(acmhip_arena_get(dev, ACM_ARENA_H_HDR, hdr_total * sizeof(acmhip_blkhdr), (void **)&h_hdr));
-				}
+				ACM_TRY(host_arenas(dev, idx_total, hdr_total, &h_idx, &h_hdr));
 				pool.run(redo.size(), [&](size_t a) { host_stage(redo[a]); });
 				tm.host_parsed += redo.size();
 				for (size_t k : redo) {
@@ -353,8 +343,8 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 					if (!s.active)
 						continue;
 					const uint64_t words = (uint64_t)s.nb * its[wins[k].item].info.rows * its[wins[k].item].info.cols;
-					WHIP(hipMemcpyAsync(d_idx + s.idx_off, h_idx + s.idx_off, words * sizeof(int16_t), hipMemcpyHostToDevice, st));
-					WHIP(hipMemcpyAsync(d_hdr + s.hdr_off, h_hdr + s.hdr_off, s.nb * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
+					ACM_HIP_TRY(hipMemcpyAsync(d_idx + s.idx_off, h_idx + s.idx_off, words * sizeof(int16_t), hipMemcpyHostToDevice, st));
+					ACM_HIP_TRY(hipMemcpyAsync(d_hdr + s.hdr_off, h_hdr + s.hdr_off, s.nb * sizeof(acmhip_blkhdr), hipMemcpyHostToDevice, st));
 					tm.h2d_bytes += words * sizeof(int16_t) + s.nb * sizeof(acmhip_blkhdr);
 				}
 			}
@@ -363,41 +353,26 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 	}
 
 	/* 4. one plan over every window that has samples: a pseudo-stream over its blocks, emitting from the row of its first sample */
-	std::vector<acmhip_stream_desc> descs;
-	std::vector<acmhip_patch> patches;
+	PlanStreams ps;
 	for (size_t k : act) {
 		const Win &s = ws[k];
 		if (!s.active)
 			continue;
-		const Item &it = its[wins[k].item];
-		acmhip_stream_desc d{};
-		d.idx_off = s.idx_off;
-		d.hdr_off = s.hdr_off;
-		d.pcm_off = wins[k].slot_off;
-		d.n_emit = s.lead + wins[k].words;
-		d.level = it.info.level;
-		d.rows = it.info.rows;
-		d.nrows = s.nb * it.info.rows;
-		d.row_begin = s.row_begin;
-		for (acmhip_patch p : s.patches) {
-			p.stream = (uint32_t)descs.size();
-			patches.push_back(p);
-		}
-		descs.push_back(d);
+		const acm_stage_info &info = its[wins[k].item].info;
+		ps.add(info, s.idx_off, s.hdr_off, wins[k].slot_off, s.nb * info.rows, s.row_begin, s.lead + wins[k].words, s.patches);
 		tm.samples += wins[k].words;
 	}
-	if (!descs.empty()) {
-		WTRY(acmhip_plan_create(dev, descs.data(), descs.size(), patches.data(), patches.size(), opts.plan_flags, &plan));
-		WHIP(hipEventRecord(ev[2], st));
-		WTRY(out_f32 ? acmhip_plan_launch_f32(plan, d_idx, d_hdr, reinterpret_cast<float *>(d_pcm))
-			     : acmhip_plan_launch(plan, d_idx, d_hdr, d_pcm, opts.fmt));
-		WHIP(hipEventRecord(ev[3], st));
+	if (!ps.descs.empty()) {
+		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &run.plan));
+		ACM_HIP_TRY(hipEventRecord(ev[2], st));
+		ACM_TRY(launch_plan(run.plan, out_f32, d_idx, d_hdr, d_pcm, opts.fmt));
+		ACM_HIP_TRY(hipEventRecord(ev[3], st));
 		if (!keep_on_device) {
-			WHIP(hipEventRecord(ev[4], st));
-			WHIP(hipMemcpyAsync(h_pcm, d_pcm, pcm_total * pcm_unit, hipMemcpyDeviceToHost, st));
-			WHIP(hipEventRecord(ev[5], st));
+			ACM_HIP_TRY(hipEventRecord(ev[4], st));
+			ACM_HIP_TRY(hipMemcpyAsync(h_pcm, d_pcm, pcm_total * pcm_unit, hipMemcpyDeviceToHost, st));
+			ACM_HIP_TRY(hipEventRecord(ev[5], st));
 		}
-		WHIP(hipStreamSynchronize(st));
+		ACM_HIP_TRY(hipStreamSynchronize(st));
 		float ms = 0;
 		if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
 			tm.h2d_s = ms * 1e-3;
@@ -412,7 +387,15 @@ extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item
 					memcpy(w.pcm, h_pcm + w.dev_off, std::min<uint64_t>(w.words, w.pcm_cap) * sizeof(int16_t));
 			});
 	}
-	cleanup();
+	return ACMHIP_OK;
+}
+
+extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+					acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, acm_window_timing *timing)
+{
+	acm_window_timing tm{};
+	const auto t0 = clk::now();
+	ACM_TRY(decode_windows(dev, items, n, index, wins, nwin, opts_in, tm));
 	tm.total_s = secs(t0, clk::now());
 	if (timing)
 		*timing = tm;
