@@ -2,7 +2,7 @@
 import numpy as np
 
 import oracle_api as O
-from libacm_amd import synth
+from libacm_amd import capi, synth
 
 
 def make_stream(seed, level, rows, nblocks, channels=1, cut=0, **kw):
@@ -10,6 +10,12 @@ def make_stream(seed, level, rows, nblocks, channels=1, cut=0, **kw):
     total = max(1, nblocks * rows * (1 << level) - cut)
     return synth.generate(seed=synth.BASE_SEED + seed, level=level, rows=rows, nblocks=nblocks,
                           channels=channels, total_values=total, **kw)
+
+
+def plan_rows(level):
+    """rows the planner hands out at a time: whole tiles of the lean kernel's vector-ALU build, cut into the byte-plane build's own (a level
+    of the chunk kernel: 2048-sample chunks; level 13: row pairs)"""
+    return max(capi.lib().acmhip_mform_tile_rows(level), capi.lib().acmk_tile2_rows(level), 4)
 
 
 def oracle_pcm(data, force_chans=0, be=0, sgned=1):
@@ -110,35 +116,74 @@ def decode_record(stream_cls_factory, data, force_chans=0, be=0, sgned=1, step=8
     return rec
 
 
+class BitWriter:
+    """Bits LSB first, as libacm_amd/csrc/acm_synth.c writes them: fields are kept as arrays of single bits and packed once (numpy
+    unpackbits / packbits), so a stream of a few hundred thousand fields costs milliseconds."""
+
+    def __init__(self):
+        self.parts = []
+
+    def put(self, v, n):
+        self.put_many([int(v) & ((1 << n) - 1)], n)
+
+    def put_many(self, values, n):
+        """every value of `values` as an n-bit field (n <= 16), one behind the other"""
+        if n:
+            v = np.ascontiguousarray(values, dtype="<u2").reshape(-1, 1)
+            self.parts.append(np.unpackbits(v.view(np.uint8), axis=1, bitorder="little")[:, :n].reshape(-1))
+
+    def put_bits(self, bits):
+        self.parts.append(np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1))
+
+    def stream_header(self, level, rows, total, channels, rate):
+        """reader: decode.c:712-752"""
+        for v, n in ((0x97, 8), (0x28, 8), (0x03, 8), (1, 8), (total & 0xFFFF, 16), (total >> 16, 16), (channels, 16), (rate, 16), (level, 4), (rows, 12)):
+            self.put(v, n)
+
+    def bytes(self):
+        """the stream so far, its last byte filled up with zero bits"""
+        return np.packbits(np.concatenate(self.parts) if self.parts else np.zeros(0, np.uint8), bitorder="little").tobytes()
+
+
 def handmade_stream(level, rows, blocks, channels=1, rate=22050, seed=1):
     """An ACM file written by hand (bits LSB first, as libacm_amd/csrc/acm_synth.c writes them; reader: decode.c:586-589 block
     header, :491-502 column loop, :712-752 stream header): `blocks` = [(pwr, val, code)], every column of a block uses the one
     filler `code` - 0 (no payload) or a linear width 3..16 (rows x code bits, random; keep code <= pwr + 1).  For files whose
     bit rate is as uneven as one likes (the striped upload of acm_batch.cpp has to notice)."""
     rng = np.random.default_rng([0xACE5, seed, level, rows])
-    acc, nbits, out = 0, 0, bytearray()
-
-    def put(v, n):
-        nonlocal acc, nbits
-        acc |= (int(v) & ((1 << n) - 1)) << nbits
-        nbits += n
-        while nbits >= 8:
-            out.append(acc & 0xFF)
-            acc >>= 8
-            nbits -= 8
-
+    w = BitWriter()
     cols = 1 << level
-    total = len(blocks) * rows * cols
-    for v, n in ((0x032897, 24), (1, 8), (total & 0xFFFF, 16), (total >> 16, 16), (channels, 16), (rate, 16), (level, 4), (rows, 12)):
-        put(v, n)
+    w.stream_header(level, rows, len(blocks) * rows * cols, channels, rate)
     for pwr, val, code in blocks:
         assert code == 0 or 3 <= code <= min(16, pwr + 1)
-        put(pwr, 4)
-        put(val, 16)
+        w.put(pwr, 4)
+        w.put(val, 16)
         for _ in range(cols):
-            put(code, 5)
-            for v in rng.integers(0, 1 << code, size=rows) if code else ():
-                put(v, code)
-    if nbits:
-        put(0, 8 - nbits)
-    return bytes(out)
+            w.put(code, 5)
+            if code:
+                w.put_many(rng.integers(0, 1 << code, size=rows), code)
+    return w.bytes()
+
+
+def crafted_stream(level, rows, blocks, channels=1, cut=0, rate=22050):
+    """An ACM file with CHOSEN indices, header and bit order as handmade_stream writes them: `blocks` = [(pwr, val, code, idx)], idx an int
+    array of shape (rows, 1 << level), `code` one linear filler width 3..16 for the whole block (filler value = idx + 2^(code-1)).  Every
+    index lies inside the filler's range and code <= pwr + 1, so every index is inside the block's own amplitude table: no H1 patch.
+    `cut` trims total_values so that the stream does not end on a block boundary."""
+    w = BitWriter()
+    cols = 1 << level
+    w.stream_header(level, rows, max(1, len(blocks) * rows * cols - cut), channels, rate)
+    for pwr, val, code, idx in blocks:
+        idx = np.asarray(idx)
+        assert idx.shape == (rows, cols) and 3 <= code <= min(16, pwr + 1) and 0 <= pwr <= 15 and 0 <= val <= 65535
+        half = 1 << (code - 1)
+        assert -half <= int(idx.min()) and int(idx.max()) < half, (code, int(idx.min()), int(idx.max()))
+        w.put(pwr, 4)
+        w.put(val, 16)
+        # column by column: the 5-bit code, then the column's `rows` values of `code` bits each
+        fill = np.ascontiguousarray((idx.T.astype(np.int64) + half).astype("<u2")).reshape(cols, rows, 1)
+        bits = np.empty((cols, 5 + rows * code), dtype=np.uint8)
+        bits[:, :5] = (code >> np.arange(5)) & 1
+        bits[:, 5:] = np.unpackbits(fill.view(np.uint8), axis=2, bitorder="little")[:, :, :code].reshape(cols, rows * code)
+        w.put_bits(bits)
+    return w.bytes()

@@ -5,7 +5,7 @@ the host stager (acmhip_mform_rows, acm_pack.cpp) against the CPU oracle, bit-ex
 import numpy as np
 import pytest
 
-from helpers import fmt_args, make_stream, oracle_pcm
+from helpers import fmt_args, make_stream, oracle_pcm, plan_rows
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +20,6 @@ def force_k2(monkeypatch):
 
 def tile_rows(level):
     return capi.lib().acmhip_mform_tile_rows(level)
-
-
-def plan_rows(level):
-    """rows the planner hands out at a time: whole tiles of the lean kernel's vector-ALU build, cut into the byte-plane build's own (a level
-    of the chunk kernel: 2048-sample chunks; level 13: row pairs)"""
-    return max(tile_rows(level), capi.lib().acmk_tile2_rows(level), 4)
 
 
 def check(dev, files, fmt=capi.FMT_S16LE, force_chans=0):
