@@ -81,6 +81,9 @@ def run_f32(dev, files, flags=capi.PLAN_AUTO, form="int16", windows=None):
         assert bad.size == 0, "stream %d (level %d rows %d): %d of %d floats differ, first at %d" % (k, s.info.level, s.info.rows, bad.size, d.n_emit, bad[0])
         written[a:b] = True
     assert (h32[~written] == 0xFFFFFFFF).all(), "float writes outside the streams' samples: %s" % np.nonzero(h32[~written] != 0xFFFFFFFF)[0][:8]
+    for rep in range(2):
+        assert (out16[rep][~written] == 0xA5A5).all(), "int16 launch %d writes outside the streams' samples: %s" % (
+            rep, np.nonzero(~written & (out16[rep] != 0xA5A5))[0][:8])
     return st
 
 
@@ -263,6 +266,7 @@ def test_batch_f32(dev, parse, ranges, staging):
         if s16[k] == 0:
             assert np.array_equal(h16[a:b], oracle_pcm(f)[0]), k
     assert (h32[~written] == 0xFFFFFFFF).all()
+    assert (h16[~written] == 0xA5A5).all()
 
 
 def test_batch_f32_refusals(dev):

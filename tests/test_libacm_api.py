@@ -370,6 +370,33 @@ def test_interleaved_reads_on_two_streams(side):
     assert b"".join(ga) == wa and b"".join(gb) == wb
 
 
+def test_acm_read_writes_no_byte_beyond_the_request(side):
+    """acm_read(buf, n) into a buffer of n bytes + 64 guard bytes: requests of a sample, three samples, just below and above a 4 KB
+    page and far beyond one read-ahead window's first rows, on a mono and a stereo stream, with a seek between the reads - the guard
+    bytes stay as they were, return values and bytes are the oracle's"""
+    from helpers import make_stream
+    L = O.bind_libacm(capi.lib())
+    for ch, (lv, rows, nb) in ((1, (7, 16, 90)), (2, (9, 5, 44))):
+        f = make_stream(2800 + ch, lv, rows, nb, channels=ch, cut=3 * ch)
+        s, o = ours(f), O.Oracle(f)
+        assert s.err == 0 and o.err == 0
+        for k, n in enumerate((2, 6, 4094, 4098, 123458, 4098, 6, 4094)):
+            if k == 5:
+                pos = 1237 if ch == 1 else 30011
+                assert s.seek_pcm(pos) == o.seek_pcm(pos) == pos
+            be, sg = k % 2, 1 - (k // 2) % 2
+            buf = (C.c_uint8 * (n + 64))()
+            C.memset(buf, 0xA5, n + 64)
+            rc = L.acm_read(s.h, buf, n, be, 2, sg)
+            want_rc, want = o.read(n, be=be, sgned=sg)
+            assert rc == want_rc and (rc > 0 or (ch == 2 and n == 2)), (ch, k, n, rc, want_rc)
+            assert bytes(buf[:max(rc, 0)]) == want, (ch, k, n)
+            assert bytes(buf[n:]) == b"\xA5" * 64, (ch, k, n)
+            assert s.getter("pcm_tell") == o.getter("pcm_tell")
+        s.close()
+        o.close()
+
+
 def read_digest(rc_bytes):
     """(rc, PCM bytes) of one read -> [rc, sha256 of the bytes], the form the reference's recorded answers take"""
     return [rc_bytes[0], sha(rc_bytes[1])]
