@@ -594,6 +594,74 @@ uint64_t acm_batch_window_pcm_words(const acm_batch_item *items, size_t n, const
 int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 			      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, acm_window_timing *timing);
 
+/* ------------------------------------------------------------------------
+ * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs
+ * before its first crop.  acm_index_file parses a whole file to get it, decoding every filler index and dropping it; the device
+ * only WALKS the stream (acm_index_scan_wave, csrc/acm_parse.hip: one stream per wavefront, the walk of acm_batch_decode's device
+ * parser without its column offsets), validates the ternary columns it skips by length, and writes one acm_block_mark per block:
+ * 16 bytes of device memory per block beside the file image, nothing per column or per sample.
+ *
+ * For every item, marks[0 .. blocks], blocks, end_status and status are byte for byte what
+ * acm_index_file(data, len, force_chans, marks, max_blocks, &info) writes and returns (info.blocks, info.end_status, the return
+ * code), whoever did the work.  The device takes the clean streams; a stream it flags (data running out, an invalid filler code,
+ * a ternary symbol out of range), whose walk ends short of the blocks the header promises, whose last mark lies behind the end
+ * of the file, or that the layout kept off the device (not ACM, no room for marks, a file of 256 MiB or more, a header that
+ * promises more blocks than the bytes can hold, unless max_blocks asks for fewer than they could hold) goes to the host pool, which runs acm_index_file on it while later groups are
+ * still on the device.  A dirty stream never fails the call.  H1 does not matter to an index: such streams stay on the device.
+ *
+ * The batch travels in groups (csrc/acm_index_layout.cpp: file bytes + marks of a group <= opts->max_group_bytes, at most 32768
+ * streams); the upload of group k + 1 overlaps the walk of group k, so the device holds two groups at most.
+ *
+ * opts->parse:
+ *   ACM_BATCH_PARSE_HOST    the pool only; dev may be NULL (a box without a GPU).
+ *   ACM_BATCH_PARSE_DEVICE  the device walk for every stream the layout lets it have; dev == NULL: ACMHIP_ERR_NO_DEVICE.
+ *   ACM_BATCH_PARSE_AUTO    DEVICE when the batch is worth at least 12 x threads streams of its longest stream's size (192 at 16 threads),
+ *                           HOST below that and when dev is NULL.  Measured on an MI355X with 16 host threads
+ *                           (profiles/index_build_notes.txt): a launch of the walk lasts as long as its longest stream however many
+ *                           streams it has - 35 ms for 2 Msamples -, so the pool wins small batches (256 files of the 4000-file
+ *                           corpus, 47 streams' worth: 15 against 48 ms), the two meet at 1024 of its files (196 streams' worth,
+ *                           56 against 60 ms) and the device is ahead beyond: the whole corpus 116 against 338 ms for the host parser
+ *                           (batch.build_index), 1024 level-9 streams of 250 blocks 70 against 232 ms.
+ * opts == NULL: AUTO, the library's group size, one thread per CPU.
+ * ---------------------------------------------------------------------- */
+typedef struct acm_batch_index_out {     /* one per item */
+	acm_block_mark *marks;           /* in:  room for max_blocks + 1 marks */
+	size_t   max_blocks;             /* in */
+	uint32_t blocks;                 /* out: acm_stage_info.blocks of acm_index_file */
+	int32_t  end_status;             /* out: acm_stage_info.end_status of acm_index_file */
+	int32_t  status;                 /* out: what acm_index_file returns for this item: ACM_OK, ACM_ERR_NOT_ACM, ACMHIP_ERR_ARG */
+	uint32_t reserved;
+} acm_batch_index_out;
+
+typedef struct acm_index_opts {
+	int      force_chans;
+	int      threads;                /* host pool, 0 = one per CPU */
+	unsigned parse;                  /* ACM_BATCH_PARSE_* */
+	unsigned reserved;
+	uint64_t max_group_bytes;        /* file bytes + marks of one group on the device; 0 = the library decides (1 GiB: every group costs
+	                                    the walk of its longest stream again, groups only bound the memory) */
+} acm_index_opts;
+
+typedef struct acm_index_timing {
+	double   stage_s;                /* host time spent filling the pinned file arena and the job tables */
+	double   h2d_s, kernel_s, d2h_s; /* device-side durations summed over the groups (they overlap each other and the host pool) */
+	double   total_s;                /* wall clock of the whole call */
+	uint64_t blocks;                 /* blocks indexed, by anyone */
+	uint64_t device_indexed;         /* items whose marks are the device walk's ... */
+	uint64_t host_indexed;           /* ... and items acm_index_file ran on (the two add up to n) */
+	uint64_t h2d_bytes;              /* file images and job tables sent to the device */
+	uint64_t device_bytes;           /* device memory the call worked in: two groups of file slots, marks, jobs and results */
+	uint32_t groups;
+	uint32_t reserved;
+} acm_index_timing;
+
+/* blocks to make room for: per_item[i] (may be NULL) = the max_blocks that lets item i's whole index fit (the blocks its header
+ * promises, but no more than its bytes can hold; 0 for a file that is not ACM) - marks takes one entry more.  Returns their sum. */
+uint64_t acm_batch_index_blocks(const acm_batch_item *items, size_t n, int force_chans, uint64_t *per_item);
+/* items: data / len are read, nothing is written.  out[i] belongs to items[i]. */
+int  acm_batch_index_files(acmhip_device *dev, const acm_batch_item *items, size_t n, acm_batch_index_out *out,
+			   const acm_index_opts *opts, acm_index_timing *timing);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,12 +75,16 @@ def pcm_capacity_words(head, file_len, force_chans=0):
     return (blocks * bl + 63) // 64 * 64
 
 
-def build_index(files, threads=0):
+def build_index(files, threads=0, decoder=None):
     """The block index of every file (capi.index_file: start bit, val and pwr of each block - 16 bytes per block), built once on the
     host and kept: GpuDecoder.crop() takes it back on every call.  files: paths or file images.  Returns a list of numpy record arrays
     (capi.BlockIndex: capi.BLOCK_MARK_DT records that also remember how the stream ends; np.save / np.load keep the records), an empty
-    one for a file that is not ACM.  threads: 0 = one per CPU, at most 64."""
+    one for a file that is not ACM.  threads: 0 = one per CPU, at most 64.
+    decoder: a GpuDecoder - the index is built through its device handle (GpuDecoder.build_index: the device walks the clean streams
+    where that pays, the same marks either way); None: the host parser, file by file."""
     from concurrent.futures import ThreadPoolExecutor
+    if decoder is not None:
+        return decoder.build_index(files, threads=threads)
 
     def one(f):
         try:
@@ -114,6 +118,7 @@ class GpuDecoder:
         self.fmt = fmt
         self.parse = parse
         self.timing = None
+        self.index_timing = None
         torch.cuda.set_device(ordinal)
         # the library runs on a stream of its own (torch's current stream is usually the null stream, which
         # acmhip_device_open does not adopt); __call__ orders the two around the torch-owned PCM tensor
@@ -142,14 +147,26 @@ class GpuDecoder:
         return d_pcm, offsets, words, statuses
 
 
-    def crop(self, files, windows, index, out=None):
-        """Random-access crops: windows = (file_no, first_sample, n_samples) triples over interleaved samples, index = build_index(files).
+    def build_index(self, files, threads=0, parse=None, max_group_bytes=0):
+        """The block index of every file, as batch.build_index(files) returns it, through acm_batch_index_files: the device walks the
+        clean streams and writes 16 bytes per block (parse=capi.PARSE_DEVICE; the decoder's own parse mode by default), the host pool
+        indexes what the device is not sure about.  self.index_timing: the call's capi.IndexTiming."""
+        files = [_load(f) for f in files]
+        index, self.index_timing = capi.batch_index_files(self.dev, files, parse=self.parse if parse is None else parse,
+                                                          max_group_bytes=max_group_bytes, threads=threads)
+        return index
+
+    def crop(self, files, windows, index=None, out=None):
+        """Random-access crops: windows = (file_no, first_sample, n_samples) triples over interleaved samples, index = build_index(files)
+        (None: built here, through this decoder - keep it where more than one call crops the same files).
         Only the blocks a window needs are parsed, uploaded and synthesised.
         -> (pcm tensor in HBM of this decoder's dtype, per-window offsets of the first requested sample, per-window sample counts,
         per-window statuses).  Window k is pcm[offsets[k] : offsets[k] + counts[k]] = the whole decode's [first : first + n], clipped to
         the end of the stream."""
         torch = self.torch
         files = [_load(f) for f in files]
+        if index is None:
+            index = self.build_index(files)
         cap = capi.batch_window_pcm_words(files, windows)
         if out is not None and out.dtype != self.dtype:
             raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))

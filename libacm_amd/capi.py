@@ -129,6 +129,21 @@ class WindowTiming(C.Structure):
                 ("h2d_bytes", C.c_uint64), ("blocks_parsed", C.c_uint64)]
 
 
+class BatchIndexOut(C.Structure):
+    _fields_ = [("marks", C.c_void_p), ("max_blocks", C.c_size_t), ("blocks", C.c_uint32), ("end_status", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class IndexOpts(C.Structure):
+    _fields_ = [("force_chans", C.c_int), ("threads", C.c_int), ("parse", C.c_uint), ("reserved", C.c_uint), ("max_group_bytes", C.c_uint64)]
+
+
+class IndexTiming(C.Structure):
+    _fields_ = [("stage_s", C.c_double), ("h2d_s", C.c_double), ("kernel_s", C.c_double), ("d2h_s", C.c_double), ("total_s", C.c_double),
+                ("blocks", C.c_uint64), ("device_indexed", C.c_uint64), ("host_indexed", C.c_uint64), ("h2d_bytes", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("groups", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/acm_hip.h declares (checked by tests/test_abi.py)
 ACMHIP_SYMBOLS = [
     "acmhip_last_error", "acmhip_device_count", "acmhip_device_open", "acmhip_device_close",
@@ -141,6 +156,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows",
+    "acm_batch_index_blocks", "acm_batch_index_files",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -232,6 +248,9 @@ def lib():
     L.acm_batch_window_pcm_words.restype = C.c_uint64
     L.acm_batch_decode_windows.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
                                            C.POINTER(BatchOpts), C.POINTER(WindowTiming)]
+    L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
+    L.acm_batch_index_blocks.restype = C.c_uint64
+    L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
     _lib = L
     return L
 
@@ -933,3 +952,35 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
     _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
     return ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], [int(wins[k].dev_off) for k in range(nw)],
             [(int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)], tm)
+
+
+# --------------------------------------------------------------------------- the block index of a batch
+def batch_index_files(dev, files, parse=PARSE_AUTO, max_group_bytes=0, force_chans=0, threads=0, max_blocks=None, return_status=False):
+    """acm_batch_index_files over a list of file images -> (list of BlockIndex, IndexTiming): entry i is what index_file(files[i])
+    returns - the device walks the clean streams (PARSE_DEVICE, or PARSE_AUTO where it pays), the host pool indexes the rest - and an
+    empty index for a file that is not ACM (status ACM_ERR_NOT_ACM).  dev: a Device, or None with PARSE_HOST / PARSE_AUTO (the pool only).
+    max_blocks (tests): the room per item instead of what acm_batch_index_blocks asks for.  return_status: the per-item return codes as a third
+    value."""
+    bufs, items = _batch_items(files)
+    n = len(files)
+    need = np.zeros(max(n, 1), dtype=np.uint64)
+    lib().acm_batch_index_blocks(items, n, force_chans, need.ctypes.data)
+    if max_blocks is not None:
+        need[:n] = max_blocks
+    at = np.zeros(n + 1, dtype=np.int64)
+    at[1:] = np.cumsum(need[:n].astype(np.int64) + 1)
+    marks = np.zeros(int(at[n]), dtype=BLOCK_MARK_DT)
+    out = (BatchIndexOut * max(n, 1))()
+    for k in range(n):
+        out[k].marks = marks.ctypes.data + int(at[k]) * BLOCK_MARK_DT.itemsize
+        out[k].max_blocks = int(need[k])
+    opts = IndexOpts(force_chans, threads, parse, 0, max_group_bytes)
+    tm = IndexTiming()
+    _check(lib().acm_batch_index_files(dev.h if dev is not None else None, items, n, out, C.byref(opts), C.byref(tm)), "acm_batch_index_files")
+    res = []
+    for k in range(n):
+        if out[k].status != 0:
+            res.append(as_index(np.zeros(0, dtype=BLOCK_MARK_DT), None))
+        else:
+            res.append(as_index(marks[int(at[k]):int(at[k]) + out[k].blocks + 1].copy(), out[k].end_status))
+    return (res, tm, [int(out[k].status) for k in range(n)]) if return_status else (res, tm)

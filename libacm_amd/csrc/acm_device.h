@@ -138,8 +138,11 @@ enum {
 	ACM_ARENA_H_IDX = 0, ACM_ARENA_H_HDR, ACM_ARENA_H_PCM, ACM_ARENA_H_FILES, ACM_ARENA_H_JOBS, ACM_ARENA_H_PKBLOB, ACM_ARENA_H_PKCHUNK,
 	ACM_ARENA_D_IDX, ACM_ARENA_D_HDR, ACM_ARENA_D_PCM, ACM_ARENA_D_FILES, ACM_ARENA_D_COLPOS, ACM_ARENA_D_JOBS, ACM_ARENA_D_STAGE,
 	ACM_ARENA_D_PKBLOB, ACM_ARENA_D_PKCHUNK, ACM_ARENA_D_BLKOFF,
+	ACM_ARENA_D_MARKS, ACM_ARENA_H_MARKS,           /* batch index build (acm_batch_index.cpp): the marks of two groups, on the device and pinned */
 	ACM_ARENA_SLOTS
 };
+/* is this slot pinned host memory (else device memory)? */
+static inline int acm_arena_is_host(int slot) { return slot < ACM_ARENA_D_IDX || slot == ACM_ARENA_H_MARKS; }
 int acmhip_arena_get(acmhip_device *dev, int slot, size_t bytes, void **out);
 void acmhip_arena_lock(acmhip_device *dev);
 void acmhip_arena_unlock(acmhip_device *dev);
@@ -217,6 +220,13 @@ int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const 
 int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock, const uint8_t *d_files,
 			     uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags,
 			     uint64_t max_columns, void *stream);
+/* The block index of njobs streams (<= ACM_PARSE_RANGE_MAX_STREAMS), one wavefront each (acm_index_scan_wave): of a job only file_off, file_len,
+ * data_start, level, rows, blocks and hdr_off - here the stream's first entry of d_marks - are read.  Block b of stream j leaves
+ * d_marks[hdr_off + b] = { bit, val, pwr }, a walk that covers all its blocks also d_marks[hdr_off + blocks] = { end bit, 0, 0 }; d_res[j] =
+ * { blocks done, status, end bit }.  status != 0: data ran out, an invalid filler code, or a ternary symbol out of range (codes 19, 22, 29:
+ * validated here, not only skipped) - the exact host reader takes the stream.  Nothing per column is written. */
+int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, acm_block_mark *d_marks, AcmParseResult *d_res,
+		      void *stream);
 /* Striped upload of a block-range batch: every file's arena slot (the file padded to 16 bytes + 16 zero bytes) is cut into R
  * stripes at acmk_stripe_bound(len, s, R); stripe s of all files travels as ONE transfer into a staging arena and a scatter
  * kernel puts the pieces in place, so the first ranges are walked, synthesised and read back while the later stripes are

@@ -204,7 +204,7 @@ extern "C" void acmhip_device_close(acmhip_device *dev)
 	for (int k = 0; k < ACM_ARENA_SLOTS; k++) {
 		if (!dev->arena[k])
 			continue;
-		if (k < ACM_ARENA_D_IDX)
+		if (acm_arena_is_host(k))
 			(void)hipHostFree(dev->arena[k]);
 		else
 			(void)hipFree(dev->arena[k]);
@@ -236,7 +236,7 @@ extern "C" int acmhip_arena_get(acmhip_device *dev, int slot, size_t bytes, void
 		HIPTRY(hipSetDevice(dev->ordinal));
 		if (dev->arena[slot]) {
 			HIPTRY(hipStreamSynchronize(dev->stream));
-			if (slot < ACM_ARENA_D_IDX)
+			if (acm_arena_is_host(slot))
 				(void)hipHostFree(dev->arena[slot]);
 			else
 				(void)hipFree(dev->arena[slot]);
@@ -244,7 +244,7 @@ extern "C" int acmhip_arena_get(acmhip_device *dev, int slot, size_t bytes, void
 			dev->arena_cap[slot] = 0;
 		}
 		const size_t want = bytes + bytes / 8;          /* a little headroom against creeping batches */
-		if (slot < ACM_ARENA_D_IDX)
+		if (acm_arena_is_host(slot))
 			HIPTRY(hipHostMalloc(&dev->arena[slot], want, hipHostMallocDefault));
 		else
 			HIPTRY(hipMalloc(&dev->arena[slot], want));

@@ -17,6 +17,8 @@
  *                      contiguous run of the row-major staged form the synthesis kernels read.  Symbols of
  *                      the k/t fillers come out of a 7-bit look-up table in LDS: one code path for all of
  *                      them, so lanes holding different fillers do not serialise.
+ *   acm_index_scan_wave  the wave-per-stream walk once more, for the block index of a batch (acm_batch_index.cpp): one 16-byte mark
+ *                      per block, nothing per column, the ternary columns validated by the whole wavefront.
  *
  * The device handles the CLEAN path only.  Anything it is not sure to reproduce bit for bit - data
  * running out, an invalid filler code (decode.c:190-194), a ternary symbol out of range (:412, :438, :464),
@@ -620,6 +622,116 @@ out:
 	}
 }
 
+/*
+ * The block index of a stream: the walk of acm_parse_scan_wave with nothing per column.
+ *
+ * An index (include/acm_hip.h: acm_block_mark) needs where every block starts and its (val, pwr) header - both fall out of the walk, so
+ * a batch of files is indexed at the walk's rate without decoding a value: same register file (window, code tables through
+ * v_readlane), same fixed-length fast loop and k-column descent, no column offsets, no block offsets, no pair table.  One 16-byte
+ * mark per block leaves through lane 0's vector store, as the block header does there.
+ * What the walk above leaves to the column kernel has to happen here: a ternary column (codes 19, 22, 29) is skipped by its length,
+ * but the host reader ends the stream on a symbol out of range inside it (decode.c:412, :438, :464).  Such codes get a sentinel of
+ * their own in the length table - the fast loop keeps its single exit - and the whole wavefront validates the column: lane g takes
+ * groups g, g + 64, ...; a ballot decides.  A bad symbol flags the stream like data running out or an invalid code does, and the
+ * exact host reader indexes it (acm_batch_index.cpp).
+ */
+constexpr uint32_t TERN_CHECK = 0xFFFFFFFDu;    /* code_len of a ternary filler here: fixed length, but look inside */
+
+/* are all `groups` symbols of the ternary column whose payload starts at `bit` in range?  The column ends inside the file (the caller
+ * checked).  A group is read out of the window where the window holds it (two ds_bpermute); a column may be longer than the window -
+ * 4095 rows of code 22 are 9555 bits - and a lane whose group lies behind it fetches its own two dwords. */
+__device__ __forceinline__ bool tern_column_valid(WaveWindow &ww, const uint32_t bit, const uint32_t code, const uint32_t groups)
+{
+	const uint32_t width = code == 19u ? 5u : 7u, lim = code == 19u ? 27u : code == 22u ? 125u : 121u;
+	(void)ww.at(bit);
+	bool bad = false;
+	for (uint32_t g0 = 0; g0 < groups; g0 += 64u) {         /* (wave-uniform trip count: every lane takes part in the permutes) */
+		const uint32_t g = g0 + ww.lane;
+		const uint32_t pos = bit + min(g, groups - 1u) * width;
+		const uint32_t dw = pos >> 5, r = dw - ww.base;
+		uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.lo);
+		uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.hi);
+		if (r > 63u) {
+			a = __builtin_nontemporal_load(ww.w + min(dw, ww.maxdw));
+			b = __builtin_nontemporal_load(ww.w + min(dw + 1u, ww.maxdw));
+		}
+		const uint32_t v = (uint32_t)((((uint64_t)b << 32) | a) >> (pos & 31u)) & ((1u << width) - 1u);
+		bad |= g < groups && v >= lim;
+	}
+	return __builtin_amdgcn_ballot_w64(bad) == 0;
+}
+
+__global__ void __launch_bounds__(64 * WAVE_SCAN_WAVES)
+acm_index_scan_wave(const AcmParseJob *__restrict__ jobs, const uint32_t njobs, const uint8_t *__restrict__ files,
+		    acm_block_mark *__restrict__ marks, AcmParseResult *__restrict__ res)
+{
+	const uint32_t jobno = blockIdx.x * WAVE_SCAN_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	if (jobno >= njobs)
+		return;
+	const uint32_t lane = threadIdx.x & 63u;
+	const AcmParseJob job = jobs[jobno];
+	const uint32_t rows = job.rows, cols = 1u << job.level;
+	const uint32_t safe = 8u * job.file_len;
+	/* per-lane tables, looked up with v_readlane: lane = filler code */
+	const uint32_t code_len = code_class(lane & 31u) == CLS_TERN ? TERN_CHECK : column_bits(lane & 31u, rows);
+	const uint32_t code_tab = k_table_for(lane & 31u);
+	WaveWindow ww;
+	ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
+	ww.maxdw = (job.file_len + 15u) / 4u;
+	ww.lane = lane;
+	uint32_t bit = job.data_start * 8u;
+	ww.load(bit >> 5);
+	/* a mark as one 16-byte store: bit (files are < 256 MiB: the high word is zero), val, pwr */
+	uint4 *const mk = reinterpret_cast<uint4 *>(marks + job.hdr_off);
+	uint32_t done = 0, status = 1;
+	for (uint32_t b = 0; b < job.blocks; b++) {
+		if (bit + 20 > safe)
+			goto out;
+		const uint32_t at = bit;
+		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
+		bit += 20;
+		for (uint32_t k = 0;;) {
+			/* the fast loop of acm_parse_scan_wave: fixed-length columns whose inside does not matter, one exit */
+			uint32_t code, len;
+			bool fixed;
+			do {
+				code = (uint32_t)ww.peek64(bit) & 31u;
+				len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
+				fixed = len < TERN_CHECK;
+				bit += 5 + (fixed ? len : 0u);
+				k++;
+			} while (fixed & (bit <= safe) & (k < cols));
+			if (!fixed) {
+				if (len == TERN_CHECK) {
+					const uint32_t groups = code == 29u ? (rows + 1u) / 2u : (rows + 2u) / 3u;
+					const uint32_t nbits = column_bits(code, rows);         /* the last group is whole */
+					if (bit + nbits > safe || !tern_column_valid(ww, bit, code, groups))
+						goto out;
+					bit += nbits;
+				} else if (len == K_WALK) {
+					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
+					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
+				} else {
+					goto out;
+				}
+			}
+			if (bit > safe)                                 /* the column must end inside the file */
+				goto out;
+			if (k >= cols)
+				break;
+		}
+		if (lane == 0)
+			mk[b] = make_uint4(at, 0u, h20 >> 4, h20 & 15u);
+		done++;
+	}
+	status = 0;
+	if (lane == 0)
+		mk[done] = make_uint4(bit, 0u, 0u, 0u);         /* the entry behind the last block: where it ends */
+out:
+	if (lane == 0)
+		res[jobno] = AcmParseResult{ done, status, bit, 0u };
+}
+
 /* ---- kernel 2: decode the columns ---- */
 
 /* One look-up entry per (k/t filler, next 7 bits): the symbol at the head of those bits.
@@ -1011,6 +1123,19 @@ extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njob
 				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, 0u, 1u, nullptr, nullptr, nullptr);
 		ACMP_CHECK();
 	}
+	return 0;
+}
+
+extern "C" int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, acm_block_mark *d_marks, AcmParseResult *d_res,
+				 void *stream)
+{
+	if (njobs == 0)
+		return 0;
+	if (njobs > ACM_PARSE_RANGE_MAX_STREAMS)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL(acm_index_scan_wave, dim3((njobs + WAVE_SCAN_WAVES - 1) / WAVE_SCAN_WAVES), dim3(64 * WAVE_SCAN_WAVES), 0, (hipStream_t)stream,
+			   d_jobs, njobs, d_files, d_marks, d_res);
+	ACMP_CHECK();
 	return 0;
 }
 
