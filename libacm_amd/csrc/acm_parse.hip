@@ -9,16 +9,19 @@
  *
  *   acm_parse_scan     one LANE per stream walks its stream and writes colpos[block][column] (the bit offset
  *                      of every column's 5-bit code) and the block headers.  Sequential per stream, light.
- *                      Up to 32 K streams: acm_parse_scan_wave, one stream per WAVEFRONT - the walk is wave-uniform
- *                      on the scalar unit, the lanes are its register file (bitstream window, code tables, column
- *                      offsets) and resolve a k-column together; 2.2x round 1's scalar walk on 1024 long streams.
+ *                      Up to 32 K streams a WAVEFRONT walks instead - the walk is wave-uniform on the scalar unit, the
+ *                      lanes are its register file (bitstream window, code tables, column offsets) and resolve a
+ *                      k-column together; 2.2x round 1's scalar walk on 1024 long streams.  That walk exists once,
+ *                      WaveWalk<OFFSETS, TERN>, and three kernels are built around it:
+ *     acm_parse_scan_wave    one stream per wavefront, whole or in block ranges   (OFFSETS)
+ *     acm_parse_scan_blocks  one indexed block per wavefront (acm_batch_windows.cpp)   (OFFSETS)
+ *     acm_index_scan_wave    one stream per wavefront for the block index of a batch (acm_batch_index.cpp): one 16-byte
+ *                            mark per block, nothing per column, the ternary columns validated by the whole wavefront   (TERN)
  *   acm_parse_columns  one LANE per COLUMN decodes `rows` indices from its bit offset.  64 adjacent columns
  *                      per wavefront, all lanes produce row r in the same iteration, so every store is a
  *                      contiguous run of the row-major staged form the synthesis kernels read.  Symbols of
  *                      the k/t fillers come out of a 7-bit look-up table in LDS: one code path for all of
  *                      them, so lanes holding different fillers do not serialise.
- *   acm_index_scan_wave  the wave-per-stream walk once more, for the block index of a batch (acm_batch_index.cpp): one 16-byte mark
- *                      per block, nothing per column, the ternary columns validated by the whole wavefront.
  *
  * The device handles the CLEAN path only.  Anything it is not sure to reproduce bit for bit - data
  * running out, an invalid filler code (decode.c:190-194), a ternary symbol out of range (:412, :438, :464),
@@ -32,7 +35,7 @@
 
 #include "acm_device.h"
 
-#pragma clang diagnostic ignored "-Winline-asm"         /* m0 on a clobber list: see acm_parse_scan_wave */
+#pragma clang diagnostic ignored "-Winline-asm"         /* m0 on a clobber list: see WaveWalk */
 
 namespace {
 
@@ -405,8 +408,116 @@ __device__ __forceinline__ uint32_t walk_k_column(WaveWindow &ww, uint32_t pos, 
 	return rows_left ? 0xFFFFFFFFu : pos;
 }
 
+constexpr uint32_t TERN_CHECK = 0xFFFFFFFDu;    /* code_len of a ternary filler where its inside matters: fixed length, but look inside */
+
+/* are all `groups` symbols of the ternary column whose payload starts at `bit` in range?  The column ends inside the file (the caller
+ * checked).  A group is read out of the window where the window holds it (two ds_bpermute); a column may be longer than the window -
+ * 4095 rows of code 22 are 9555 bits - and a lane whose group lies behind it fetches its own two dwords. */
+__device__ __forceinline__ bool tern_column_valid(WaveWindow &ww, const uint32_t bit, const uint32_t code, const uint32_t groups)
+{
+	const uint32_t width = code == 19u ? 5u : 7u, lim = code == 19u ? 27u : code == 22u ? 125u : 121u;
+	(void)ww.at(bit);
+	bool bad = false;
+	for (uint32_t g0 = 0; g0 < groups; g0 += 64u) {         /* (wave-uniform trip count: every lane takes part in the permutes) */
+		const uint32_t g = g0 + ww.lane;
+		const uint32_t pos = bit + min(g, groups - 1u) * width;
+		const uint32_t dw = pos >> 5, r = dw - ww.base;
+		uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.lo);
+		uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.hi);
+		if (r > 63u) {
+			a = __builtin_nontemporal_load(ww.w + min(dw, ww.maxdw));
+			b = __builtin_nontemporal_load(ww.w + min(dw + 1u, ww.maxdw));
+		}
+		const uint32_t v = (uint32_t)((((uint64_t)b << 32) | a) >> (pos & 31u)) & ((1u << width) - 1u);
+		bad |= g < groups && v >= lim;
+	}
+	return __builtin_amdgcn_ballot_w64(bad) == 0;
+}
+
+/*
+ * The walk core: the one walk of the three wavefront kernels below.  It owns the register file (window, code tables), the block
+ * header read, the fixed-length fast loop, the k-column descent and the bounds check; a kernel keeps what it does with a block.
+ * Two switches, both fixed at compile time:
+ *   OFFSETS  the bit offset of every column's code collects in `cpv` (v_writelane; lane k = the k-th column of the call, so a call
+ *            walks at most 64 columns) for the caller to store, coalesced
+ *   TERN     what a walk without a column kernel behind it has to do itself: a ternary column (codes 19, 22, 29) is skipped by its
+ *            length, but the host reader ends the stream on a symbol out of range inside it (decode.c:412, :438, :464).  Such codes
+ *            get a sentinel of their own in the length table - the fast loop keeps its single exit - and the whole wavefront
+ *            validates the column: lane g takes groups g, g + 64, ...; a ballot decides
+ */
+template <bool OFFSETS, bool TERN>
+struct WaveWalk {
+	WaveWindow ww;          /* (the caller loads it, once it knows where it starts) */
+	uint32_t rows;
+	uint32_t code_len, code_tab;    /* per-lane tables, looked up with v_readlane: lane = filler code */
+	uint32_t cpv;           /* OFFSETS: the offsets of the columns the last call walked */
+
+	__device__ __forceinline__ void setup(const AcmParseJob &job, const uint8_t *__restrict__ files, const uint32_t lane)
+	{
+		rows = job.rows;
+		code_len = TERN && code_class(lane & 31u) == CLS_TERN ? TERN_CHECK : column_bits(lane & 31u, rows);
+		code_tab = k_table_for(lane & 31u);
+		ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
+		ww.maxdw = (job.file_len + 15u) / 4u;
+		ww.lane = lane;
+	}
+	/* the 20-bit block header at `bit` (val << 4 | pwr); the caller checked that it lies inside the file */
+	__device__ __forceinline__ uint32_t header(uint32_t &bit)
+	{
+		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
+		bit += 20;
+		return h20;
+	}
+	/* walk n >= 1 columns from `bit`, none of them ending behind `safe`; false: the walk must stop - data running out, an invalid code,
+	 * (TERN) a ternary symbol out of range */
+	__device__ __forceinline__ bool columns(uint32_t &bit, const uint32_t n, const uint32_t safe)
+	{
+		constexpr uint32_t SLOW = TERN ? TERN_CHECK : K_WALK;   /* lengths from here on are sentinels */
+		uint32_t k = 0;
+		if (OFFSETS)
+			cpv = 0;
+		for (;;) {
+			/* the fast loop: fixed-length columns whose inside does not matter, one exit; why it ended is sorted out behind it.
+			 * A column that starts in the last 5 bits of the file ends behind it: one bounds check, at the end. */
+			uint32_t code, len;
+			bool fixed;
+			do {
+				/* cpv[lane k] = bit.  Two scalar operands do not fit one VALU instruction: the lane select goes
+				 * through m0, which compiler-generated gfx950 code does not use here (tests/test_isa_invariants.py) */
+				if (OFFSETS)
+					asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(cpv) : "s"(bit), "s"(k) : "m0");
+				code = (uint32_t)ww.peek64(bit) & 31u;
+				len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
+				fixed = len < SLOW;
+				bit += 5 + (fixed ? len : 0u);
+				k++;
+			} while (fixed & (bit <= safe) & (k < n));
+			if (!fixed) {
+				if (TERN && len == TERN_CHECK) {
+					const uint32_t groups = code == 29u ? (rows + 1u) / 2u : (rows + 2u) / 3u;
+					const uint32_t nbits = column_bits(code, rows);         /* the last group is whole */
+					if (bit + nbits > safe || !tern_column_valid(ww, bit, code, groups))
+						return false;
+					bit += nbits;
+				} else if (len == K_WALK) {
+					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
+					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
+				} else {
+					return false;
+				}
+			}
+			if (bit > safe)                                 /* the column must end inside `safe` */
+				return false;
+			if (k >= n)
+				return true;
+		}
+	}
+};
+
 constexpr int WAVE_SCAN_WAVES = 4;      /* streams per workgroup: one per SIMD of the CU */
 
+/* One stream per wavefront, whole or in block ranges: the walk core with column offsets, 64 columns per call; this kernel's own are
+ * the ranges, the striped upload, the block offsets and the byte-plane places. */
 __global__ void __launch_bounds__(64 * WAVE_SCAN_WAVES)
 acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const uint8_t *__restrict__ files,
 		    uint32_t *__restrict__ colpos, acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ res,
@@ -423,13 +534,8 @@ acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const 
 	 * stream whose range reaches beyond them stops as if its data had run out, and the host reader takes it */
 	const uint32_t safe = 8u * (stripes_up && stripes_up < nranges ? min(job.file_len, acm_stripe_bound(job.file_len, stripes_up, nranges))
 								      : job.file_len);
-	/* per-lane tables, looked up with v_readlane: lane = filler code */
-	const uint32_t code_len = column_bits(lane & 31u, rows);
-	const uint32_t code_tab = k_table_for(lane & 31u);
-	WaveWindow ww;
-	ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
-	ww.maxdw = (job.file_len + 15u) / 4u;
-	ww.lane = lane;
+	WaveWalk<true, false> wk;
+	wk.setup(job, files, lane);
 	/* block range `range` of `nranges` (1 of 1: the whole stream): a later range resumes where the one before stopped */
 	const uint32_t b_lo = acm_range_bound(job.blocks, range, nranges, job.range_unit), b_hi = acm_range_bound(job.blocks, range + 1u, nranges, job.range_unit);
 	uint32_t bit = job.data_start * 8u;
@@ -466,45 +572,19 @@ acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const 
 		mf_at = prev.mf_at;
 	}
 	const uint32_t mf_at_lo = mf_at;                /* where this range's first block would be staged */
-	ww.load(bit >> 5);
+	wk.ww.load(bit >> 5);
 	uint32_t done = b_lo, status = 1;
 	uint32_t *cp = colpos + job.col_off + (uint64_t)b_lo * cols;
 	for (uint32_t b = b_lo; b < b_hi; b++) {
 		if (bit + 20 > safe)
 			goto out;
-		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
-		bit += 20;
+		const uint32_t h20 = wk.header(bit);
 		for (uint32_t c0 = 0; c0 < cols; c0 += 64) {
 			const uint32_t n = __builtin_amdgcn_readfirstlane(min(64u, cols - c0));
-			uint32_t cpv = 0, k = 0;
-			for (;;) {
-				/* the fast loop: fixed-length columns, one exit; why it ended is sorted out behind it.  A column
-				 * that starts in the last 5 bits of the file ends behind it: one bounds check, at the end. */
-				uint32_t code, len;
-				bool fixed;
-				do {
-					/* cpv[lane k] = bit.  Two scalar operands do not fit one VALU instruction: the lane select goes
-					 * through m0, which compiler-generated gfx950 code does not use here (tests/test_isa_invariants.py) */
-					asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(cpv) : "s"(bit), "s"(k) : "m0");
-					code = (uint32_t)ww.peek64(bit) & 31u;
-					len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
-					fixed = len < K_WALK;
-					bit += 5 + (fixed ? len : 0u);
-					k++;
-				} while (fixed & (bit <= safe) & (k < n));
-				if (!fixed) {
-					if (len != K_WALK)
-						goto out;
-					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
-					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
-				}
-				if (bit > safe)                                 /* the column must end inside the file */
-					goto out;
-				if (k >= n)
-					break;
-			}
+			if (!wk.columns(bit, n, safe))
+				goto out;
 			if (lane < n)
-				cp[c0 + lane] = cpv;
+				cp[c0 + lane] = wk.cpv;
 		}
 		{
 			/* blkoff[b]: where the row pair that holds the block's first row lies */
@@ -546,8 +626,8 @@ out:
  *
  * The walk above is sequential per stream only because nobody tells it where blocks start.  With a block index (include/acm_hip.h:
  * acm_index_file) the host knows the first bit of every block, so every (job, block) pair is a walk of its own - cols columns, a few
- * microseconds - and a batch of windows fills the chip however few streams it has.  The wavefront is the same register file as in
- * acm_parse_scan_wave (window, code tables, column offsets through v_writelane), the same fixed-length fast loop and k-column descent.
+ * microseconds - and a batch of windows fills the chip however few streams it has.  The walk core as in acm_parse_scan_wave: with
+ * column offsets, 64 columns per call.
  * The index is not trusted: the block's header must read what its mark says and the walk must end exactly at the next mark, or the job
  * is flagged and the host stages it again.  `safe` is the block's own end: a walk cannot leave its block, let alone its span.
  */
@@ -562,57 +642,27 @@ acm_parse_scan_blocks(const AcmParseJob *__restrict__ jobs, const AcmBlockJob *_
 	const uint32_t lane = threadIdx.x & 63u;
 	const AcmBlockJob me = bjobs[no];
 	const AcmParseJob job = jobs[me.job];
-	const uint32_t rows = job.rows, cols = 1u << job.level;
+	const uint32_t cols = 1u << job.level;
 	const uint32_t safe = min(me.end_bit, job.file_len * 8u);
-	const uint32_t code_len = column_bits(lane & 31u, rows);
-	const uint32_t code_tab = k_table_for(lane & 31u);
-	WaveWindow ww;
-	ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
-	ww.maxdw = (job.file_len + 15u) / 4u;
-	ww.lane = lane;
+	WaveWalk<true, false> wk;
+	wk.setup(job, files, lane);
 	uint32_t bit = me.bit;
 	uint32_t *cp = colpos + job.col_off + (uint64_t)me.block * cols;
 	bool ok = false;
 	if (me.block < job.blocks && bit + 20 <= safe) {
-		ww.load(bit >> 5);
-		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
-		bit += 20;
-		if (h20 != me.h20)
-			goto out;
-		for (uint32_t c0 = 0; c0 < cols; c0 += 64) {
+		wk.ww.load(bit >> 5);
+		const uint32_t h20 = wk.header(bit);
+		ok = h20 == me.h20;
+		for (uint32_t c0 = 0; ok && c0 < cols; c0 += 64) {
 			const uint32_t n = __builtin_amdgcn_readfirstlane(min(64u, cols - c0));
-			uint32_t cpv = 0, k = 0;
-			for (;;) {
-				uint32_t code, len;
-				bool fixed;
-				do {
-					/* cpv[lane k] = bit: the lane select goes through m0 (see acm_parse_scan_wave) */
-					asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(cpv) : "s"(bit), "s"(k) : "m0");
-					code = (uint32_t)ww.peek64(bit) & 31u;
-					len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
-					fixed = len < K_WALK;
-					bit += 5 + (fixed ? len : 0u);
-					k++;
-				} while (fixed & (bit <= safe) & (k < n));
-				if (!fixed) {
-					if (len != K_WALK)
-						goto out;
-					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
-					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
-				}
-				if (bit > safe)                                 /* the column must end inside the block */
-					goto out;
-				if (k >= n)
-					break;
-			}
-			if (lane < n)
-				cp[c0 + lane] = cpv;
+			ok = wk.columns(bit, n, safe);
+			if (ok && lane < n)
+				cp[c0 + lane] = wk.cpv;
 		}
-		ok = bit == me.end_bit;
+		ok = ok && bit == me.end_bit;
 		if (ok && lane == 0)
 			hdr[job.hdr_off + me.block] = acmhip_blkhdr{ h20 >> 4, h20 & 15u };
 	}
-out:
 	/* (vector atomics from one lane: the job's record is shared by the wavefronts of its blocks) */
 	if (lane == 0) {
 		if (ok)
@@ -623,44 +673,14 @@ out:
 }
 
 /*
- * The block index of a stream: the walk of acm_parse_scan_wave with nothing per column.
+ * The block index of a stream: the walk core with nothing per column, and with TERN.
  *
  * An index (include/acm_hip.h: acm_block_mark) needs where every block starts and its (val, pwr) header - both fall out of the walk, so
- * a batch of files is indexed at the walk's rate without decoding a value: same register file (window, code tables through
- * v_readlane), same fixed-length fast loop and k-column descent, no column offsets, no block offsets, no pair table.  One 16-byte
- * mark per block leaves through lane 0's vector store, as the block header does there.
- * What the walk above leaves to the column kernel has to happen here: a ternary column (codes 19, 22, 29) is skipped by its length,
- * but the host reader ends the stream on a symbol out of range inside it (decode.c:412, :438, :464).  Such codes get a sentinel of
- * their own in the length table - the fast loop keeps its single exit - and the whole wavefront validates the column: lane g takes
- * groups g, g + 64, ...; a ballot decides.  A bad symbol flags the stream like data running out or an invalid code does, and the
- * exact host reader indexes it (acm_batch_index.cpp).
+ * a batch of files is indexed at the walk's rate without decoding a value: no column offsets - hence one call per block, all its
+ * columns -, no block offsets, no pair table.  One 16-byte mark per block leaves through lane 0's vector store, as the block header
+ * does in acm_parse_scan_wave.  There is no column kernel behind this walk, so it looks into the ternary columns itself: a bad symbol
+ * flags the stream like data running out or an invalid code does, and the exact host reader indexes it (acm_batch_index.cpp).
  */
-constexpr uint32_t TERN_CHECK = 0xFFFFFFFDu;    /* code_len of a ternary filler here: fixed length, but look inside */
-
-/* are all `groups` symbols of the ternary column whose payload starts at `bit` in range?  The column ends inside the file (the caller
- * checked).  A group is read out of the window where the window holds it (two ds_bpermute); a column may be longer than the window -
- * 4095 rows of code 22 are 9555 bits - and a lane whose group lies behind it fetches its own two dwords. */
-__device__ __forceinline__ bool tern_column_valid(WaveWindow &ww, const uint32_t bit, const uint32_t code, const uint32_t groups)
-{
-	const uint32_t width = code == 19u ? 5u : 7u, lim = code == 19u ? 27u : code == 22u ? 125u : 121u;
-	(void)ww.at(bit);
-	bool bad = false;
-	for (uint32_t g0 = 0; g0 < groups; g0 += 64u) {         /* (wave-uniform trip count: every lane takes part in the permutes) */
-		const uint32_t g = g0 + ww.lane;
-		const uint32_t pos = bit + min(g, groups - 1u) * width;
-		const uint32_t dw = pos >> 5, r = dw - ww.base;
-		uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.lo);
-		uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((r & 63u) << 2), (int)ww.hi);
-		if (r > 63u) {
-			a = __builtin_nontemporal_load(ww.w + min(dw, ww.maxdw));
-			b = __builtin_nontemporal_load(ww.w + min(dw + 1u, ww.maxdw));
-		}
-		const uint32_t v = (uint32_t)((((uint64_t)b << 32) | a) >> (pos & 31u)) & ((1u << width) - 1u);
-		bad |= g < groups && v >= lim;
-	}
-	return __builtin_amdgcn_ballot_w64(bad) == 0;
-}
-
 __global__ void __launch_bounds__(64 * WAVE_SCAN_WAVES)
 acm_index_scan_wave(const AcmParseJob *__restrict__ jobs, const uint32_t njobs, const uint8_t *__restrict__ files,
 		    acm_block_mark *__restrict__ marks, AcmParseResult *__restrict__ res)
@@ -670,64 +690,30 @@ acm_index_scan_wave(const AcmParseJob *__restrict__ jobs, const uint32_t njobs, 
 		return;
 	const uint32_t lane = threadIdx.x & 63u;
 	const AcmParseJob job = jobs[jobno];
-	const uint32_t rows = job.rows, cols = 1u << job.level;
+	const uint32_t cols = 1u << job.level;
 	const uint32_t safe = 8u * job.file_len;
-	/* per-lane tables, looked up with v_readlane: lane = filler code */
-	const uint32_t code_len = code_class(lane & 31u) == CLS_TERN ? TERN_CHECK : column_bits(lane & 31u, rows);
-	const uint32_t code_tab = k_table_for(lane & 31u);
-	WaveWindow ww;
-	ww.w = reinterpret_cast<const uint32_t *>(files + job.file_off);
-	ww.maxdw = (job.file_len + 15u) / 4u;
-	ww.lane = lane;
+	WaveWalk<false, true> wk;
+	wk.setup(job, files, lane);
 	uint32_t bit = job.data_start * 8u;
-	ww.load(bit >> 5);
+	wk.ww.load(bit >> 5);
 	/* a mark as one 16-byte store: bit (files are < 256 MiB: the high word is zero), val, pwr */
 	uint4 *const mk = reinterpret_cast<uint4 *>(marks + job.hdr_off);
 	uint32_t done = 0, status = 1;
-	for (uint32_t b = 0; b < job.blocks; b++) {
+	for (; done < job.blocks; done++) {
 		if (bit + 20 > safe)
-			goto out;
+			break;
 		const uint32_t at = bit;
-		const uint32_t h20 = (uint32_t)ww.peek64(bit) & 0xFFFFFu;
-		bit += 20;
-		for (uint32_t k = 0;;) {
-			/* the fast loop of acm_parse_scan_wave: fixed-length columns whose inside does not matter, one exit */
-			uint32_t code, len;
-			bool fixed;
-			do {
-				code = (uint32_t)ww.peek64(bit) & 31u;
-				len = (uint32_t)__builtin_amdgcn_readlane((int)code_len, (int)code);
-				fixed = len < TERN_CHECK;
-				bit += 5 + (fixed ? len : 0u);
-				k++;
-			} while (fixed & (bit <= safe) & (k < cols));
-			if (!fixed) {
-				if (len == TERN_CHECK) {
-					const uint32_t groups = code == 29u ? (rows + 1u) / 2u : (rows + 2u) / 3u;
-					const uint32_t nbits = column_bits(code, rows);         /* the last group is whole */
-					if (bit + nbits > safe || !tern_column_valid(ww, bit, code, groups))
-						goto out;
-					bit += nbits;
-				} else if (len == K_WALK) {
-					const uint32_t tab = (uint32_t)__builtin_amdgcn_readlane((int)code_tab, (int)code);
-					bit = rows <= 16 ? walk_k_column<4>(ww, bit, tab, rows, safe) : walk_k_column<5>(ww, bit, tab, rows, safe);
-				} else {
-					goto out;
-				}
-			}
-			if (bit > safe)                                 /* the column must end inside the file */
-				goto out;
-			if (k >= cols)
-				break;
-		}
+		const uint32_t h20 = wk.header(bit);
+		if (!wk.columns(bit, cols, safe))
+			break;
 		if (lane == 0)
-			mk[b] = make_uint4(at, 0u, h20 >> 4, h20 & 15u);
-		done++;
+			mk[done] = make_uint4(at, 0u, h20 >> 4, h20 & 15u);
 	}
-	status = 0;
-	if (lane == 0)
-		mk[done] = make_uint4(bit, 0u, 0u, 0u);         /* the entry behind the last block: where it ends */
-out:
+	if (done == job.blocks) {
+		status = 0;
+		if (lane == 0)
+			mk[done] = make_uint4(bit, 0u, 0u, 0u);         /* the entry behind the last block: where it ends */
+	}
 	if (lane == 0)
 		res[jobno] = AcmParseResult{ done, status, bit, 0u };
 }
@@ -1036,6 +1022,22 @@ extern "C" int acmk_launch_scatter_stripe(const AcmParseJob *d_jobs, uint32_t nj
 	return 0;
 }
 
+/* the column kernel behind a walk: `gx` workgroups per stream as the caller sized them, clamped to [1, 2048] (the kernel strides over
+ * the grid), the streams along the grid's y in slices of 65535 */
+static int launch_columns(uint64_t gx, const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, const uint32_t *d_colpos, int16_t *d_idx,
+			  const acmhip_blkhdr *d_hdr, const AcmParseResult *d_res, uint32_t *d_flags, uint32_t range, uint32_t nranges, uint8_t *d_mf,
+			  uint32_t *d_pairs, const uint32_t *d_blkoff, hipStream_t st)
+{
+	gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
+	for (uint32_t at = 0; at < njobs; at += 65535) {
+		const uint32_t n = njobs - at < 65535 ? njobs - at : 65535;
+		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
+				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, range, nranges, d_mf, d_pairs, d_blkoff);
+		ACMP_CHECK();
+	}
+	return 0;
+}
+
 extern "C" int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 				       uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
 				       AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t range, uint32_t nranges,
@@ -1090,19 +1092,9 @@ extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t nj
 	ACMP_CHECK();
 	/* a block range of the longest stream: its share of the blocks, rounded up, + one for where the cut falls */
 	const uint64_t range_columns = max_columns / nranges + 32768;           /* (the kernel strides over the grid: a bound, not a contract) */
-	uint64_t gx = ((range_columns < max_columns ? range_columns : max_columns) + COL_THREADS - 1) / COL_THREADS;
-	if (gx < 1)
-		gx = 1;
-	if (gx > 2048)
-		gx = 2048;
-	for (uint32_t at = 0; at < njobs; at += 65535) {
-		const uint32_t n = njobs - at < 65535 ? njobs - at : 65535;
-		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
-				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, range, nranges, mf ? d_mf : nullptr,
-				   mf ? d_pairs : nullptr, mf ? d_blkoff : nullptr);
-		ACMP_CHECK();
-	}
-	return 0;
+	const uint64_t gx = ((range_columns < max_columns ? range_columns : max_columns) + COL_THREADS - 1) / COL_THREADS;
+	return launch_columns(gx, d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, range, nranges, mf ? d_mf : nullptr,
+			      mf ? d_pairs : nullptr, mf ? d_blkoff : nullptr, st);
 }
 
 extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock,
@@ -1115,15 +1107,8 @@ extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njob
 	hipLaunchKernelGGL(acm_parse_scan_blocks, dim3((nblock + WAVE_SCAN_WAVES - 1) / WAVE_SCAN_WAVES), dim3(64 * WAVE_SCAN_WAVES), 0, st,
 			   d_jobs, d_bjobs, nblock, d_files, d_colpos, d_hdr, d_res);
 	ACMP_CHECK();
-	uint64_t gx = (max_columns + COL_THREADS - 1) / COL_THREADS;
-	gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
-	for (uint32_t at = 0; at < njobs; at += 65535) {
-		const uint32_t n = njobs - at < 65535 ? njobs - at : 65535;
-		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
-				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, 0u, 1u, nullptr, nullptr, nullptr);
-		ACMP_CHECK();
-	}
-	return 0;
+	const uint64_t gx = (max_columns + COL_THREADS - 1) / COL_THREADS;
+	return launch_columns(gx, d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, 0u, 1u, nullptr, nullptr, nullptr, st);
 }
 
 extern "C" int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, acm_block_mark *d_marks, AcmParseResult *d_res,

@@ -27,7 +27,7 @@ class Src:
         rc, _ = capi.probe(data, force_chans)
         self.st = capi.stage_file(data, force_chans) if rc == 0 else None
         self.rc = rc
-        self.marks = capi.index_file(data, force_chans)[0] if rc == 0 else None
+        self.marks, self.ix = capi.index_file(data, force_chans) if rc == 0 else (None, None)
         self._pcm = {}
 
     def pcm(self, fmt=capi.FMT_S16LE, force_chans=0):
@@ -196,6 +196,45 @@ def test_h1_streams(dev):
     got, st, words, slots, tm = run(dev, srcs, windows, capi.PARSE_DEVICE)
     assert tm.host_parsed > 0 and tm.device_parsed > 0
     assert tm.device_parsed + tm.host_parsed == sum(1 for w in words if w)
+
+
+SINGLE_CODES = (17, 18, 20, 21, 23, 24, 26, 27) + (19, 22, 29)         # the eight k-fillers, the three ternary ones
+SINGLE_ROWS = (1, 2, 15, 16, 17, 31, 40, 255)                           # around the 16-row switch of the jump table, one row, tall columns
+SINGLE_LEVELS = (3, 5, 6, 7)                                            # 8, 32, 64, 128 columns: below, at and above one wavefront's 64 offsets
+
+
+def single_filler_sources():
+    """(srcs, windows): three-block streams of ONE filler each, every one whole and clean for the host reader (asserted here, without
+    a device); per stream the whole file and a window that starts inside the last block"""
+    from libacm_amd import synth
+    srcs, windows = [], []
+    for code in SINGLE_CODES:
+        for rows in SINGLE_ROWS:
+            for level in SINGLE_LEVELS:
+                f = len(srcs)
+                s = Src(synth.generate(seed=synth.BASE_SEED + 8900 + f, level=level, rows=rows, nblocks=3, mix=synth.MIX_SINGLE,
+                                       single_code=code, pwr_min=12, pwr_max=12))
+                srcs.append(s)
+                W, bl = s.st.words, s.st.block_len
+                # whole, indexed to its end by the host, no index outside its block's range (H1): nothing sends it back to the host reader
+                assert (s.ix.blocks, s.ix.end_status, s.marks.size) == (3, 0, 4), (code, rows, level)
+                assert (s.st.info.blocks, s.st.info.end_status, s.st.info.npatches) == (3, 0, 0) and W == 3 * bl, (code, rows, level)
+                assert (s.st.info.cols, bl) == (1 << level, rows << level), (code, rows, level)
+                windows += [(f, 0, W), (f, 2 * bl + bl // 2, W - 2 * bl - bl // 2)]
+    return srcs, windows
+
+
+def test_block_walk_single_fillers(dev):
+    """the block-per-wavefront walk (acm_parse.hip: acm_parse_scan_blocks) on streams that hold ONE filler each - the counterpart of
+    test_gpu_parity.py::test_device_walk_k_columns, which reaches the stream-per-wavefront kernel only: every k code and every ternary
+    code x rows around the 16-row switch of the jump table, one row, tall columns that need several 64-bit windows x columns per block
+    below / at / above one wavefront's 64 offsets.  The streams are clean (single_filler_sources), so the device must
+    walk every window itself: a fall-back to the host reader would hide a broken walk"""
+    srcs, windows = single_filler_sources()
+    for parse in BOTH:
+        got, st, words, slots, tm = run(dev, srcs, windows, parse)
+        assert not any(st) and tm.device_parsed + tm.host_parsed == len(windows)
+        assert (tm.host_parsed == 0) == (parse == capi.PARSE_DEVICE) and (tm.device_parsed == 0) == (parse == capi.PARSE_HOST)
 
 
 def test_truncated_and_foreign_files(dev):

@@ -152,40 +152,45 @@ def test_every_wait_is_written_by_hand(kernel_asm):
 
 
 def test_parse_walk_owns_m0(tmp_path):
-    """acm_parse_scan_wave routes a v_writelane lane select through m0 by hand (acm_parse.hip); nothing the compiler
-    generated in that kernel may touch m0, and the kernel must stay free of scratch"""
+    """the walk core of acm_parse.hip (WaveWalk) routes a v_writelane lane select through m0 by hand where it collects column
+    offsets - acm_parse_scan_wave, acm_parse_scan_blocks -: nothing the compiler generated in those kernels may touch m0; the index
+    walk collects nothing and must not name m0 at all; and all three must stay free of scratch"""
     out = tmp_path / "acm_parse.s"
     cmd = [_build.HIPCC, "-O3", "-std=c++17", "--offload-arch=" + _build.GFX, "-I", _build.INC, "-I", _build.CSRC,
            "--cuda-device-only", "-S", "-o", str(out), os.path.join(_build.CSRC, "acm_parse.hip")]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-2000:]
     asm = out.read_text()
-    m = re.search(r"^(_ZN\S*acm_parse_scan_wave\S*):", asm, re.M)
-    assert m
-    body = asm[m.end():asm.index(".Lfunc_end", m.end())].split("\n")
-    by_hand, mine, writes = False, 0, 0
-    for l in body:
-        t = l.strip()
-        if t.startswith(";;#ASMSTART"):
-            by_hand = True
-        elif t.startswith(";;#ASMEND"):
-            by_hand = False
-        elif t and not t.startswith(";"):
-            code = t.split(";")[0]
-            if by_hand:
-                mine += "m0" in code
-                writes += code.startswith("v_writelane_b32")
-            else:
-                assert not re.search(r"\bm0\b", code), t
-                assert not t.startswith("scratch_"), t
-    assert writes >= 1 and mine == 2 * writes
+    for kernel, collects in (("acm_parse_scan_wave", True), ("acm_parse_scan_blocks", True), ("acm_index_scan_wave", False)):
+        m = re.search(r"^(_ZN\S*" + kernel + r"\S*):", asm, re.M)
+        assert m, kernel
+        body = asm[m.end():asm.index(".Lfunc_end", m.end())].split("\n")
+        by_hand, mine, writes = False, 0, 0
+        for l in body:
+            t = l.strip()
+            if t.startswith(";;#ASMSTART"):
+                by_hand = True
+            elif t.startswith(";;#ASMEND"):
+                by_hand = False
+            elif t and not t.startswith(";"):
+                code = t.split(";")[0]
+                if by_hand:
+                    mine += "m0" in code
+                    writes += code.startswith("v_writelane_b32")
+                else:
+                    assert not re.search(r"\bm0\b", code), (kernel, t)
+                    assert not t.startswith("scratch_"), (kernel, t)
+        if collects:
+            assert writes >= 1 and mine == 2 * writes, (kernel, writes, mine)
+        else:
+            assert (writes, mine) == (0, 0), (kernel, writes, mine)
     # ... and so must the column kernel: its row loop exists twice (plain blocks / blocks whose first or last row pair has another class);
     # written as a generic lambda the two copies kept their captures in scratch memory and the kernel ran 8 x slower (profiles/r6_level9_notes.txt 17)
     m = re.search(r"^(_ZN\S*acm_parse_columns\S*):", asm, re.M)
     assert m
     cols = asm[m.end():asm.index(".Lfunc_end", m.end())]
     assert "scratch_" not in cols and cols.count("global_store_byte") >= 4
-    for kernel in ("acm_parse_columns", "acm_parse_scan_wave"):
+    for kernel in ("acm_parse_columns", "acm_parse_scan_wave", "acm_parse_scan_blocks", "acm_index_scan_wave"):
         md = re.search(r"\.amdhsa_kernel \S*" + kernel + r"\S*\n(?:.*\n)*?\s*\.amdhsa_private_segment_fixed_size (\d+)", asm)
         assert md and md.group(1) == "0", kernel
 
