@@ -662,6 +662,30 @@ uint64_t acm_batch_index_blocks(const acm_batch_item *items, size_t n, int force
 int  acm_batch_index_files(acmhip_device *dev, const acm_batch_item *items, size_t n, acm_batch_index_out *out,
 			   const acm_index_opts *opts, acm_index_timing *timing);
 
+/* ------------------------------------------------------------------------
+ * The block index as a by-product of a whole decode (csrc/acm_batch.cpp): whoever bit-parses a stream for acm_batch_decode stands
+ * on the first bit of every block and reads its (val, pwr), so a data set that is decoded whole once has paid for its index.
+ *
+ * acm_batch_decode_indexed with index == NULL is acm_batch_decode.  With n entries of index, items, PCM, offsets, statuses and
+ * *timing are exactly what acm_batch_decode gives for the same arguments, and for every item index[i].marks[0 .. blocks], blocks,
+ * end_status and status are byte for byte what acm_index_file(data, len, force_chans, marks, B_i, &info) writes and returns, B_i
+ * being the item's per_item value of acm_batch_index_blocks() - the blocks the decode stages.  marks behind blocks + 1 entries are
+ * not written; a file that is not ACM leaves its marks untouched.  index[i].marks == NULL or index[i].max_blocks < B_i for an item
+ * that is ACM: ACMHIP_ERR_ARG before anything is written.
+ *
+ * Nobody parses a stream for the index who would not have parsed it anyway (timing->device_parsed / host_parsed are those of
+ * acm_batch_decode): the device walk (acm_parse_scan_wave whole or in block ranges, acm_parse_scan beyond 32768 streams) stores a
+ * 16-byte mark beside every block header it stores - 16 bytes of device memory per block, read back once behind the last walk -,
+ * the host pool's stagers and the redo of a stream the device flagged write the caller's marks where they begin a block, and a
+ * prestaged batch hands over the marks acm_batch_prestage kept.
+ * ---------------------------------------------------------------------- */
+int  acm_batch_decode_indexed(acmhip_device *dev, acm_batch_item *items, size_t n, const acm_batch_opts *opts,
+			      acm_batch_index_out *index /* n entries, or NULL */, acm_batch_timing *timing);
+/* The index of item i of a prestaged batch, no device: *marks (blocks + 1 entries inside p, valid until acm_batch_prestage_free; NULL
+ * for a file that is not ACM), *blocks and *end_status as acm_index_file gives them for the item's acm_batch_index_blocks() blocks.
+ * Returns the item's acm_index_file code, or ACMHIP_ERR_ARG for an i that p does not have. */
+int  acm_batch_prestaged_index(const acm_batch_prestaged *p, size_t i, const acm_block_mark **marks, uint32_t *blocks, int32_t *end_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,7 +77,8 @@ def pcm_capacity_words(head, file_len, force_chans=0):
 
 def build_index(files, threads=0, decoder=None):
     """The block index of every file (capi.index_file: start bit, val and pwr of each block - 16 bytes per block), built once on the
-    host and kept: GpuDecoder.crop() takes it back on every call.  files: paths or file images.  Returns a list of numpy record arrays
+    host and kept: GpuDecoder.crop() takes it back on every call.  (Files that are decoded whole anyway need no pass of their own:
+    GpuDecoder.__call__(files, return_index=True) hands the same index out beside the PCM.)  files: paths or file images.  Returns a list of numpy record arrays
     (capi.BlockIndex: capi.BLOCK_MARK_DT records that also remember how the stream ends; np.save / np.load keep the records), an empty
     one for a file that is not ACM.  threads: 0 = one per CPU, at most 64.
     decoder: a GpuDecoder - the index is built through its device handle (GpuDecoder.build_index: the device walks the clean streams
@@ -128,9 +129,11 @@ class GpuDecoder:
         """a PCM buffer this decoder can decode into (decode_sharded keeps two of them per rank and reuses them)"""
         return self.torch.empty(max(words, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
 
-    def __call__(self, files, out=None):
+    def __call__(self, files, out=None, return_index=False):
         """-> (pcm tensor in HBM - int16, or float32 -, per-file sample offsets into it, per-file sample counts, per-file statuses).
-        out: a tensor of this decoder's dtype of at least acm_batch_pcm_words(files) samples to decode into (else a new one is allocated)"""
+        out: a tensor of this decoder's dtype of at least acm_batch_pcm_words(files) samples to decode into (else a new one is allocated).
+        return_index=True: a fifth element, the block index of every file as build_index(files) returns it - a by-product of this
+        decode's own parse (acm_batch_decode_indexed: no stream is walked a second time), ready for crop()"""
         torch = self.torch
         cap = capi.batch_pcm_words(files)
         if out is not None and out.dtype != self.dtype:
@@ -141,10 +144,11 @@ class GpuDecoder:
         # one call: threaded (or device-side) bit parsing, pipelined H2D, synthesis; the PCM stays in d_pcm.  In steady state
         # nothing in it allocates or frees device memory (grow-only arenas, plan tables from the handle's spare blocks), so a
         # transfer of the previous chunk that is still in flight is not waited for
-        statuses, words, offsets, self.timing = capi.batch_decode_device(
-            self.dev, files, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
+        res = capi.batch_decode_device(
+            self.dev, files, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, index=return_index)
+        statuses, words, offsets, self.timing = res[:4]
         # acm_batch_decode returns with its stream drained: d_pcm is complete and visible to torch's streams
-        return d_pcm, offsets, words, statuses
+        return (d_pcm, offsets, words, statuses) + tuple(res[4:])
 
 
     def build_index(self, files, threads=0, parse=None, max_group_bytes=0):

@@ -156,7 +156,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows",
-    "acm_batch_index_blocks", "acm_batch_index_files",
+    "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -251,6 +251,8 @@ def lib():
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
+    L.acm_batch_decode_indexed.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchOpts), C.POINTER(BatchIndexOut), C.POINTER(BatchTiming)]
+    L.acm_batch_prestaged_index.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -787,9 +789,38 @@ BATCH_STAGE_INT16 = 8
 BATCH_PCM_F32 = 16
 
 
+class _IndexOut:
+    """the marks acm_batch_decode_indexed fills for these items: one allocation, acm_batch_index_blocks() + 1 entries per item"""
+
+    def __init__(self, items, n, force_chans):
+        need = np.zeros(max(n, 1), dtype=np.uint64)
+        lib().acm_batch_index_blocks(items, n, force_chans, need.ctypes.data)
+        self.n = n
+        self.at = np.zeros(n + 1, dtype=np.int64)
+        self.at[1:] = np.cumsum(need[:n].astype(np.int64) + 1)
+        self.marks = np.zeros(int(self.at[n]), dtype=BLOCK_MARK_DT)
+        self.out = (BatchIndexOut * max(n, 1))()
+        for k in range(n):
+            self.out[k].marks = self.marks.ctypes.data + int(self.at[k]) * BLOCK_MARK_DT.itemsize
+            self.out[k].max_blocks = int(need[k])
+
+    def result(self):
+        """what batch.build_index returns: a BlockIndex per item, an empty one for a file that is not ACM"""
+        res = []
+        for k in range(self.n):
+            o, at = self.out[k], int(self.at[k])
+            if o.status != 0:
+                res.append(as_index(np.zeros(0, dtype=BLOCK_MARK_DT), None))
+            else:
+                res.append(as_index(self.marks[at:at + o.blocks + 1].copy(), o.end_status))
+        return res
+
+
 def batch_decode(dev, files, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, pinned=False, prestage=False,
-                 packed=False, byteplane=None):
+                 packed=False, byteplane=None, index=False, batch_flags=0):
     """acm_batch_decode over a list of bytes objects -> (list of (status, uint16 array), BatchTiming).
+    index=True: acm_batch_decode_indexed - the block index of every file, a by-product of the decode's own parse, as a further, last
+    element in the form batch.build_index returns.  batch_flags: further ACM_BATCH_* bits (block ranges).
 
     pinned=True: the output buffers are carved from one pinned arena (acmhip_host_alloc) and the call is told so
     (ACM_BATCH_PCM_PINNED: the read-back engine writes them directly); the arrays returned are copies.
@@ -823,15 +854,19 @@ def batch_decode(dev, files, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN
         items[k].len = bufs[k].size
         items[k].pcm = outs[k].ctypes.data if outs[k].size else None
         items[k].pcm_cap = outs[k].size
-    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | (BATCH_PCM_PINNED if pinned else 0) | (BATCH_STAGE_PACKED if packed else 0) |
-                     (BATCH_STAGE_BYTEPLANE if byteplane else 0) | (BATCH_STAGE_INT16 if byteplane is False else 0))
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | batch_flags | (BATCH_PCM_PINNED if pinned else 0) |
+                     (BATCH_STAGE_PACKED if packed else 0) | (BATCH_STAGE_BYTEPLANE if byteplane else 0) | (BATCH_STAGE_INT16 if byteplane is False else 0))
     tm = BatchTiming()
     pre = C.c_void_p()
+    ix = _IndexOut(items, n, force_chans) if index else None
     try:
         if prestage:
             _check(lib().acm_batch_prestage(items, n, C.byref(opts), C.byref(pre), None), "acm_batch_prestage")
             opts.prestaged = pre
-        _check(lib().acm_batch_decode(dev.h, items, n, C.byref(opts), C.byref(tm)), "acm_batch_decode")
+        if ix is not None:
+            _check(lib().acm_batch_decode_indexed(dev.h, items, n, C.byref(opts), ix.out, C.byref(tm)), "acm_batch_decode_indexed")
+        else:
+            _check(lib().acm_batch_decode(dev.h, items, n, C.byref(opts), C.byref(tm)), "acm_batch_decode")
         res = [(items[k].status, outs[k][:items[k].words].copy() if pinned else outs[k][:items[k].words]) for k in range(n)]
     finally:
         if pre:
@@ -839,7 +874,7 @@ def batch_decode(dev, files, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN
         if pinned:
             del outs, whole
             lib().acmhip_host_free(arena)
-    return res, tm
+    return (res, tm, ix.result()) if ix is not None else (res, tm)
 
 
 def _batch_items(files):
@@ -858,20 +893,26 @@ def batch_pcm_words(files, force_chans=0):
 
 
 def batch_decode_device(dev, files, d_pcm, d_pcm_words, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO,
-                        parse=PARSE_AUTO, f32=False, batch_flags=0):
+                        parse=PARSE_AUTO, f32=False, batch_flags=0, index=False):
     """acm_batch_decode with device-resident output: PCM of stream k lands at d_pcm + 2*offsets[k] bytes.
     f32=True: ACM_BATCH_PCM_F32 - float32 samples at d_pcm + 4*offsets[k] bytes (d_pcm_words counts floats then).
     batch_flags: further ACM_BATCH_* bits (staging, block ranges).
 
-    Returns (statuses, words, offsets, BatchTiming); nothing is copied back to the host."""
+    Returns (statuses, words, offsets, BatchTiming); nothing is copied back to the host.  index=True: acm_batch_decode_indexed - the block
+    index of every file, in the form batch.build_index returns, as a further, last element."""
     bufs, items = _batch_items(files)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | batch_flags | (BATCH_PCM_F32 if f32 else 0),
                      d_pcm, d_pcm_words)
     tm = BatchTiming()
-    _check(lib().acm_batch_decode(dev.h, items, len(files), C.byref(opts), C.byref(tm)), "acm_batch_decode")
     n = len(files)
-    return ([int(items[k].status) for k in range(n)], [int(items[k].words) for k in range(n)],
-            [int(items[k].dev_off) for k in range(n)], tm)
+    ix = _IndexOut(items, n, force_chans) if index else None
+    if ix is not None:
+        _check(lib().acm_batch_decode_indexed(dev.h, items, n, C.byref(opts), ix.out, C.byref(tm)), "acm_batch_decode_indexed")
+    else:
+        _check(lib().acm_batch_decode(dev.h, items, n, C.byref(opts), C.byref(tm)), "acm_batch_decode")
+    res = ([int(items[k].status) for k in range(n)], [int(items[k].words) for k in range(n)],
+           [int(items[k].dev_off) for k in range(n)], tm)
+    return res + (ix.result(),) if ix is not None else res
 
 
 # --------------------------------------------------------------------------- windows through a block index

@@ -29,6 +29,7 @@
 #include "acm_batch_common.h"
 #include "acm_device.h"
 #include "acm_hip.h"
+#include "acm_index.h"
 #include "libacm.h"
 
 namespace {
@@ -71,11 +72,11 @@ struct ParseGroup {
 } // namespace
 
 /* what acm_batch_prestage keeps: per item the header, the status, the staged blocks (one allocation for all items, laid out
- * like the batch's own arenas) and the H1 patches */
+ * like the batch's own arenas), the H1 patches and the block index (need_blocks + 1 marks per item that is ACM) */
 struct acm_batch_prestaged {
 	struct Item {
 		acm_stage_info info{};
-		uint64_t need_blocks = 0, idx_off = 0, hdr_off = 0;
+		uint64_t need_blocks = 0, idx_off = 0, hdr_off = 0, marks_off = 0;
 		std::vector<acmhip_patch> patches;
 		int status = 0;
 		bool ok = false;
@@ -85,6 +86,7 @@ struct acm_batch_prestaged {
 	std::vector<size_t> len;
 	int16_t *idx = nullptr;
 	acmhip_blkhdr *hdr = nullptr;
+	std::vector<acm_block_mark> marks;
 	size_t idx_cap = 0, hdr_cap = 0;        /* bytes */
 	int force_chans = 0;
 };
@@ -177,9 +179,14 @@ extern "C" int acm_batch_prestage(const acm_batch_item *items, size_t n, const a
 		s.ok = s.status == ACM_OK;
 	});
 	Int16Arenas arenas;
+	uint64_t marks_total = 0;
 	for (size_t i = 0; i < n; i++)
-		if (p->items[i].ok)
+		if (p->items[i].ok) {
 			arenas.place(p->items[i].info, items[i].len, &p->items[i].need_blocks, &p->items[i].idx_off, &p->items[i].hdr_off);
+			p->items[i].marks_off = marks_total;
+			marks_total += p->items[i].need_blocks + 1;
+		}
+	p->marks.resize(marks_total);
 	p->idx = static_cast<int16_t *>(g_stage_cache.get(std::max<uint64_t>(arenas.idx_total, 1) * sizeof(int16_t), &p->idx_cap));
 	p->hdr = static_cast<acmhip_blkhdr *>(g_stage_cache.get(std::max<uint64_t>(arenas.hdr_total, 1) * sizeof(acmhip_blkhdr), &p->hdr_cap));
 	if (!p->idx || !p->hdr) {
@@ -191,8 +198,9 @@ extern "C" int acm_batch_prestage(const acm_batch_item *items, size_t n, const a
 		if (!s.ok)
 			return;
 		acm_stage_info info{};
-		/* first pass counts patches (normally zero), second only if there are any */
-		int r = acm_stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks, nullptr, 0, &info);
+		/* first pass counts patches (normally zero) and keeps the marks, second only if there are any */
+		int r = acmindex::stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks, nullptr, 0,
+					     &info, p->marks.data() + s.marks_off);
 		if (r == ACM_OK && info.npatches) {
 			s.patches.resize(info.npatches);
 			r = acm_stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks,
@@ -210,6 +218,17 @@ extern "C" int acm_batch_prestage(const acm_batch_item *items, size_t n, const a
 		*seconds = secs(t0, clk::now());
 	*out = p;
 	return ACMHIP_OK;
+}
+
+extern "C" int acm_batch_prestaged_index(const acm_batch_prestaged *p, size_t i, const acm_block_mark **marks, uint32_t *blocks, int32_t *end_status)
+{
+	if (!p || i >= p->items.size() || !marks || !blocks || !end_status)
+		return ACMHIP_ERR_ARG;
+	const acm_batch_prestaged::Item &s = p->items[i];
+	*marks = s.ok ? p->marks.data() + s.marks_off : nullptr;
+	*blocks = s.ok ? s.info.blocks : 0;
+	*end_status = s.ok ? s.info.end_status : 0;
+	return s.ok ? ACM_OK : s.status;
 }
 
 extern "C" uint64_t acm_batch_pcm_words(const acm_batch_item *items, size_t n, int force_chans)
@@ -239,13 +258,13 @@ bool tracing()
 
 #define BNOTE(...) do { if (trace) { fprintf(stderr, "[batch %8.3f ms] ", secs(t0, clk::now()) * 1e3); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
 
-/* One acm_batch_decode call behind the arena lock: the device-side state of the pipeline over a BatchLayout it only reads.  The stages
+/* One acm_batch_decode / acm_batch_decode_indexed call behind the arena lock: the device-side state of the pipeline over a BatchLayout it only reads.  The stages
  * are called once each, in the order of acm_batch_decode; a stage that fails returns its code and the destructor does the rest. */
 class BatchRun {
 public:
 	BatchRun(acmhip_device *dev_, acm_batch_item *items_, size_t n_, const acm_batch_opts &opts_, const BatchLayout &L_, Pool &pool_,
-		 const std::vector<LayoutItem> &probed, clk::time_point t0_, clk::time_point t_hdr_)
-		: lock(dev_), dev(dev_), items(items_), n(n_), opts(opts_), pre(opts_.prestaged), L(L_), pool(pool_), t0(t0_), t_hdr(t_hdr_),
+		 const std::vector<LayoutItem> &probed, acm_batch_index_out *index_, clk::time_point t0_, clk::time_point t_hdr_)
+		: lock(dev_), dev(dev_), items(items_), n(n_), index(index_), opts(opts_), pre(opts_.prestaged), L(L_), pool(pool_), t0(t0_), t_hdr(t_hdr_),
 		  out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), R(L_.R), nd(L_.dev_ids.size()), nbat((nd + STRIPE_BATCH - 1) / STRIPE_BATCH),
 		  st_main((hipStream_t)acmhip_device_stream(dev_)), slots(n_), chunks(L_.chunks.size()), rchunks(R > 1 ? R : 0),
 		  groups(L_.groups.size()), ev_stripe(R > 1 ? R + 1 : 0, nullptr), stripe_uncopied(R > 1 ? new std::atomic<int>[R] : nullptr),
@@ -294,6 +313,14 @@ private:
 	void host_pack(size_t i);
 	void host_mform(size_t i);
 	void host_stage_int16(size_t i);
+	void index_staged(size_t i, int rc, const acm_stage_info &info)    /* the host reader went over stream i with index[i].marks in hand */
+	{
+		if (!index)
+			return;
+		index[i].status = rc;
+		index[i].blocks = rc == ACM_OK ? info.blocks : 0;
+		index[i].end_status = rc == ACM_OK ? info.end_status : 0;
+	}
 	void host_stage(size_t i)
 	{
 		host_stage_int16(i);
@@ -328,6 +355,7 @@ private:
 	acmhip_device *const dev;
 	acm_batch_item *const items;
 	const size_t n;
+	acm_batch_index_out *const index;       /* null: nobody asked for the block index */
 	const acm_batch_opts &opts;
 	const acm_batch_prestaged *const pre;
 	const BatchLayout &L;
@@ -341,6 +369,7 @@ private:
 	int16_t *h_idx = nullptr, *h_pcm = nullptr, *d_idx = nullptr, *d_pcm = nullptr;
 	uint32_t *d_colpos = nullptr, *d_blkoff = nullptr;
 	acmhip_blkhdr *h_hdr = nullptr, *d_hdr = nullptr;
+	acm_block_mark *h_marks = nullptr, *d_marks = nullptr;  /* the index as a by-product of the device walk: parallel to the header arena */
 	uint8_t *h_files = nullptr, *d_files = nullptr, *h_jobs = nullptr, *d_jobs = nullptr, *d_stage = nullptr;
 	uint8_t *h_pkblob = nullptr, *d_pkblob = nullptr;
 	acmhip_packed_chunk *h_pkchunk = nullptr, *d_pkchunk = nullptr;
@@ -410,6 +439,10 @@ int BatchRun::acquire()
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, L.stripe_tab_off + L.stripe_tab_bytes, (void **)&d_jobs));
 		if (R > 1)
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_STAGE, L.files_total, (void **)&d_stage));
+		if (index) {
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_MARKS, hdr_total * sizeof(acm_block_mark), (void **)&d_marks));
+			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_MARKS, hdr_total * sizeof(acm_block_mark), (void **)&h_marks));
+		}
 	}
 	for (std::vector<Chunk> *v : { &chunks, &rchunks })
 		for (Chunk &ch : *v)
@@ -496,20 +529,26 @@ void BatchRun::host_stage_int16(size_t i)
 	const SlotLayout &p = L.slots[i];
 	acm_batch_item &it = items[i];
 	acm_stage_info info{};
+	acm_block_mark *const marks = index ? index[i].marks : nullptr;        /* filled where the reader begins a block */
 	if (pre) {
-		/* parsed already: the staged blocks only have to move into the upload arenas */
+		/* parsed already: the staged blocks - and their marks - only have to move into the upload arenas */
 		const acm_batch_prestaged::Item &ps = pre->items[i];
 		if (!ps.ok) {
 			it.status = ps.status;
 			s.ok = false;
+			index_staged(i, ps.status, info);
 			return;
 		}
 		const uint64_t bl = (uint64_t)ps.info.rows * ps.info.cols;
 		if (ps.need_blocks != p.need_blocks || ps.info.blocks > p.need_blocks) {      /* cannot happen for the same bytes */
 			it.status = ACM_ERR_OTHER;
 			s.ok = false;
+			index_staged(i, ACM_ERR_OTHER, info);
 			return;
 		}
+		if (marks)
+			memcpy(marks, pre->marks.data() + ps.marks_off, ((size_t)ps.info.blocks + 1) * sizeof(acm_block_mark));
+		index_staged(i, ACM_OK, ps.info);
 		memcpy(h_idx + p.idx_off, pre->idx + ps.idx_off, ps.info.blocks * bl * sizeof(int16_t));
 		memcpy(h_hdr + p.hdr_off, pre->hdr + ps.hdr_off, ps.info.blocks * sizeof(acmhip_blkhdr));
 		s.patches = ps.patches;
@@ -524,22 +563,23 @@ void BatchRun::host_stage_int16(size_t i)
 	int r;
 	if (L.stage_mform && p.mf_rows_cap) {
 		uint64_t mf_rows = 0, mf_bytes = 0;
-		r = acm_stage_file_mform(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, &info,
-					 h_pkblob + p.mf_off, p.mf_off, reinterpret_cast<acmhip_mform_pair *>(h_pkchunk) + p.mf_pair_off, &mf_rows,
-					 &mf_bytes);
+		r = acmindex::stage_file_mform(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, &info,
+					       h_pkblob + p.mf_off, p.mf_off, reinterpret_cast<acmhip_mform_pair *>(h_pkchunk) + p.mf_pair_off, &mf_rows,
+					       &mf_bytes, marks);
 		if (r == ACM_OK && mf_rows && mf_rows <= p.mf_rows_cap) {
 			s.pk_ntiles = (uint32_t)(mf_rows / (uint64_t)acmhip_mform_tile_rows(info.level));
 			s.mf_used = mf_bytes;
 			s.mf_fused = true;
 		}
 	} else {
-		r = acm_stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, nullptr, 0, &info);
+		r = acmindex::stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, nullptr, 0, &info, marks);
 	}
 	if (r == ACM_OK && info.npatches) {
 		s.patches.resize(info.npatches);
 		r = acm_stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off,
 				   p.need_blocks, s.patches.data(), s.patches.size(), &info);
 	}
+	index_staged(i, r, info);
 	if (r != ACM_OK) {
 		it.status = r;
 		s.ok = false;
@@ -771,7 +811,7 @@ int BatchRun::launch_range(size_t r, size_t stripes_up)
 	const int e = acmk_launch_parse_range_mf(reinterpret_cast<const AcmParseJob *>(d_jobs), (uint32_t)nd, d_files, d_colpos, d_idx,
 						 d_hdr, d_res, reinterpret_cast<uint32_t *>(d_res + nd), max_columns, (uint32_t)r, (uint32_t)R, (uint32_t)stripes_up,
 						 L.dev_mform ? d_pkblob : nullptr, L.dev_mform ? reinterpret_cast<uint32_t *>(d_pkchunk) : nullptr,
-						 L.dev_mform ? d_blkoff : nullptr, st_parse);
+						 L.dev_mform ? d_blkoff : nullptr, d_marks, st_parse);
 	if (e != 0)
 		return acmhip_report_hip(e, "acmk_launch_parse_range");
 	BNOTE("range %zu: walk queued", r);
@@ -868,6 +908,8 @@ int BatchRun::upload_and_walk()
 		}
 	}
 	ACM_HIP_TRY(hipMemcpyAsync(h_jobs + L.jobs_bytes, d_jobs + L.jobs_bytes, L.res_bytes, hipMemcpyDeviceToHost, st_parse));
+	if (d_marks && L.hdr_total)             /* the marks of every range, once, behind the last range's walk */
+		ACM_HIP_TRY(hipMemcpyAsync(h_marks, d_marks, L.hdr_total * sizeof(acm_block_mark), hipMemcpyDeviceToHost, st_parse));
 	ACM_HIP_TRY(hipEventRecord(ev_parsed, st_parse));
 	return ACMHIP_OK;
 }
@@ -904,6 +946,12 @@ int BatchRun::settle()
 		items[i].status = ACM_OK;
 		items[i].words = deliverable_words(s.info.total_values, (uint64_t)s.info.rows * s.info.cols, s.info.channels, p.need_blocks);
 		tm.device_parsed++;
+		if (index) {
+			/* a clean walk: the marks it left beside the headers, and the entry behind the last block from where it ended */
+			memcpy(index[i].marks, h_marks + p.hdr_off, p.need_blocks * sizeof(acm_block_mark));
+			index[i].marks[p.need_blocks] = acm_block_mark{ results[k].end_bit, 0, 0 };
+			index_staged(i, ACM_OK, s.info);
+		}
 	}
 	return ACMHIP_OK;
 }
@@ -1201,6 +1249,12 @@ void BatchRun::roll_up(acm_batch_timing *timing)
 extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_t n,
 				const acm_batch_opts *opts_in, acm_batch_timing *timing)
 {
+	return acm_batch_decode_indexed(dev, items, n, opts_in, nullptr, timing);
+}
+
+extern "C" int acm_batch_decode_indexed(acmhip_device *dev, acm_batch_item *items, size_t n, const acm_batch_opts *opts_in,
+					acm_batch_index_out *index, acm_batch_timing *timing)
+{
 	if (!dev || (n && !items))
 		return ACMHIP_ERR_ARG;
 	acm_batch_opts opts{};
@@ -1227,12 +1281,31 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 
 	/* 1. headers -> the layout: where everything goes and which way every stream travels (acm_batch_layout.cpp) */
 	std::vector<LayoutItem> probed(n);
+	if (index) {
+		/* room for every item's whole index, checked before anything is written: items, PCM and marks stay as they are */
+		std::vector<uint8_t> short_of(n, 0);
+		pool.run(n, [&](size_t i) {
+			acm_stage_info info;
+			short_of[i] = acm_stage_probe(items[i].data, items[i].len, opts.force_chans, &info) == ACM_OK &&
+				      (!index[i].marks || index[i].max_blocks < blocks_possible(info, items[i].len));
+		});
+		for (size_t i = 0; i < n; i++)
+			if (short_of[i]) {
+				acmhip_set_error_text("acm_batch_decode_indexed: an item's marks are missing or hold fewer than acm_batch_index_blocks() asks for");
+				return ACMHIP_ERR_ARG;
+			}
+	}
 	pool.run(n, [&](size_t i) {
 		acm_batch_item &it = items[i];
 		acm_stage_info &info = probed[i].info;
 		it.words = 0;
 		it.dev_off = 0;
 		it.status = acm_stage_probe(it.data, it.len, opts.force_chans, &info);
+		if (index) {                            /* a file that is not ACM: acm_index_file's answer, its marks untouched */
+			index[i].status = (index[i].marks || it.status == ACMHIP_ERR_ARG) ? it.status : ACMHIP_ERR_ARG;
+			index[i].blocks = 0;
+			index[i].end_status = 0;
+		}
 		it.level = info.level;
 		it.rows = info.rows;
 		it.channels = info.channels;
@@ -1247,7 +1320,7 @@ extern "C" int acm_batch_decode(acmhip_device *dev, acm_batch_item *items, size_
 	for (size_t i = 0; i < n; i++)
 		items[i].dev_off = layout.slots[i].pcm_off;
 
-	BatchRun run(dev, items, n, opts, layout, pool, probed, t0, clk::now());
+	BatchRun run(dev, items, n, opts, layout, pool, probed, index, t0, clk::now());
 	ACM_TRY(run.acquire());                 /* arenas, streams, events */
 	ACM_TRY(run.start_pool());              /* 2a / 2b. the device parser's tables; the pool: file copies, host parsing, copy-out */
 	ACM_TRY(run.plan_device_chunks());

@@ -138,7 +138,8 @@ enum {
 	ACM_ARENA_H_IDX = 0, ACM_ARENA_H_HDR, ACM_ARENA_H_PCM, ACM_ARENA_H_FILES, ACM_ARENA_H_JOBS, ACM_ARENA_H_PKBLOB, ACM_ARENA_H_PKCHUNK,
 	ACM_ARENA_D_IDX, ACM_ARENA_D_HDR, ACM_ARENA_D_PCM, ACM_ARENA_D_FILES, ACM_ARENA_D_COLPOS, ACM_ARENA_D_JOBS, ACM_ARENA_D_STAGE,
 	ACM_ARENA_D_PKBLOB, ACM_ARENA_D_PKCHUNK, ACM_ARENA_D_BLKOFF,
-	ACM_ARENA_D_MARKS, ACM_ARENA_H_MARKS,           /* batch index build (acm_batch_index.cpp): the marks of two groups, on the device and pinned */
+	ACM_ARENA_D_MARKS, ACM_ARENA_H_MARKS,           /* the marks of a batch index build's two groups (acm_batch_index.cpp), or of a decode that hands
+	                                                   the index out (acm_batch_decode_indexed: hdr_total of them), on the device and pinned */
 	ACM_ARENA_SLOTS
 };
 /* is this slot pinned host memory (else device memory)? */
@@ -198,21 +199,24 @@ int acmk_launch_patch(const AcmDevPatch *d_patches, uint64_t n, int32_t *d_x, vo
 int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
 		      uint32_t level, uint32_t k, const int32_t *d_in, int32_t *d_out, uint32_t shift, void *stream);
 int acmk_parse_supported(uint32_t level, uint32_t rows, uint64_t file_len, uint64_t blocks);
+/* d_marks (here and in the two launchers below; may be null): the block index as a by-product of the walk (acm_batch_decode_indexed) - an arena
+ * of acm_block_mark indexed like d_hdr; every block the walk completes leaves d_marks[hdr_off + b] = { its first bit, val, pwr }.  The entry
+ * behind a stream's last block is not written: it is d_res[j].end_bit of a walk that came back clean */
 int acmk_launch_parse(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
-		      acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, void *stream);
+		      acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, void *stream);
 /* the same for block range r of R: stream j's blocks [blocks * r / R, blocks * (r + 1) / R), resuming at the bit offset range
  * r - 1 left in d_res (ranges are launched in order on one stream; njobs <= ACM_PARSE_RANGE_MAX_STREAMS) */
 #define ACM_PARSE_RANGE_MAX_STREAMS 32768
 int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
 			    acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t r, uint32_t R,
-			    uint32_t stripes_up, void *stream);
+			    uint32_t stripes_up, acm_block_mark *d_marks, void *stream);
 /* the same with byte-plane staging for the jobs that ask for it (mf_rows != 0): d_mf = the byte-plane arena, d_pairs = its pair table,
  * d_blkoff = one word per block (indexed like d_hdr): where the row pair that holds the block's first row starts in its stream's region, in
  * 64-byte units (blocks of an odd height: every other one begins inside a pair).  Streams are walked
  * by the wave-per-stream kernel only (njobs <= ACM_PARSE_RANGE_MAX_STREAMS) */
 int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
 			       acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t r, uint32_t R,
-			       uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, void *stream);
+			       uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, acm_block_mark *d_marks, void *stream);
 /* Indexed input: njobs jobs (here: windows into streams; a job's file is the byte span of its blocks, data_start unused) whose blocks are
  * the nblock walks of d_bjobs, one wavefront each; then the column kernel over every job, in one piece, int16 rows only.  d_res and d_flags
  * [njobs] must be zero on entry; afterwards job j is clean iff d_res[j].status == 0 && d_res[j].blocks_done == its blocks && d_flags[j] == 0

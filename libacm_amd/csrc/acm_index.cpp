@@ -54,8 +54,7 @@ struct Reader {
 			return ACM_ERR_OTHER;
 		return acmfill::open_common(&a, force_chans);
 	}
-	/* file bit offset of the next unread bit (the buffer starts at file byte buf_start_ofs: the source is read in order) */
-	uint64_t bit() const { return 8ull * ((uint64_t)a.buf_start_ofs + a.buf_pos) - a.bit_avail; }
+	uint64_t bit() const { return acmindex::MarkSink::bit(a); }
 	/* Put the reader where one that came from the start of the file is when it stands at `at` (a bit inside the file): that reader
 	 * takes the file in chunks of kChunkBytes from offset 0 and its accumulator in dwords from offset 0 (decode.c:69-135), and what it
 	 * does in the last bytes of a file - the partial dword, the one zero byte behind the end - depends on both. */
@@ -98,22 +97,20 @@ extern "C" int acm_index_file(const uint8_t *data, size_t len, int force_chans, 
 	const uint64_t want = std::min<uint64_t>(blocks_promised(c.a), max_blocks);
 	std::vector<int16_t> block(c.a.block_len);              /* the indices are parsed (H1 is counted) and dropped */
 	acmfill::PatchSink sink{ nullptr, 0, 0, 0 };
+	const acmindex::MarkSink mk{ marks };
 	uint64_t b = 0;
 	int status = 0;
 	for (; b < want; b++) {
 		acmhip_blkhdr h;
-		marks[b].bit = c.bit();
+		mk.begin(b, c.a);
 		rc = acmfill::parse_block(&c.a, &c.tab, block.data(), &h, &sink);
 		if (rc != 1) {
 			status = (rc == acmfill::kCleanEof) ? 0 : rc;
 			break;
 		}
-		marks[b].val = h.val;
-		marks[b].pwr = h.pwr;
+		mk.whole(b, h);
 	}
-	if (b == want)
-		marks[b].bit = c.bit();
-	marks[b].val = marks[b].pwr = 0;                        /* (a block that failed: its start is the bit behind the last whole one) */
+	mk.end(b, b == want, c.a);
 	info->blocks = (uint32_t)b;
 	info->end_status = status;
 	info->npatches = sink.count;
@@ -227,4 +224,47 @@ extern "C" int acm_stage_window(const uint8_t *data, size_t len, int force_chans
 	if (ncopy)
 		memcpy(patches, found.data(), ncopy * sizeof(acmhip_patch));
 	return ACM_OK;
+}
+
+extern "C" int acmk_stage_marks(const uint8_t *data, size_t len, int force_chans, int stager, acm_block_mark *marks, size_t max_blocks,
+				acm_stage_info *info)
+{
+	if (!data || !info || !marks || stager < 0 || stager > 2)
+		return ACMHIP_ERR_ARG;
+	int rc = acm_stage_probe(data, len, force_chans, info);
+	if (rc != ACM_OK)
+		return rc;
+	const uint32_t level = info->level;
+	const uint64_t bl = (uint64_t)info->rows * info->cols;
+	std::vector<int16_t> idx(std::max<uint64_t>(max_blocks * bl, 1));
+	std::vector<acmhip_blkhdr> hdr(std::max<size_t>(max_blocks, 1));
+	if (stager == 1) {
+		if (acmhip_mform_tile_rows(level) <= 0)
+			return ACMHIP_ERR_ARG;
+		const uint64_t rows_cap = ((uint64_t)max_blocks * info->rows) & ~1ull;
+		std::vector<uint8_t> mf(acmhip_mform_bytes(level, rows_cap) + 256);
+		std::vector<acmhip_mform_pair> pairs(acmhip_mform_pairs(rows_cap) + 32);
+		uint64_t mf_rows = 0, mf_bytes = 0;
+		rc = rows_cap ? acmindex::stage_file_mform(data, len, force_chans, idx.data(), hdr.data(), max_blocks, info, mf.data(), 0, pairs.data(), &mf_rows,
+							   &mf_bytes, marks)
+			      : acmindex::stage_file(data, len, force_chans, idx.data(), hdr.data(), max_blocks, nullptr, 0, info, marks);
+	} else {
+		if (stager == 2 && acmhip_packed_tile_rows(level) <= 0)
+			return ACMHIP_ERR_ARG;
+		rc = acmindex::stage_file(data, len, force_chans, idx.data(), hdr.data(), max_blocks, nullptr, 0, info, marks);
+	}
+	if (rc == ACM_OK && info->npatches) {
+		std::vector<acmhip_patch> patches(info->npatches);
+		rc = acmindex::stage_file(data, len, force_chans, idx.data(), hdr.data(), max_blocks, patches.data(), patches.size(), info, nullptr);
+	}
+	if (rc == ACM_OK && stager == 2 && !info->npatches) {
+		const uint64_t ntiles = (uint64_t)info->blocks * info->rows / (uint64_t)acmhip_packed_tile_rows(level);
+		uint64_t bound = 0, bytes = 0;
+		if (ntiles && acmhip_pack_bound(level, ntiles, &bound) == ACMHIP_OK) {
+			std::vector<uint8_t> blob(bound);
+			std::vector<acmhip_packed_chunk> chunks(ntiles * (uint64_t)acmhip_packed_slots(level));
+			(void)acmhip_pack_tiles(level, idx.data(), ntiles, chunks.data(), blob.data(), 0, &bytes);
+		}
+	}
+	return rc;
 }

@@ -213,7 +213,8 @@ __device__ __forceinline__ uint32_t column_bits(uint32_t code, uint32_t rows)
  */
 template <bool LONE>
 __device__ __forceinline__ void scan_stream(const AcmParseJob &job, const uint8_t *__restrict__ files, uint32_t *__restrict__ colpos,
-					    acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ out, const uint32_t *collen)
+					    acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ out, const uint32_t *collen,
+					    acm_block_mark *__restrict__ marks)
 {
 	const uint32_t rows = job.rows, cols = 1u << job.level;
 	const uint32_t safe = job.file_len * 8u;                /* bits that really belong to the file */
@@ -228,6 +229,7 @@ __device__ __forceinline__ void scan_stream(const AcmParseJob &job, const uint8_
 			status = 1;
 			break;
 		}
+		const uint32_t at = bs.bit;
 		const uint32_t pwr = bs.get(4);
 		const uint32_t val = bs.get(16);
 		for (uint32_t c = 0; c < cols; c++) {
@@ -269,15 +271,18 @@ __device__ __forceinline__ void scan_stream(const AcmParseJob &job, const uint8_
 		if (status)
 			break;
 		hdr[job.hdr_off + b] = acmhip_blkhdr{ val, pwr };
+		if (marks)                                      /* the block's mark, as acm_index_scan_wave writes it: one 16-byte store */
+			reinterpret_cast<uint4 *>(marks)[job.hdr_off + b] = make_uint4(at, 0u, val, pwr);
 		cp += cols;
 		done++;
 	}
-	*out = AcmParseResult{ done, status };
+	*out = AcmParseResult{ done, status, bs.bit, 0u };
 }
 
 __global__ void __launch_bounds__(SCAN_THREADS)
 acm_parse_scan(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const uint8_t *__restrict__ files,
-	       uint32_t *__restrict__ colpos, acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ res)
+	       uint32_t *__restrict__ colpos, acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ res,
+	       acm_block_mark *__restrict__ marks)
 {
 	/* Streams are dealt out across wavefronts first, lanes second: a walk is a chain of dependent steps and
 	 * lanes of one wavefront serialise each other's branches. */
@@ -289,7 +294,7 @@ acm_parse_scan(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const uint8
 	uint32_t *collen = scan_lds + threadIdx.x * 33;
 	for (uint32_t code = 0; code < 32; code++)
 		collen[code] = column_bits(code, job.rows);
-	scan_stream<false>(job, files, colpos, hdr, res + j, collen);
+	scan_stream<false>(job, files, colpos, hdr, res + j, collen, marks);
 }
 
 #ifdef ACM_TUNING
@@ -301,7 +306,7 @@ acm_parse_scan_lone(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const 
 	if (threadIdx.x != 0 || blockIdx.x >= njobs)
 		return;
 	const AcmParseJob job = jobs[blockIdx.x];
-	scan_stream<true>(job, files, colpos, hdr, res + blockIdx.x, nullptr);
+	scan_stream<true>(job, files, colpos, hdr, res + blockIdx.x, nullptr, nullptr);
 }
 #endif
 
@@ -517,12 +522,14 @@ struct WaveWalk {
 constexpr int WAVE_SCAN_WAVES = 4;      /* streams per workgroup: one per SIMD of the CU */
 
 /* One stream per wavefront, whole or in block ranges: the walk core with column offsets, 64 columns per call; this kernel's own are
- * the ranges, the striped upload, the block offsets and the byte-plane places. */
+ * the ranges, the striped upload, the block offsets and the byte-plane places.  marks (null: nobody asked for the index) runs parallel to
+ * hdr: the mark of every block the walk completes goes where its header goes, one 16-byte store from lane 0 as in acm_index_scan_wave.
+ * The entry behind a stream's last block is the host's to make, from end_bit of a walk that came back clean. */
 __global__ void __launch_bounds__(64 * WAVE_SCAN_WAVES)
 acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const uint8_t *__restrict__ files,
 		    uint32_t *__restrict__ colpos, acmhip_blkhdr *__restrict__ hdr, AcmParseResult *__restrict__ res,
 		    const uint32_t range, const uint32_t nranges, const uint32_t stripes_up, uint32_t *__restrict__ blkoff,
-		    uint32_t *__restrict__ mf_pairs)
+		    uint32_t *__restrict__ mf_pairs, acm_block_mark *__restrict__ marks)
 {
 	const uint32_t jobno = blockIdx.x * WAVE_SCAN_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	if (jobno >= njobs)
@@ -578,6 +585,7 @@ acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const 
 	for (uint32_t b = b_lo; b < b_hi; b++) {
 		if (bit + 20 > safe)
 			goto out;
+		const uint32_t at = bit;
 		const uint32_t h20 = wk.header(bit);
 		for (uint32_t c0 = 0; c0 < cols; c0 += 64) {
 			const uint32_t n = __builtin_amdgcn_readfirstlane(min(64u, cols - c0));
@@ -599,6 +607,8 @@ acm_parse_scan_wave(const AcmParseJob *__restrict__ jobs, uint32_t njobs, const 
 				hdr[job.hdr_off + b] = acmhip_blkhdr{ h20 >> 4, h20 & 15u };
 				if (blkoff)
 					blkoff[job.hdr_off + b] = first_at;
+				if (marks)
+					reinterpret_cast<uint4 *>(marks)[job.hdr_off + b] = make_uint4(at, 0u, h20 >> 4, h20 & 15u);
 			}
 			mf_at += (inner >> 1) * ((cols * bp_half_bytes(cls)) >> 6);
 			if (inner & 1u) {
@@ -1041,16 +1051,17 @@ static int launch_columns(uint64_t gx, const AcmParseJob *d_jobs, uint32_t njobs
 extern "C" int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 				       uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
 				       AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t range, uint32_t nranges,
-				       uint32_t stripes_up, void *stream)
+				       uint32_t stripes_up, acm_block_mark *d_marks, void *stream)
 {
 	return acmk_launch_parse_range_mf(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, range, nranges, stripes_up,
-					  nullptr, nullptr, nullptr, stream);
+					  nullptr, nullptr, nullptr, d_marks, stream);
 }
 
 extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 					  uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
 					  AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t range, uint32_t nranges,
-					  uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, void *stream)
+					  uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, acm_block_mark *d_marks,
+					  void *stream)
 {
 	if (njobs == 0)
 		return 0;
@@ -1085,10 +1096,11 @@ extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t nj
 #endif
 	if (njobs <= wave_max)
 		hipLaunchKernelGGL(acm_parse_scan_wave, dim3((njobs + WAVE_SCAN_WAVES - 1) / WAVE_SCAN_WAVES), dim3(64 * WAVE_SCAN_WAVES), 0, st,
-				   d_jobs, njobs, d_files, d_colpos, d_hdr, d_res, range, nranges, stripes_up, mf ? d_blkoff : nullptr, mf ? d_pairs : nullptr);
+				   d_jobs, njobs, d_files, d_colpos, d_hdr, d_res, range, nranges, stripes_up, mf ? d_blkoff : nullptr, mf ? d_pairs : nullptr,
+				   d_marks);
 	else
 		hipLaunchKernelGGL(acm_parse_scan, dim3(scan_waves), dim3(SCAN_THREADS), scan_lanes * 33 * sizeof(uint32_t), st,
-				   d_jobs, njobs, d_files, d_colpos, d_hdr, d_res);
+				   d_jobs, njobs, d_files, d_colpos, d_hdr, d_res, d_marks);
 	ACMP_CHECK();
 	/* a block range of the longest stream: its share of the blocks, rounded up, + one for where the cut falls */
 	const uint64_t range_columns = max_columns / nranges + 32768;           /* (the kernel strides over the grid: a bound, not a contract) */
@@ -1126,7 +1138,7 @@ extern "C" int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, cons
 
 extern "C" int acmk_launch_parse(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 				 uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
-				 AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, void *stream)
+				 AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, void *stream)
 {
-	return acmk_launch_parse_range(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, 0, 1, 0, stream);
+	return acmk_launch_parse_range(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, 0, 1, 0, d_marks, stream);
 }

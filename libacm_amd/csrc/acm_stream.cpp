@@ -27,6 +27,7 @@
 #include "acm_device.h"
 #include "acm_fill.h"
 #include "acm_hip.h"
+#include "acm_index.h"
 #include "libacm.h"
 
 #include <stddef.h>
@@ -767,6 +768,12 @@ extern "C" int acm_stage_file(const uint8_t *data, size_t len, int force_chans,
 			      int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
 			      acmhip_patch *patches, size_t max_patches, acm_stage_info *info)
 {
+	return acmindex::stage_file(data, len, force_chans, idx, hdr, max_blocks, patches, max_patches, info, nullptr);
+}
+
+int acmindex::stage_file(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
+			 acmhip_patch *patches, size_t max_patches, acm_stage_info *info, acm_block_mark *marks)
+{
 	if (!data || !info || (max_blocks && (!idx || !hdr)) || (max_patches && !patches))
 		return ACMHIP_ERR_ARG;
 	memset(info, 0, sizeof(*info));
@@ -781,16 +788,20 @@ extern "C" int acm_stage_file(const uint8_t *data, size_t len, int force_chans,
 	const uint64_t want = std::min<uint64_t>(need, max_blocks);
 	std::vector<acmhip_patch> found;
 	acmfill::PatchSink sink{ &found, 0, 0, 0 };
+	const acmindex::MarkSink mk{ marks };
 	uint64_t b = 0;
 	int status = 0;
 	for (; b < want; b++) {
 		sink.base_sample = b * bl;
+		mk.begin(b, c.a);
 		rc = acmfill::parse_block(&c.a, &c.tab, idx + b * bl, hdr + b, &sink);
 		if (rc != 1) {
 			status = (rc == kCleanEof) ? 0 : rc;
 			break;
 		}
+		mk.whole(b, hdr[b]);
 	}
+	mk.end(b, b == want, c.a);
 	info->blocks = (uint32_t)b;
 	info->end_status = status;
 	info->npatches = found.size();
@@ -816,10 +827,18 @@ extern "C" int acm_stage_file_mform(const uint8_t *data, size_t len, int force_c
 				    acm_stage_info *info, uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows,
 				    uint64_t *mf_bytes)
 {
+	return acmindex::stage_file_mform(data, len, force_chans, idx, hdr, max_blocks, info, mf_out, mf_base, pairs, mf_rows, mf_bytes, nullptr);
+}
+
+int acmindex::stage_file_mform(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
+			       acm_stage_info *info, uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows,
+			       uint64_t *mf_bytes, acm_block_mark *marks)
+{
 	if (!data || !info || !mf_rows || !mf_bytes || (max_blocks && (!idx || !hdr)))
 		return ACMHIP_ERR_ARG;
 	*mf_rows = *mf_bytes = 0;
-	auto plain = [&]() { return acm_stage_file(data, len, force_chans, idx, hdr, max_blocks, nullptr, 0, info); };
+	/* (the plain way parses the stream from its header again and writes every mark again) */
+	auto plain = [&]() { return stage_file(data, len, force_chans, idx, hdr, max_blocks, nullptr, 0, info, marks); };
 	memset(info, 0, sizeof(*info));
 	StageCtx c;
 	int rc = c.open(data, len, force_chans);
@@ -858,15 +877,18 @@ extern "C" int acm_stage_file_mform(const uint8_t *data, size_t len, int force_c
 		return plain();
 	std::vector<acmhip_patch> found;
 	acmfill::PatchSink sink{ &found, 0, 0, 0 };
+	const acmindex::MarkSink mk{ marks };
 	uint64_t b = 0;
 	int status = 0;
 	for (; b < want; b++) {
 		sink.base_sample = b * bl;
+		mk.begin(b, c.a);
 		rc = acmfill::parse_block(&c.a, &c.tab, block.data(), hdr + b, &sink);
 		if (rc != 1) {
 			status = (rc == kCleanEof) ? 0 : rc;
 			break;
 		}
+		mk.whole(b, hdr[b]);
 		if (!found.empty())
 			return plain();                 /* H1: the stream keeps the int16 form (and the caller stages again, for the patches) */
 		const uint64_t r0 = b * rows;
@@ -896,6 +918,7 @@ extern "C" int acm_stage_file_mform(const uint8_t *data, size_t len, int force_c
 	}
 	if (b != want || deliverable(b) != deliverable(want))
 		return plain();                         /* the file ends early: fewer whole tiles than its header promised - the plain way */
+	mk.end(b, true, c.a);
 	info->blocks = (uint32_t)b;
 	info->end_status = status;
 	info->npatches = 0;
