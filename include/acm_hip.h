@@ -525,8 +525,9 @@ void acmhip_prewarm(void);
 uint64_t acm_batch_pcm_words(const acm_batch_item *items, size_t n, int force_chans);
 
 /* ------------------------------------------------------------------------
- * Windowed batch decode (csrc/acm_batch_windows.cpp): random-access crops out of many files in one call, at a cost proportional
- * to the windows - bit parsing, PCIe, synthesis and stores - not to the files.  Needs the block index of every item.
+ * Windowed batch decode (csrc/acm_batch_windows.cpp over the layout of csrc/acm_window_layout.cpp): random-access crops out of
+ * many files in one call, at a cost proportional to the windows - bit parsing, PCIe, synthesis and stores - not to the files.
+ * Needs the block index of every item.
  *
  * Let `whole` be the items[i].words samples acm_batch_decode delivers for item i.  A window's PCM is
  * whole[first_word : first_word + max_words] clipped to the end of whole, bit for bit; `words` its length (0 for a window that

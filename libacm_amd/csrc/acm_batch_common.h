@@ -1,8 +1,11 @@
 /*
- * acm_batch_common.h - what the batch front ends (acm_batch.cpp: whole files; acm_batch_windows.cpp: windows through a block index)
- * share: the worker pool, the arena arithmetic and the delivery rule of acm_read_loop() (acm_batch_layout.h), and the handful of
- * steps both take on the device - a call's hold on the arenas, its events, a plan's descriptors, the verdict on the device parser's
- * results, the file arena's zero tails, the launch.  Internal.
+ * acm_batch_common.h - what the batch front ends share.  Each is a device-free layout and a driver that only walks it:
+ *   acm_batch.cpp          whole files                       over acm_batch_layout.cpp
+ *   acm_batch_windows.cpp  windows through a block index     over acm_window_layout.cpp
+ *   acm_batch_index.cpp    the block index of many files     over acm_index_layout.cpp
+ * Here: the worker pool (acm_pool.h), the arena arithmetic and the delivery rule of acm_read_loop() (acm_batch_layout.h), and the
+ * handful of steps the drivers take on the device - a call's hold on the arenas, its events, a plan's descriptors, the verdict on
+ * the device parser's results, the file arena's zero tails, the launch.  Internal.
  */
 #ifndef ACM_BATCH_COMMON_H
 #define ACM_BATCH_COMMON_H
@@ -25,6 +28,7 @@
 #include "acm_batch_layout.h"
 #include "acm_device.h"
 #include "acm_hip.h"
+#include "acm_pool.h"
 
 /* inside a function that returns an ACMHIP_* code: pass a failure on (its cleanup is the destructors') */
 #define ACM_TRY(call) do { const int rc_ = (call); if (rc_ != ACMHIP_OK) return rc_; } while (0)
@@ -53,82 +57,6 @@ inline int default_threads()
 	}
 	return std::min(n, 64);
 }
-
-/* A fixed set of worker threads that lives for one acm_batch_decode call.  run() is a blocking parallel-for
- * (the caller works too); start()/wait() leave the caller free to drive the device meanwhile. */
-class Pool {
-public:
-	explicit Pool(int threads)
-	{
-		for (int t = 0; t < threads; t++)
-			workers_.emplace_back([this]() { loop(); });
-	}
-	~Pool()
-	{
-		{
-			std::lock_guard<std::mutex> g(m_);
-			quit_ = true;
-		}
-		cv_.notify_all();
-		for (auto &t : workers_)
-			t.join();
-	}
-	void start(size_t n, std::function<void(size_t)> fn)
-	{
-		std::lock_guard<std::mutex> g(m_);
-		fn_ = std::move(fn);
-		n_ = n;
-		next_.store(0);
-		active_ = workers_.size();
-		gen_++;
-		cv_.notify_all();
-	}
-	void wait()
-	{
-		std::unique_lock<std::mutex> g(m_);
-		done_.wait(g, [this]() { return active_ == 0; });
-	}
-	void run(size_t n, const std::function<void(size_t)> &fn)
-	{
-		if (workers_.empty() || n <= 1) {
-			for (size_t i = 0; i < n; i++)
-				fn(i);
-			return;
-		}
-		start(n, fn);
-		for (size_t i; (i = next_.fetch_add(1)) < n;)
-			fn(i);
-		wait();
-	}
-
-private:
-	void loop()
-	{
-		uint64_t seen = 0;
-		for (;;) {
-			{
-				std::unique_lock<std::mutex> g(m_);
-				cv_.wait(g, [&]() { return quit_ || gen_ != seen; });
-				if (quit_)
-					return;
-				seen = gen_;
-			}
-			for (size_t i; (i = next_.fetch_add(1)) < n_;)
-				fn_(i);
-			std::lock_guard<std::mutex> g(m_);
-			if (--active_ == 0)
-				done_.notify_all();
-		}
-	}
-	std::vector<std::thread> workers_;
-	std::mutex m_;
-	std::condition_variable cv_, done_;
-	std::function<void(size_t)> fn_;
-	std::atomic<size_t> next_{ 0 };
-	size_t n_ = 0, active_ = 0;
-	uint64_t gen_ = 0;
-	bool quit_ = false;
-};
 
 /* A call's hold on a device handle's arenas (they live in the handle and are reused by the next batch).  First member of a front end's
  * state object: whatever that object's destructor drains and destroys, the arenas are unlocked after it */

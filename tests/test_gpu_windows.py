@@ -303,6 +303,30 @@ def test_auto_chooses_by_staged_blocks(dev):
     assert tm.blocks_parsed >= 256 and tm.device_parsed == len(big) and tm.host_parsed == 0
 
 
+def test_mixed_host_and_device_windows(dev):
+    """one call that holds a window the device parser takes and one the host stages from the start: a file chopped by its last byte is
+    still whole - its last block ends inside the zero byte the reader appends - but the last mark lies behind the bytes a span can
+    have, so the window over the last block stays with the host while the one over the first goes to the device"""
+    whole = make_stream(7002, 5, 4, 6)
+    s = Src(whole[:-1])
+    assert len(s.data) == 459
+    assert (s.ix.blocks, s.ix.end_status, s.marks.size) == (6, 0, 7) and int(s.marks["bit"][6]) == 3674 > 8 * len(s.data)
+    assert s.st.words == 768 and np.array_equal(s.pcm(), Src(whole).pcm())
+    windows = [(0, 0, 200), (0, 5 * 128 + 7, 100)]
+    got, st, words, slots, tm = run(dev, [s], windows, capi.PARSE_DEVICE)
+    assert tm.device_parsed == 1 and tm.host_parsed == 1
+    got, st, words, slots, tm = run(dev, [s], windows, capi.PARSE_HOST)
+    assert tm.device_parsed == 0 and tm.host_parsed == 2
+    # a window the host stager rejects on that first pass (the header of its last block is not what the index says) has nothing to
+    # upload: the call sends the device window's byte span and the two job tables, and that is all
+    m = s.marks.copy()
+    m["val"][5] ^= 0x40
+    got, st, words, slots, tm = run(dev, [s], windows, capi.PARSE_DEVICE, index=[m], check=False)
+    assert (st[0], words[0]) == (0, 200) and np.array_equal(got[0], s.pcm()[:200])
+    assert st[1] != 0 and words[1] == 0
+    assert tm.device_parsed == 1 and tm.host_parsed == 1 and tm.h2d_bytes == h2d_bound([s], windows[:1])
+
+
 def test_scale_2048_windows(dev):
     """one call, 2048 windows over 512 level-9 streams of 64 blocks mixed with level-7 and level-11 streams"""
     rng = np.random.default_rng(512)
