@@ -379,7 +379,8 @@ int  acm_stage_file(const uint8_t *data, size_t len, int force_chans,
  * *mf_bytes as acmhip_mform_rows writes them; room for acmhip_mform_bytes() / acmhip_mform_pairs() of every row the header
  * promises) and idx receives only the rows from *mf_rows - 2 on, which is all the int16 kernels read of such a stream.
  * *mf_rows = 0: the stream has no form (its level - levels 13 / 14 included, whose int16 rows a plan too small for the lean kernel
- * reads from row 0 on -, H1 patches - then info->npatches says so and the caller stages again with room for them -, a file that
+ * reads from row 0 on -, H1 patches - then info->npatches says so and a caller of this call stages again with room for them (the
+ * library's own callers get them from the same pass) -, a file that
  * ends early) and idx holds every row.  Every index has a place in the form (the whole-range class).  Any block height: a row pair
  * may lie across two blocks.
  */
@@ -388,7 +389,7 @@ int  acm_stage_file_mform(const uint8_t *data, size_t len, int force_chans, int1
 			  uint64_t *mf_bytes);
 
 /* ------------------------------------------------------------------------
- * Block index (csrc/acm_index.cpp; no reference counterpart - the reference re-parses a stream from its first block to seek,
+ * Block index (csrc/acm_stage.cpp; no reference counterpart - the reference re-parses a stream from its first block to seek,
  * util.c:219-242).  A block depends on the blocks in front of it in two ways only: where it starts, and what they left in the
  * never-cleared amplitude table (hazard H1), which their (val, pwr) headers determine.  With one mark per block a reader enters
  * the stream at any block and stages exactly what a reader that came from the header would.

@@ -29,7 +29,7 @@
 #include "acm_batch_common.h"
 #include "acm_device.h"
 #include "acm_hip.h"
-#include "acm_index.h"
+#include "acm_stage.h"
 #include "libacm.h"
 
 namespace {
@@ -197,22 +197,17 @@ extern "C" int acm_batch_prestage(const acm_batch_item *items, size_t n, const a
 		acm_batch_prestaged::Item &s = p->items[i];
 		if (!s.ok)
 			return;
-		acm_stage_info info{};
-		/* first pass counts patches (normally zero) and keeps the marks, second only if there are any */
-		int r = acmindex::stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks, nullptr, 0,
-					     &info, p->marks.data() + s.marks_off);
-		if (r == ACM_OK && info.npatches) {
-			s.patches.resize(info.npatches);
-			r = acm_stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks,
-					   s.patches.data(), s.patches.size(), &info);
-		}
+		acmstage::Staged st;
+		const int r = acmstage::stage_file(items[i].data, items[i].len, opts.force_chans, p->idx + s.idx_off, p->hdr + s.hdr_off, s.need_blocks,
+						   p->marks.data() + s.marks_off, nullptr, &st);
 		if (r != ACM_OK) {
 			s.status = r;
 			s.ok = false;
 			return;
 		}
-		s.info = info;
-		s.status = info.end_status;
+		s.info = st.info;
+		s.patches = std::move(st.patches);
+		s.status = st.info.end_status;
 	});
 	if (seconds)
 		*seconds = secs(t0, clk::now());
@@ -558,27 +553,21 @@ void BatchRun::host_stage_int16(size_t i)
 		it.words = deliverable_words(ps.info.total_values, bl, ps.info.channels, ps.info.blocks);
 		return;
 	}
-	/* first pass counts patches (normally zero), second only if there are any.  With ACM_BATCH_STAGE_BYTEPLANE the first pass also
-	 * writes the byte-plane form, block by block out of the cache (acm_stage_file_mform), where the stream can have it */
-	int r;
-	if (L.stage_mform && p.mf_rows_cap) {
-		uint64_t mf_rows = 0, mf_bytes = 0;
-		r = acmindex::stage_file_mform(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, &info,
-					       h_pkblob + p.mf_off, p.mf_off, reinterpret_cast<acmhip_mform_pair *>(h_pkchunk) + p.mf_pair_off, &mf_rows,
-					       &mf_bytes, marks);
-		if (r == ACM_OK && mf_rows && mf_rows <= p.mf_rows_cap) {
-			s.pk_ntiles = (uint32_t)(mf_rows / (uint64_t)acmhip_mform_tile_rows(info.level));
-			s.mf_used = mf_bytes;
-			s.mf_fused = true;
-		}
-	} else {
-		r = acmindex::stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, nullptr, 0, &info, marks);
+	/* one pass, patches (normally none) included.  With ACM_BATCH_STAGE_BYTEPLANE it also writes the byte-plane form, block by block
+	 * out of the cache (acm_stage_file_mform), where the stream can have it */
+	const bool fuse = L.stage_mform && p.mf_rows_cap;
+	const acmstage::MformArena mf{ fuse ? h_pkblob + p.mf_off : nullptr, p.mf_off,
+				       fuse ? reinterpret_cast<acmhip_mform_pair *>(h_pkchunk) + p.mf_pair_off : nullptr };
+	acmstage::Staged st;
+	const int r = acmstage::stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off, p.need_blocks, marks,
+					   fuse ? &mf : nullptr, &st);
+	if (r == ACM_OK && st.mf_rows && st.mf_rows <= p.mf_rows_cap) {
+		s.pk_ntiles = (uint32_t)(st.mf_rows / (uint64_t)acmhip_mform_tile_rows(st.info.level));
+		s.mf_used = st.mf_bytes;
+		s.mf_fused = true;
 	}
-	if (r == ACM_OK && info.npatches) {
-		s.patches.resize(info.npatches);
-		r = acm_stage_file(it.data, it.len, opts.force_chans, h_idx + p.idx_off, h_hdr + p.hdr_off,
-				   p.need_blocks, s.patches.data(), s.patches.size(), &info);
-	}
+	info = st.info;
+	s.patches = std::move(st.patches);
 	index_staged(i, r, info);
 	if (r != ACM_OK) {
 		it.status = r;

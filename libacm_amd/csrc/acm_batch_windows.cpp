@@ -2,7 +2,7 @@
  * acm_batch_windows.cpp - windowed batch decode: random-access crops out of many files in one call (include/acm_hip.h).
  *
  * No counterpart in the reference (it seeks by re-parsing a stream from its first block, util.c:219-242, one stream at a time).
- * With the block index of a file (acm_index.cpp) a window costs what the window holds: only the blocks from two rows in front of
+ * With the block index of a file (acm_index_file, acm_stage.cpp) a window costs what the window holds: only the blocks from two rows in front of
  * its first sample to its last one are bit-parsed, cross PCIe, are synthesised and stored.  Each window becomes a pseudo-stream over
  * those blocks - a stream descriptor whose row_begin is the row of the first sample - and one plan over int16 rows covers the call.
  *
@@ -23,7 +23,7 @@
 #include "acm_batch_common.h"
 #include "acm_device.h"
 #include "acm_hip.h"
-#include "acm_index.h"
+#include "acm_stage.h"
 #include "acm_window_layout.h"
 #include "libacm.h"
 
@@ -125,7 +125,7 @@ void WinRun::stage_one(size_t k)
 	const WindowItem &it = its[w.item];
 	acm_stage_info info;
 	live[k].patches.clear();
-	const int r = acmindex::stage_window(f.data, f.len, opts.force_chans, it.marks, it.blocks, s.b0, s.nb,
+	const int r = acmstage::stage_window(f.data, f.len, opts.force_chans, it.marks, it.blocks, s.b0, s.nb,
 					     h_idx + s.idx_off, h_hdr + s.hdr_off, &live[k].patches, &info);
 	if (r != ACM_OK || info.blocks != s.nb) {
 		w.status = r != ACM_OK ? r : info.end_status ? info.end_status : ACM_ERR_CORRUPT;
@@ -274,7 +274,7 @@ std::vector<WindowItem> probe_items(Pool &pool, const acm_batch_item *items, siz
 		}
 		const uint64_t bl = (uint64_t)it.info.rows * it.info.cols;
 		const uint64_t promised = ((uint64_t)it.info.total_values + bl - 1) / bl;
-		if (index[i].blocks > promised || !acmindex::index_plausible(it.info, items[i].len, index[i].marks, index[i].blocks)) {
+		if (index[i].blocks > promised || !acmstage::index_plausible(it.info, items[i].len, index[i].marks, index[i].blocks)) {
 			it.end_status = ACMHIP_ERR_ARG;
 			return;
 		}

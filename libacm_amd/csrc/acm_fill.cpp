@@ -640,6 +640,33 @@ int skip_bits(ACMStream *s, unsigned n)
 	return v < 0 ? v : 0;
 }
 
+int open_common(ACMStream *a, int force_chans)
+{
+	if (read_headers(a) < 0)
+		return ACM_ERR_NOT_ACM;                 /* every header-stage failure reads as "not ACM" (:783-785) */
+	if (force_chans > 0)
+		a->info.channels = (unsigned)force_chans;
+	else if (force_chans == -1 && !a->wavc_file && a->info.channels < 2)
+		a->info.channels = 2;
+	a->info.acm_cols = 1u << a->info.acm_level;
+	a->wrapbuf_len = 2 * a->info.acm_cols - 2;
+	a->block_len = a->info.acm_rows * a->info.acm_cols;
+	return ACM_OK;
+}
+
+void fill_stage_info(const ACMStream *a, acm_stage_info *info)
+{
+	info->level = a->info.acm_level;
+	info->rows = a->info.acm_rows;
+	info->cols = a->info.acm_cols;
+	info->channels = a->info.channels;
+	info->hdr_channels = a->info.acm_channels;
+	info->rate = a->info.rate;
+	info->total_values = a->total_values;
+	info->wavc = a->wavc_file;
+	info->header_bytes = a->wavc_file ? 42 : 14;
+}
+
 void reset_reader(ACMStream *s)
 {
 	s->file_eof = 0;

@@ -66,7 +66,7 @@ void reset_reader(ACMStream *s);
 /* consume n (< 32) bits through the exact reader (used to re-enter the stream at a remembered bit offset); 0 or error */
 int skip_bits(ACMStream *s, unsigned n);
 
-/* header parse + channel forcing + derived sizes, shared by open and the staging calls (decode.c:783-804; acm_stream.cpp).
+/* header parse + channel forcing + derived sizes, shared by acm_open_decoder and the staging calls (decode.c:783-804).
  * ACM_OK or ACM_ERR_NOT_ACM */
 int open_common(ACMStream *a, int force_chans);
 /* the header's fields as the staging calls report them (blocks, end_status and npatches are the caller's) */

@@ -1,7 +1,7 @@
 /*
  * acm_mform.h - the byte-plane stager as a writer that takes a stream pair by pair (acm_pack.cpp).  Internal to libacm_hip.so:
  * acmhip_mform_rows (include/acm_hip.h) is begin + one put_pair per row pair + end; the host parser's fused staging
- * (acm_stage_file_mform, acm_stream.cpp) feeds it block by block while the block it has just parsed is still in the cache.
+ * (acm_stage_file_mform, acm_stage.cpp) feeds it block by block while the block it has just parsed is still in the cache.
  */
 #ifndef ACM_MFORM_H
 #define ACM_MFORM_H

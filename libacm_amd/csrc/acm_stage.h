@@ -1,9 +1,10 @@
 /*
- * acm_index.h - the block index of a file and the host stager that enters a stream through it (acm_index.cpp).
- * Internal; the public calls are acm_index_file / acm_stage_window of include/acm_hip.h.
+ * acm_stage.h - the host stagers of a file image held in memory (acm_stage.cpp): the block index, whole files as int16 rows or in the
+ * byte-plane form, and a run of blocks entered through the index.  Internal; the public calls are acm_stage_probe / acm_stage_file /
+ * acm_stage_file_mform / acm_index_file / acm_stage_window of include/acm_hip.h.  No device code behind this header.
  */
-#ifndef ACM_INDEX_H
-#define ACM_INDEX_H
+#ifndef ACM_STAGE_H
+#define ACM_STAGE_H
 
 #include <stddef.h>
 #include <stdint.h>
@@ -13,11 +14,11 @@
 #include "acm_hip.h"
 #include "libacm.h"
 
-namespace acmindex {
+namespace acmstage {
 
 /* The index as a by-product of a reader's block loop: acm_index_file's rule for a block that fails and for the entry behind the last
  * one, stated once for acm_index_file and for the stagers that hand the index out beside what they stage.  marks may be null: nothing
- * is kept.  A loop calls begin() where it stands in front of block b, whole() once parse_block has returned 1 for it, and end() with
+ * is kept.  The loop calls begin() where it stands in front of block b, whole() once parse_block has returned 1 for it, and end() with
  * the number of whole blocks when it is over */
 struct MarkSink {
 	acm_block_mark *marks;
@@ -47,12 +48,26 @@ struct MarkSink {
 	}
 };
 
-/* acm_stage_file / acm_stage_file_mform (acm_stream.cpp) with the index of what they stage as a by-product: marks (may be null) has room
- * for max_blocks + 1 entries and receives what acm_index_file(data, len, force_chans, marks, max_blocks, ..) writes */
-int stage_file(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks, acmhip_patch *patches,
-	       size_t max_patches, acm_stage_info *info, acm_block_mark *marks);
-int stage_file_mform(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks, acm_stage_info *info,
-		     uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows, uint64_t *mf_bytes, acm_block_mark *marks);
+/* what staging a file yields besides the rows, headers and marks in the caller's buffers */
+struct Staged {
+	acm_stage_info info{};
+	std::vector<acmhip_patch> patches;      /* every H1 patch of the staged blocks, in stream order */
+	uint64_t mf_rows = 0, mf_bytes = 0;     /* rows [0, mf_rows) are in the byte-plane form, in mf_bytes of the blob; 0: none */
+};
+
+/* a byte-plane arena offered to stage_file: acm_stage_file_mform's mf_out, mf_base and pairs */
+struct MformArena {
+	uint8_t *out;
+	uint64_t base;
+	acmhip_mform_pair *pairs;
+};
+
+/* acm_stage_file - or, with an arena, acm_stage_file_mform - in ONE call whatever the stream holds: every patch comes back in
+ * out->patches, so no caller stages a file a second time to make room for them.  marks (may be null) has room for max_blocks + 1
+ * entries and receives what acm_index_file(data, len, force_chans, marks, max_blocks, ..) writes.  A stream that cannot have the form
+ * (acm_stage_file_mform names the cases) is staged the plain way and out->mf_rows is 0 */
+int stage_file(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks, acm_block_mark *marks,
+	       const MformArena *mf, Staged *out);
 
 /* Is marks[0 .. blocks] an index a file of `len` bytes with this header can have?  Bits behind the header, strictly increasing,
  * every block at least its 20-bit header and a 5-bit code per column long, the indexed blocks inside the file (the end entry may
@@ -65,13 +80,12 @@ int stage_window(const uint8_t *data, size_t len, int force_chans, const acm_blo
 		 uint32_t block_first, uint32_t block_count, int16_t *idx, acmhip_blkhdr *hdr, std::vector<acmhip_patch> *patches,
 		 acm_stage_info *info);
 
-} // namespace acmindex
+} // namespace acmstage
 
 extern "C" {
-/* Test hook, no device: one file through the host stager a batch's pool picks for `stager` - 0 acm_stage_file (int16 rows), 1
- * acm_stage_file_mform (the byte-plane form), 2 acm_stage_file + acmhip_pack_tiles (the packed form) - with a second pass for H1 patches
- * as the pool makes it; what is staged is dropped, only the return code, *info and marks[0 .. max_blocks] come back.  ACMHIP_ERR_ARG for
- * a level that does not have the form asked for */
+/* Test hook, no device: one file through acmstage::stage_file the way a batch's pool calls it for `stager` - 0 int16 rows, 1 with a
+ * byte-plane arena, 2 int16 rows + acmhip_pack_tiles (the packed form); what is staged is dropped, only the return code, *info and
+ * marks[0 .. max_blocks] come back.  ACMHIP_ERR_ARG for a level that does not have the form asked for */
 int acmk_stage_marks(const uint8_t *data, size_t len, int force_chans, int stager, acm_block_mark *marks, size_t max_blocks, acm_stage_info *info);
 }
 

@@ -1,7 +1,7 @@
 /*
  * acm_stream.cpp - the libacm.h API (drop-in for /root/reference/src/decode.c
  * :758-893 and src/util.c) on top of the host parser (acm_fill) and the device
- * synthesis (acm_hip.h), plus the whole-file staging entry points.
+ * synthesis (acm_hip.h).
  *
  * acm_read() keeps the reference's call-by-call contract (decode.c:826-876)
  * but a "decoded block" is a slice of a read-ahead window: the host parses a
@@ -27,7 +27,6 @@
 #include "acm_device.h"
 #include "acm_fill.h"
 #include "acm_hip.h"
-#include "acm_index.h"
 #include "libacm.h"
 
 #include <stddef.h>
@@ -389,59 +388,7 @@ int next_block(HipStream *hs)
 	return 1;
 }
 
-/* ---- in-memory data source for the whole-file staging calls ---- */
-struct MemSource {
-	const uint8_t *p;
-	size_t len, pos;
-};
-
-int mem_read(void *ptr, int size, int n, void *arg)
-{
-	MemSource *m = (MemSource *)arg;
-	size_t want = (size_t)size * (size_t)n;
-	if (want > m->len - m->pos)
-		want = m->len - m->pos;
-	memcpy(ptr, m->p + m->pos, want);
-	m->pos += want;
-	return size ? (int)(want / (size_t)size) : 0;
-}
-
 } // namespace
-
-namespace acmfill {
-
-/* header parse + channel forcing + derived sizes, shared by open and staging (decode.c:783-804) */
-int open_common(ACMStream *a, int force_chans)
-{
-	if (acmfill::read_headers(a) < 0)
-		return ACM_ERR_NOT_ACM;                 /* every header-stage failure reads as "not ACM" (:783-785) */
-	if (force_chans > 0)
-		a->info.channels = (unsigned)force_chans;
-	else if (force_chans == -1 && !a->wavc_file && a->info.channels < 2)
-		a->info.channels = 2;
-	a->info.acm_cols = 1u << a->info.acm_level;
-	a->wrapbuf_len = 2 * a->info.acm_cols - 2;
-	a->block_len = a->info.acm_rows * a->info.acm_cols;
-	return ACM_OK;
-}
-
-void fill_stage_info(const ACMStream *a, acm_stage_info *info)
-{
-	info->level = a->info.acm_level;
-	info->rows = a->info.acm_rows;
-	info->cols = a->info.acm_cols;
-	info->channels = a->info.channels;
-	info->hdr_channels = a->info.acm_channels;
-	info->rate = a->info.rate;
-	info->total_values = a->total_values;
-	info->wavc = a->wavc_file;
-	info->header_bytes = a->wavc_file ? 42 : 14;
-}
-
-} // namespace acmfill
-
-using acmfill::fill_stage_info;
-using acmfill::open_common;
 
 /* ======================================================================== */
 /* core API                                                                  */
@@ -473,7 +420,7 @@ extern "C" int acm_open_decoder(ACMStream **res, void *arg, acm_io_callbacks io_
 	a->buf = (unsigned char *)malloc(a->buf_max);
 	int err = ACM_ERR_OTHER;
 	if (a->buf) {
-		err = open_common(a, force_chans);
+		err = acmfill::open_common(a, force_chans);
 		if (err == ACM_OK) {
 			hs->tell_now = acmfill::raw_position(a);
 			*res = a;
@@ -720,209 +667,4 @@ extern "C" int acm_seek_time(ACMStream *acm, unsigned time_ms)
 	if (res <= 0)
 		return res;
 	return (int)words_to_ms(acm, (unsigned)res);
-}
-
-/* ======================================================================== */
-/* whole-file staging (include/acm_hip.h)                                    */
-/* ======================================================================== */
-
-namespace {
-
-struct StageCtx {
-	ACMStream a;
-	MemSource src;
-	acmfill::TableHistory tab;
-	StageCtx() { memset(&a, 0, sizeof(a)); }
-	~StageCtx() { free(a.buf); }
-	int open(const uint8_t *data, size_t len, int force_chans)
-	{
-		src = MemSource{ data, len, 0 };
-		tab.reset();
-		a.io.read_func = mem_read;
-		a.io_arg = &src;
-		a.data_len = (unsigned)len;
-		a.buf_max = acmfill::kChunkBytes;
-		a.buf = (unsigned char *)malloc(a.buf_max);
-		if (!a.buf)
-			return ACM_ERR_OTHER;
-		return open_common(&a, force_chans);
-	}
-};
-
-} // namespace
-
-extern "C" int acm_stage_probe(const uint8_t *data, size_t len, int force_chans, acm_stage_info *info)
-{
-	if (!data || !info)
-		return ACMHIP_ERR_ARG;
-	memset(info, 0, sizeof(*info));
-	StageCtx c;
-	const int rc = c.open(data, len, force_chans);
-	if (rc < 0)
-		return rc;
-	fill_stage_info(&c.a, info);
-	return ACM_OK;
-}
-
-extern "C" int acm_stage_file(const uint8_t *data, size_t len, int force_chans,
-			      int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
-			      acmhip_patch *patches, size_t max_patches, acm_stage_info *info)
-{
-	return acmindex::stage_file(data, len, force_chans, idx, hdr, max_blocks, patches, max_patches, info, nullptr);
-}
-
-int acmindex::stage_file(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
-			 acmhip_patch *patches, size_t max_patches, acm_stage_info *info, acm_block_mark *marks)
-{
-	if (!data || !info || (max_blocks && (!idx || !hdr)) || (max_patches && !patches))
-		return ACMHIP_ERR_ARG;
-	memset(info, 0, sizeof(*info));
-	StageCtx c;
-	int rc = c.open(data, len, force_chans);
-	if (rc < 0)
-		return rc;
-	fill_stage_info(&c.a, info);
-
-	const size_t bl = c.a.block_len;
-	const uint64_t need = ((uint64_t)c.a.total_values + bl - 1) / bl;
-	const uint64_t want = std::min<uint64_t>(need, max_blocks);
-	std::vector<acmhip_patch> found;
-	acmfill::PatchSink sink{ &found, 0, 0, 0 };
-	const acmindex::MarkSink mk{ marks };
-	uint64_t b = 0;
-	int status = 0;
-	for (; b < want; b++) {
-		sink.base_sample = b * bl;
-		mk.begin(b, c.a);
-		rc = acmfill::parse_block(&c.a, &c.tab, idx + b * bl, hdr + b, &sink);
-		if (rc != 1) {
-			status = (rc == kCleanEof) ? 0 : rc;
-			break;
-		}
-		mk.whole(b, hdr[b]);
-	}
-	mk.end(b, b == want, c.a);
-	info->blocks = (uint32_t)b;
-	info->end_status = status;
-	info->npatches = found.size();
-	const size_t ncopy = std::min(found.size(), max_patches);
-	if (ncopy)
-		memcpy(patches, found.data(), ncopy * sizeof(acmhip_patch));
-	return ACM_OK;
-}
-
-/*
- * The same with the byte-plane form written while the parsed block is still in the cache: a block is parsed into a buffer of its own
- * (16 KB at level 9: the first-level cache, where the column scatter of the parser costs nothing), its row pairs go to the byte-plane
- * writer from there, and only the rows the int16 kernels still read - from two rows in front of the ragged tail on - are copied to
- * idx.  Against acm_stage_file + acmhip_mform_rows this drops the 2 B per sample written to and read back from the int16 arena.
- * *mf_rows = rows [0, *mf_rows) are in the form (whole tiles of the lean kernel); 0: the stream has none (a level without the form,
- * H1 patches, an index beyond the form's range, a file that ends early) and idx holds every row as acm_stage_file
- * leaves it - except that with patches (info->npatches != 0) the caller stages once more with room for them.
- */
-#include "acm_device.h"
-#include "acm_mform.h"
-
-extern "C" int acm_stage_file_mform(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
-				    acm_stage_info *info, uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows,
-				    uint64_t *mf_bytes)
-{
-	return acmindex::stage_file_mform(data, len, force_chans, idx, hdr, max_blocks, info, mf_out, mf_base, pairs, mf_rows, mf_bytes, nullptr);
-}
-
-int acmindex::stage_file_mform(const uint8_t *data, size_t len, int force_chans, int16_t *idx, acmhip_blkhdr *hdr, size_t max_blocks,
-			       acm_stage_info *info, uint8_t *mf_out, uint64_t mf_base, acmhip_mform_pair *pairs, uint64_t *mf_rows,
-			       uint64_t *mf_bytes, acm_block_mark *marks)
-{
-	if (!data || !info || !mf_rows || !mf_bytes || (max_blocks && (!idx || !hdr)))
-		return ACMHIP_ERR_ARG;
-	*mf_rows = *mf_bytes = 0;
-	/* (the plain way parses the stream from its header again and writes every mark again) */
-	auto plain = [&]() { return stage_file(data, len, force_chans, idx, hdr, max_blocks, nullptr, 0, info, marks); };
-	memset(info, 0, sizeof(*info));
-	StageCtx c;
-	int rc = c.open(data, len, force_chans);
-	if (rc < 0)
-		return rc;
-	fill_stage_info(&c.a, info);
-	const uint32_t level = info->level, rows = info->rows;
-	const int T2 = acmk_tile2_rows(level), TM = acmhip_mform_tile_rows(level);
-	/* (levels 13 / 14: whether a plan takes such a stream's form is known only from the whole plan - acmhip_plan_form_rows - so its
-	 * int16 rows may all be needed: the plain way) */
-	if (!mf_out || !pairs || T2 <= 0 || TM <= 0 || T2 % TM || level > ACM_K1_MAX_LEVEL)
-		return plain();
-	const size_t bl = c.a.block_len, cols = (size_t)1 << level;
-	const uint64_t need = ((uint64_t)c.a.total_values + bl - 1) / bl;
-	const uint64_t want = std::min<uint64_t>(need, max_blocks);
-	/* what a complete file delivers (decode.c:853-857: whole blocks, the last one cut at total_values, rounded to whole frames) */
-	auto deliverable = [&](uint64_t blocks) {
-		uint64_t pos = 0;
-		for (uint64_t b = 0; b < blocks && pos < c.a.total_values; b++) {
-			uint64_t take = std::min<uint64_t>(bl, c.a.total_values - pos);
-			if (info->channels > 1)
-				take -= take % info->channels;
-			pos += take;
-			if (take != bl)
-				break;
-		}
-		return pos;
-	};
-	const uint64_t rows2 = std::min<uint64_t>(want * rows, deliverable(want) >> level) / (uint64_t)T2 * (uint64_t)T2;
-	if (rows2 == 0)
-		return plain();
-	const uint64_t tail_from = rows2 >= 2 ? rows2 - 2 : 0;
-	std::vector<int16_t> block(bl), straddle((rows & 1) ? 2 * cols : 0);
-	AcmMformWriter w;
-	if (acm_mform_begin(&w, level, mf_out, mf_base, pairs) != ACMHIP_OK)
-		return plain();
-	std::vector<acmhip_patch> found;
-	acmfill::PatchSink sink{ &found, 0, 0, 0 };
-	const acmindex::MarkSink mk{ marks };
-	uint64_t b = 0;
-	int status = 0;
-	for (; b < want; b++) {
-		sink.base_sample = b * bl;
-		mk.begin(b, c.a);
-		rc = acmfill::parse_block(&c.a, &c.tab, block.data(), hdr + b, &sink);
-		if (rc != 1) {
-			status = (rc == kCleanEof) ? 0 : rc;
-			break;
-		}
-		mk.whole(b, hdr[b]);
-		if (!found.empty())
-			return plain();                 /* H1: the stream keeps the int16 form (and the caller stages again, for the patches) */
-		const uint64_t r0 = b * rows;
-		/* row pairs count from the stream's row 0: with an odd acm_rows every other block starts on the second row of a pair, whose
-		 * first row is the last one of the block before (kept in `straddle`) */
-		for (uint32_t r = 0; r < rows && r0 + r < rows2;) {
-			const int16_t *two = block.data() + (size_t)r * cols;
-			if ((r0 + r) & 1) {
-				memcpy(straddle.data() + cols, two, cols * sizeof(int16_t));
-				two = straddle.data();
-				r += 1;
-			} else if (r + 1 < rows) {
-				r += 2;
-			} else {
-				if (straddle.empty())
-					straddle.resize(2 * cols);
-				memcpy(straddle.data(), two, cols * sizeof(int16_t));
-				break;
-			}
-			if (acm_mform_put_pair(&w, two) != ACMHIP_OK)
-				return plain();         /* an index beyond the form's range */
-		}
-		if (r0 + rows > tail_from) {
-			const uint32_t from = r0 >= tail_from ? 0u : (uint32_t)(tail_from - r0);
-			memcpy(idx + (r0 + from) * cols, block.data() + (size_t)from * cols, (size_t)(rows - from) * cols * sizeof(int16_t));
-		}
-	}
-	if (b != want || deliverable(b) != deliverable(want))
-		return plain();                         /* the file ends early: fewer whole tiles than its header promised - the plain way */
-	mk.end(b, true, c.a);
-	info->blocks = (uint32_t)b;
-	info->end_status = status;
-	info->npatches = 0;
-	*mf_rows = rows2;
-	*mf_bytes = acm_mform_end(&w);
-	return ACM_OK;
 }

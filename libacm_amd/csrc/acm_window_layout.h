@@ -10,7 +10,7 @@
 
 #include "acm_batch_layout.h"
 #include "acm_device.h"
-#include "acm_index.h"
+#include "libacm.h"
 
 namespace acmbatch {
 

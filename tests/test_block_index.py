@@ -1,5 +1,5 @@
 """The block index (acm_index_file), the host window stager (acm_stage_window) and the window semantics of
-acm_batch_decode_windows, on the CPU (libacm_amd/csrc/acm_index.cpp, acm_batch_windows.cpp; include/acm_hip.h).
+acm_batch_decode_windows, on the CPU (libacm_amd/csrc/acm_stage.cpp, acm_batch_windows.cpp; include/acm_hip.h).
 
 The yardstick throughout is acm_stage_file over the whole file: the index must report what it reports, and a window staged through
 the index must be exactly the slice of what it writes - indices, headers and H1 patches (sample positions and values)."""
@@ -224,7 +224,7 @@ def test_index_and_stager_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "fuzz_index")
     csrc = os.path.join(ROOT, "libacm_amd", "csrc")
     src = [os.path.join(ROOT, "tests", "native", "fuzz_index.cpp")] + \
-          [os.path.join(csrc, f) for f in ("acm_index.cpp", "acm_fill.cpp", "acm_stream.cpp", "acm_pack.cpp", "acm_host_synth.cpp")]
+          [os.path.join(csrc, f) for f in ("acm_stage.cpp", "acm_fill.cpp", "acm_pack.cpp")]
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", exe] + src + ["-lpthread"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -1,4 +1,4 @@
-"""The block index as a by-product of the host stagers, without a device (libacm_amd/csrc/acm_index.h: MarkSink, acmk_stage_marks;
+"""The block index as a by-product of the host stagers, without a device (libacm_amd/csrc/acm_stage.h: MarkSink, acmk_stage_marks;
 acm_batch.cpp: acm_batch_prestage / acm_batch_prestaged_index).
 
 Every file goes through every host stager the pool of acm_batch_decode can pick at its level - acm_stage_file (int16 rows),
@@ -46,8 +46,8 @@ def test_wavc_prefix():
 
 
 def test_h1_stream():
-    """indices outside the block's amplitude range: the stagers parse twice (the second time with room for the patches), the byte-plane
-    one falls back to the plain way - the marks are the same"""
+    """indices outside the block's amplitude range: the stagers keep the patches of their one pass, the byte-plane one gives its
+    attempt up and stages the plain way - the marks are the same"""
     files = [make_stream(850 + i, lv, 16, 6, allow_out_of_range=1, pwr_min=0, pwr_max=3) for i, lv in enumerate((3, 7, 9))]
     for f in files:
         assert index_info(f).npatches > 0 and capi.stage_file(f).info.npatches == index_info(f).npatches

@@ -456,7 +456,7 @@ def test_device_parser_stages_every_width_class_and_odd_block_heights(dev, monke
 def test_device_parser_stages_odd_block_heights(dev, monkeypatch, level, ranges):
     """the same batches as test_batch_stages_odd_block_heights, parsed AND staged on the device: every stream travels in the form, same PCM
     as the oracle.  (Levels 13 / 14: both fused stagers - this one and acm_stage_file_mform - keep the int16 form, because a plan too small
-    for the lean kernel reads int16 rows from row 0 on; acm_batch.cpp, acm_stream.cpp.)  In one piece and in block ranges: a stream's
+    for the lean kernel reads int16 rows from row 0 on; acm_batch.cpp, acm_stage.cpp.)  In one piece and in block ranges: a stream's
     ranges are cut where whole tiles end (acmk_range_bound), so no range cuts a row pair or leaves a ragged end inside the form."""
     monkeypatch.setattr(capi, "BATCH_EXTRA", capi.batch_ranges(ranges))
     files = [make_stream(33000 + 50 * level + i, level, rows, max(3, (9 * plan_rows(level) + rows - 1) // rows + i), channels=1 + i % 2, cut=i,
