@@ -318,12 +318,13 @@ __attribute__((always_inline)) inline int parse_column(Cursor &bc, unsigned code
 			if (bc.have < 7)
 				bc.refill();
 			const uint32_t e = tab[(uint32_t)bc.win & 127u];
-			if (e & (1u << 17))
-				return ACM_ERR_CORRUPT;
 			const unsigned len = e & 7u, cnt = (e >> 3) & 3u;
 			bc.win >>= len;
 			bc.have -= len;
 			bc.bit += len;
+			/* the reference has taken the symbol's 5 or 7 bits when it rejects it (:412, :438, :464), and the caller parses on from there */
+			if (e & (1u << 17))
+				return ACM_ERR_CORRUPT;
 			/* all three stores always: a surplus one writes the 0 a later symbol overwrites, or the sink */
 			col[0] = (int16_t)((int)((e >> 5) & 15u) - 8);
 			*(r + 1 < rows ? col + pitch : &sink) = (int16_t)((int)((e >> 9) & 15u) - 8);

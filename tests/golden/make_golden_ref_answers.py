@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Record tests/golden/ref_answers.json: the REAL reference's answers to the questions of the tests that compare against it
-(tests/test_oracle_vs_ref.py and the seek walks of tests/test_libacm_api.py, helpers.RefAnswers).
+(tests/test_oracle_vs_ref.py, the seek walks of tests/test_libacm_api.py and the damaged streams of tests/damaged_streams.py,
+helpers.RefAnswers).
 
 Runs those tests in this process with the live reference (oracle/_ref, built by `make -C oracle ref`; only where its sources
 are), so every answer is an observation of the compiled reference, and the tests pass against it while recording.
@@ -24,7 +25,8 @@ import oracle_api as O  # noqa: E402
 TESTS = ["tests/test_oracle_vs_ref.py",
          "tests/test_libacm_api.py::test_random_seek_walk_matches_reference",
          "tests/test_libacm_api.py::test_random_seek_walk_pcm",
-         "tests/test_libacm_api.py::test_seek_walk_on_a_stale_table_stream"]
+         "tests/test_libacm_api.py::test_seek_walk_on_a_stale_table_stream",
+         "tests/test_damaged_streams.py::test_oracle_matches_the_reference"]
 
 
 def main():

@@ -402,10 +402,12 @@ def read_digest(rc_bytes):
     return [rc_bytes[0], sha(rc_bytes[1])]
 
 
-@pytest.mark.parametrize("shape", [(7, 16, 120, 1, 0), (5, 1, 300, 2, 1), (9, 16, 12, 2, 0), (6, 3, 80, 1, 0)])
+@pytest.mark.parametrize("shape", [(7, 16, 120, 1, 0), (5, 1, 300, 2, 1), (9, 16, 12, 2, 0), (6, 3, 80, 1, 0),
+                                   (11, 3, 40, 1, 0), (12, 5, 10, 2, 0), (13, 2, 12, 2, 0), (14, 1, 8, 1, 1), (15, 2, 5, 2, 1)])
 def test_random_seek_walk_pcm(side, shape):
     """seeks forward and backward (block index in use) followed by real reads: the PCM bytes and all positions equal
-    the reference's (replayed from tests/golden/ref_answers.json)"""
+    the reference's (replayed from tests/golden/ref_answers.json).  On the device side the shapes of levels 11-15 are the seeks into the
+    stage-wise and the prefix + plane kernels that are held to the reference itself"""
     import numpy as np
     from libacm_amd import synth
     level, rows, nb, ch, wavc = shape

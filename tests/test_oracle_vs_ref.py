@@ -29,10 +29,12 @@ def both(ans, data, **kw):
     assert [so, sha(po.tobytes())] == want[1:]
 
 
-@pytest.mark.parametrize("level", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12])
+@pytest.mark.parametrize("level", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15])
 def test_random_matrix(level):
+    """levels 13-15 have kernels of their own (prefix sweep + plane kernel, acm_tile2 with the shared first pass): the oracle those are
+    held to is held to the reference here, at block heights 1, 2 and 5"""
     ans = RefAnswers("test_oracle_vs_ref::test_random_matrix[%d]" % level)
-    for rows in (1, 2, 3, 16, 17, 64):
+    for rows in (1, 2, 3, 16, 17, 64) if level <= 12 else (1, 2, 5):
         if level >= 11 and rows > 17:
             continue
         for ch in (1, 2):
@@ -41,11 +43,27 @@ def test_random_matrix(level):
     ans.done()
 
 
+@pytest.mark.parametrize("shape", [(0, 4095, 3), (3, 4095, 2), (5, 4095, 3), (9, 4095, 2), (11, 700, 2), (13, 64, 2), (12, 4095, 1)])
+def test_tall_blocks(shape):
+    """(level, rows, blocks): the 12-bit row count at its end, and blocks taller than 64 rows at the upper levels"""
+    level, rows, nb = shape
+    ans = RefAnswers("test_oracle_vs_ref::test_tall_blocks[%s]" % (shape,))
+    both(ans, make_stream(level * 31 + rows, level, rows, nb, channels=1 + (level & 1), cut=3, mix=(rows >> 1) & 1))
+    ans.done()
+
+
 def test_extreme_values_and_stale_table():
     ans = RefAnswers("test_oracle_vs_ref::test_extreme_values_and_stale_table")
     for seed in range(20):
         both(ans, make_stream(3000 + seed, 5, 7, 8, mix=1, allow_out_of_range=1, prime_table=1, pwr_min=0, pwr_max=15,
                               val_min=0, val_max=65535))
+    ans.done()
+    # the same material at the other ends of the level range (a key of its own: the answers above stay as they were recorded)
+    ans = RefAnswers("test_oracle_vs_ref::test_extreme_values_and_stale_table[levels]")
+    for level in (0, 2, 9, 12, 13, 15):
+        for seed in range(6):
+            both(ans, make_stream(3100 + 10 * level + seed, level, 7 if level < 12 else 3, 8 if level < 12 else 4, mix=1, allow_out_of_range=1,
+                                  prime_table=1, pwr_min=0, pwr_max=15, val_min=0, val_max=65535))
     ans.done()
 
 
@@ -75,10 +93,13 @@ def test_bit_flips():
 def test_cascade_formulation_equals_reference_juggle():
     """juggle_block == `level` strided 3-tap FIR stages over the flat sample index,
     history = zeros, chunking irrelevant.  This is the formulation the HIP kernels implement."""
-    ans = RefAnswers("test_oracle_vs_ref::test_cascade_formulation_equals_reference_juggle")
     rng = np.random.default_rng(7)
-    for level in (1, 2, 3, 5, 7, 9, 10):
-        for rows in (1, 3, 16, 17):
+    shapes = [(level, rows) for level in (1, 2, 3, 5, 7, 9, 10) for rows in (1, 3, 16, 17)]
+    # (a key of their own: the answers of the shapes above stay as they were recorded)
+    more = [(level, rows) for level in (4, 6, 8, 11, 12) for rows in (1, 3, 17)] + [(level, rows) for level in (13, 14, 15) for rows in (1, 3)]
+    for key, todo in (("", shapes), ("[more]", more)):
+        ans = RefAnswers("test_oracle_vs_ref::test_cascade_formulation_equals_reference_juggle" + key)
+        for level, rows in todo:
             cols = 1 << level
             nb = 4
             x = rng.integers(-2 ** 31, 2 ** 31 - 1, size=nb * rows * cols, dtype=np.int64).astype(np.int32)
@@ -104,4 +125,4 @@ def test_cascade_formulation_equals_reference_juggle():
                 if k == 0:
                     y = (y + (m % (cols // 2) == 0 if cols >= 2 else 1)).astype(np.uint32)
             assert sha(np.ascontiguousarray(y.view(np.int32)).tobytes()) == want, (level, rows)
-    ans.done()
+        ans.done()
