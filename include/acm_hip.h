@@ -330,6 +330,31 @@ int  acmhip_plan_get_stats(const acmhip_plan *plan, acmhip_plan_stats *out);
 int  acmhip_plan_form_rows(const acmhip_plan *plan, size_t stream, uint64_t *rows);
 
 /*
+ * Fill mode of a device handle: a debugging aid that only tests turn on (bench.py, acmtool and the measurement scripts never do; there
+ * is no environment variable for it).  Off, the default, the library does what it did without it.  The staging arenas of a handle are
+ * grow-only and reused by every batch, window and index call, and the device blocks of destroyed plans are handed to the next plan, so
+ * a call works at the addresses of the one before it - a kernel that skips a column, a table entry nobody wrote or a read-back that
+ * was dropped finds the previous call's bytes, which for a test that decodes the same files again are the right ones.  On:
+ *   - every staging arena is filled over exactly the bytes the call asks of it before the call's first use of it, once per call (a
+ *     second request for the same arena inside one call fills only what it asks beyond the first): device arenas by a memset that has
+ *     ended before the call goes on, pinned ones by memset();
+ *   - every device block a plan is given (recycled or new: tile tables, stream lists, the stage-wise planes, the lead-in sink) is
+ *     zeroed before the plan's tables are queued.  Blocks of live plans are never touched.
+ * The PCM arenas (device and pinned) are filled with 0xA5 bytes - whatever the output type: a float32 call sees 0xA5A5A5A5 words -,
+ * the int16 index arenas with 0x5A bytes (the index 0x5A5A: indices are only ever operands), everything else with zeros: file images,
+ * job tables, column offsets, pair and chunk tables, byte-plane and packed blobs, block headers and marks are places, classes, offsets
+ * and loop bounds, read past what a call wrote by design (acmhip_plan_bind_mform), and zero is a valid one in each.  The mode can make
+ * a comparison fail; it cannot make a kernel read from anywhere it could not read from before.
+ * Returns the previous state (0 / 1), or ACMHIP_ERR_ARG.  Waits for a batch call that is using the handle.
+ */
+int  acmhip_device_set_fill(acmhip_device *dev, int on);
+/* Staging arena `slot` (0, 1, ... until ACMHIP_ERR_ARG) of the handle, for tests of the above; every out pointer may be NULL.  *name: a
+ * static string ("D_IDX", "H_PCM", ...); *ptr: where it is now (NULL: never allocated; device memory unless *is_host: pinned); *bytes:
+ * what the last call that held the handle's arenas asked of it (0: that call did not use it); *fill: the byte the fill mode puts there.
+ * Not while a call is using the handle. */
+int  acmhip_device_arena_info(acmhip_device *dev, int slot, const char **name, void **ptr, size_t *bytes, int *is_host, int *fill);
+
+/*
  * Time `reps` back-to-back acmhip_plan_launch calls with HIP events recorded on
  * the launch stream; *ms_total receives the elapsed milliseconds of the whole
  * bracket (device time, includes launch gaps).  Blocks until done.

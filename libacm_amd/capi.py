@@ -20,6 +20,12 @@ PLAN_LEAN_ALWAYS, PLAN_NO_LEAN, PLAN_FORCE_HALO, PLAN_FORCE_CARRY = 0x400, 0x800
 # ACM_BATCH_RANGES in the environment set these instead: the shipped library reads no kernel-selection switch from the environment)
 PLAN_EXTRA = 0
 BATCH_EXTRA = 0
+# test plumbing: True makes every helper below that works on a Device (Plan, synth, the batch, window and index calls) turn the handle's
+# fill mode on first (acmhip_device_set_fill: reused arenas and recycled plan blocks start every call filled, not with the previous
+# call's bytes), and synth poison its PCM buffer before it launches.  Off by default: bench.py and the measurement scripts run the library as shipped;
+# tests/helpers.py turns it on for the GPU tests
+FILL_MODE = False
+POISON16, POISON32 = 0xA5A5, 0xFFFFFFFF         # what synth leaves in a PCM word no kernel wrote: 0xA5 bytes (16-bit formats), 0xFF bytes (float32)
 
 
 def batch_ranges(n):
@@ -157,6 +163,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
+    "acmhip_device_set_fill", "acmhip_device_arena_info",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -194,6 +201,8 @@ def lib():
     L.acmhip_device_sync.argtypes = [vp]
     L.acmhip_device_stream.argtypes = [vp]
     L.acmhip_device_stream.restype = vp
+    L.acmhip_device_set_fill.argtypes = [vp, C.c_int]
+    L.acmhip_device_arena_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.acmhip_malloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.acmhip_free.argtypes = [vp, vp]
     L.acmhip_host_alloc.argtypes = [sz, C.POINTER(vp)]
@@ -582,6 +591,7 @@ def unpack_tile(level, chunks, blob, entry):
 class Device:
     def __init__(self, ordinal=0, hip_stream=None):
         self.h = C.c_void_p()
+        self.fill = False               # the handle's fill mode as set_fill left it
         rc = lib().acmhip_device_open(ordinal, hip_stream, C.byref(self.h))
         if rc != 0:
             self.h = None
@@ -592,6 +602,24 @@ class Device:
         if self.h:
             lib().acmhip_device_close(self.h)
             self.h = None
+
+    def set_fill(self, on):
+        """acmhip_device_set_fill: the handle's fill mode on / off -> its previous state"""
+        was = lib().acmhip_device_set_fill(self.h, 1 if on else 0)
+        if was < 0:
+            _check(was, "acmhip_device_set_fill")
+        self.fill = bool(on)
+        return bool(was)
+
+    def arena_info(self):
+        """acmhip_device_arena_info over every staging arena of the handle -> {name: (slot, ptr or None, bytes the last call asked of it,
+        is_host, fill byte)}"""
+        out, slot = {}, 0
+        name, ptr, nbytes, host, fill = C.c_char_p(), C.c_void_p(), C.c_size_t(), C.c_int(), C.c_int()
+        while lib().acmhip_device_arena_info(self.h, slot, C.byref(name), C.byref(ptr), C.byref(nbytes), C.byref(host), C.byref(fill)) == 0:
+            out[name.value.decode()] = (slot, ptr.value, int(nbytes.value), bool(host.value), int(fill.value))
+            slot += 1
+        return out
 
     def __enter__(self):
         return self
@@ -625,10 +653,17 @@ class Device:
         _check(lib().acmhip_memset(self.h, dptr, byte, nbytes), "acmhip_memset")
 
 
+def _fill(dev):
+    """FILL_MODE: the handle's fill mode goes on with the first helper that is given the handle"""
+    if FILL_MODE and dev is not None and getattr(dev, "h", None) and not getattr(dev, "fill", False):
+        dev.set_fill(True)
+
+
 class Plan:
     def __init__(self, dev, descs, patches=None, flags=PLAN_AUTO, packed=None):
         """packed: optional list of PackedStream, one per desc (ntiles 0 = that stream has no packed form)"""
         self.dev = dev
+        _fill(dev)
         flags |= PLAN_EXTRA
         n = len(descs)
         arr = (StreamDesc * max(n, 1))(*descs)
@@ -727,12 +762,14 @@ class Arena:
 
 
 def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return_stats=False, patch_subset=None, packed=False, mform=False,
-          f32=False):
+          f32=False, omit=()):
     """Upload staged streams, run the hot path once, return one PCM array (uint16 view of the bytes) per stream.
     patch_subset (tests): keep only these entries of the batch's H1 patch list.
     packed: stage the packed form too (acmhip_pack_tiles) and bind it: whole tiles from row 0 are read from it.
     mform: the same with the byte-plane form (acmhip_mform_rows) and the matrix-core build of the lean kernel.
-    f32: acmhip_plan_launch_f32 instead (fmt is ignored): one float32 array per stream."""
+    f32: acmhip_plan_launch_f32 instead (fmt is ignored): one float32 array per stream.
+    omit (tests): streams that keep their place in the three arenas but are left out of the plan's descriptor list; what comes back
+    for them is whatever the launch found in their PCM slot."""
     ar = Arena(staged_list, windows)
     if patch_subset is not None and ar.patch_list:
         ar.patch_list = [ar.patch_list[k] for k in patch_subset]
@@ -741,6 +778,8 @@ def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return
     d_hdr = dev.malloc(ar.hdr.nbytes)
     d_pcm = dev.malloc(ar.pcm_words * (4 if f32 else 2))
     try:
+        if FILL_MODE:                   # whatever the allocator handed back (the PCM of the synth before, as a rule) is gone before the launch
+            dev.memset(d_pcm, 0xFF if f32 else 0xA5, ar.pcm_words * (4 if f32 else 2))
         dev.upload(d_idx, ar.idx)
         dev.upload(d_hdr, ar.hdr)
         pk, pk_ptrs = None, ()
@@ -756,7 +795,14 @@ def synth(dev, staged_list, fmt=FMT_S16LE, flags=PLAN_AUTO, windows=None, return
             for i in patched:
                 pk.streams[i].ntiles = 0
             pk_ptrs = pk.upload(dev)
-        plan = Plan(dev, ar.descs, ar.patches, flags, packed=pk.streams if pk else None)
+        descs, patches, forms = ar.descs, ar.patches, pk.streams if pk else None
+        if omit:
+            keep = [i for i in range(len(descs)) if i not in omit]
+            at = {i: k for k, i in enumerate(keep)}
+            left = [Patch(p.sample, p.value, at[p.stream]) for p in ar.patch_list if p.stream in at]
+            descs, patches = [descs[i] for i in keep], (Patch * len(left))(*left) if left else None
+            forms = [forms[i] for i in keep] if forms else None
+        plan = Plan(dev, descs, patches, flags, packed=forms)
         if pk and mform:
             plan.bind_mform(*pk_ptrs)
         elif pk:
@@ -857,6 +903,7 @@ def batch_decode(dev, files, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | batch_flags | (BATCH_PCM_PINNED if pinned else 0) |
                      (BATCH_STAGE_PACKED if packed else 0) | (BATCH_STAGE_BYTEPLANE if byteplane else 0) | (BATCH_STAGE_INT16 if byteplane is False else 0))
     tm = BatchTiming()
+    _fill(dev)
     pre = C.c_void_p()
     ix = _IndexOut(items, n, force_chans) if index else None
     try:
@@ -904,6 +951,7 @@ def batch_decode_device(dev, files, d_pcm, d_pcm_words, force_chans=0, fmt=FMT_S
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_EXTRA | batch_flags | (BATCH_PCM_F32 if f32 else 0),
                      d_pcm, d_pcm_words)
     tm = BatchTiming()
+    _fill(dev)
     n = len(files)
     ix = _IndexOut(items, n, force_chans) if index else None
     if ix is not None:
@@ -977,6 +1025,7 @@ def batch_decode_windows(dev, files, index, windows, force_chans=0, fmt=FMT_S16L
         wins[k].pcm_cap = cap
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, 0)
     tm = WindowTiming()
+    _fill(dev)
     _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
     return [(int(wins[k].status), int(wins[k].words), outs[k][:min(int(wins[k].words), int(wins[k].pcm_cap))]) for k in range(nw)], tm
 
@@ -990,6 +1039,7 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
     nw = len(windows)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, BATCH_PCM_F32 if f32 else 0, d_pcm, d_pcm_words)
     tm = WindowTiming()
+    _fill(dev)
     _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
     return ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], [int(wins[k].dev_off) for k in range(nw)],
             [(int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)], tm)
@@ -1017,6 +1067,7 @@ def batch_index_files(dev, files, parse=PARSE_AUTO, max_group_bytes=0, force_cha
         out[k].max_blocks = int(need[k])
     opts = IndexOpts(force_chans, threads, parse, 0, max_group_bytes)
     tm = IndexTiming()
+    _fill(dev)
     _check(lib().acm_batch_index_files(dev.h if dev is not None else None, items, n, out, C.byref(opts), C.byref(tm)), "acm_batch_index_files")
     res = []
     for k in range(n):

@@ -66,6 +66,13 @@ struct acmhip_device {
 	void *arena[ACM_ARENA_SLOTS] = {};
 	size_t arena_cap[ACM_ARENA_SLOTS] = {};
 	std::mutex arena_mutex;
+	/* A call's hold on the arenas is an epoch (acmhip_arena_lock); arena_asked[slot] = the bytes the call of epoch arena_epoch_of[slot]
+	 * asked of the slot: what acmhip_device_arena_info reports, and with the fill mode on (acmhip_device_set_fill) what has been filled
+	 * for that call */
+	bool fill = false;
+	uint64_t arena_epoch = 0;
+	uint64_t arena_epoch_of[ACM_ARENA_SLOTS] = {};
+	size_t arena_asked[ACM_ARENA_SLOTS] = {};
 	/* device blocks of destroyed plans (tile tables, planes, the lead-in sink), kept for the next plan: hipMalloc / hipFree
 	 * synchronise the whole device - every stream of the process, an RCCL transfer in flight included - and a batch builds and
 	 * drops a plan per chunk */
@@ -226,6 +233,97 @@ extern "C" void acmhip_device_close(acmhip_device *dev)
 	delete dev;
 }
 
+namespace {
+
+const char *const g_slot_names[ACM_ARENA_SLOTS] = {
+	"H_IDX", "H_HDR", "H_PCM", "H_FILES", "H_JOBS", "H_PKBLOB", "H_PKCHUNK",
+	"D_IDX", "D_HDR", "D_PCM", "D_FILES", "D_COLPOS", "D_JOBS", "D_STAGE",
+	"D_PKBLOB", "D_PKCHUNK", "D_BLKOFF", "D_MARKS", "H_MARKS",
+};
+
+/* What the fill mode leaves in a slot (acmhip_device_set_fill):
+ *   D_PCM, H_PCM   0xA5 - output only: nothing reads a sample back, and the pattern is the one the arena-contract tests poison with;
+ *   D_IDX, H_IDX   0x5A (index 0x5A5A) - the staged int16 indices are operands and nothing else: the parser's column kernel and the host
+ *                  stagers only store them, the synthesis kernels multiply them by the block's val (value = idx * val) and the packers
+ *                  compare them with class bounds; no kernel forms an address, an LDS offset or a trip count from one, so a row nobody
+ *                  staged decodes to PCM that is visibly wrong instead of to silence;
+ *   the rest       zero.  The file and stage arenas feed the bit reader, whose codes become column lengths and loop bounds, and the
+ *                  readers count on zeros behind a file where a stripe or a slot ends; jobs, results and flags, colpos, blkoff, the
+ *                  pair tables and chunk tables, the blobs (their first bytes name LDS places) and the marks are offsets, classes and
+ *                  bounds, and they are read past what a call wrote (32 pair-table entries, 64 arena bytes, entries two chunks ahead):
+ *                  zero is a valid place, class, offset and bound in every one of them; the headers (val, pwr) go with them */
+int fill_byte(int slot)
+{
+	switch (slot) {
+	case ACM_ARENA_D_PCM:
+	case ACM_ARENA_H_PCM:
+		return 0xA5;
+	case ACM_ARENA_D_IDX:
+	case ACM_ARENA_H_IDX:
+		return 0x5A;
+	default:
+		return 0;
+	}
+}
+
+#define ACM_FILL_TRY(call) do { const int rc_ = (call); if (rc_ != ACMHIP_OK) return rc_; } while (0)
+
+/* The bytes this call (epoch) has asked of the slot so far; in fill mode bytes [that, bytes) get the slot's fill first - the first
+ * acmhip_arena_get of a call fills all it asks for, a second one of the same slot only what it asks beyond that (live data is never
+ * wiped).  Device memory: a memset on the device stream that has ended when this returns - the streams of the call that asks are all
+ * idle until then */
+int note_slot(acmhip_device *dev, int slot, size_t bytes)
+{
+	if (dev->arena_epoch_of[slot] != dev->arena_epoch) {
+		dev->arena_epoch_of[slot] = dev->arena_epoch;
+		dev->arena_asked[slot] = 0;
+	}
+	const size_t have = dev->arena_asked[slot];
+	if (bytes <= have)
+		return ACMHIP_OK;
+	if (dev->fill) {
+		uint8_t *at = static_cast<uint8_t *>(dev->arena[slot]) + have;
+		if (acm_arena_is_host(slot)) {
+			memset(at, fill_byte(slot), bytes - have);
+		} else {
+			HIPTRY(hipSetDevice(dev->ordinal));
+			HIPTRY(hipMemsetAsync(at, fill_byte(slot), bytes - have, dev->stream));
+			HIPTRY(hipStreamSynchronize(dev->stream));
+		}
+	}
+	dev->arena_asked[slot] = bytes;
+	return ACMHIP_OK;
+}
+
+} // namespace
+
+extern "C" int acmhip_device_set_fill(acmhip_device *dev, int on)
+{
+	if (!dev)
+		return ACMHIP_ERR_ARG;
+	std::lock_guard<std::mutex> g(dev->arena_mutex);
+	const int was = dev->fill ? 1 : 0;
+	dev->fill = on != 0;
+	return was;
+}
+
+extern "C" int acmhip_device_arena_info(acmhip_device *dev, int slot, const char **name, void **ptr, size_t *bytes, int *is_host, int *fill)
+{
+	if (!dev || slot < 0 || slot >= ACM_ARENA_SLOTS)
+		return ACMHIP_ERR_ARG;
+	if (name)
+		*name = g_slot_names[slot];
+	if (ptr)
+		*ptr = dev->arena[slot];
+	if (bytes)
+		*bytes = dev->arena_epoch_of[slot] == dev->arena_epoch ? dev->arena_asked[slot] : 0;
+	if (is_host)
+		*is_host = acm_arena_is_host(slot);
+	if (fill)
+		*fill = fill_byte(slot);
+	return ACMHIP_OK;
+}
+
 extern "C" int acmhip_arena_get(acmhip_device *dev, int slot, size_t bytes, void **out)
 {
 	if (!dev || slot < 0 || slot >= ACM_ARENA_SLOTS || !out)
@@ -249,7 +347,9 @@ extern "C" int acmhip_arena_get(acmhip_device *dev, int slot, size_t bytes, void
 		else
 			HIPTRY(hipMalloc(&dev->arena[slot], want));
 		dev->arena_cap[slot] = want;
+		dev->arena_asked[slot] = 0;
 	}
+	ACM_FILL_TRY(note_slot(dev, slot, bytes));
 	*out = dev->arena[slot];
 	return ACMHIP_OK;
 }
@@ -283,8 +383,10 @@ extern "C" int acmhip_report_hip(int hip_error, const char *what)
 
 extern "C" void acmhip_arena_lock(acmhip_device *dev)
 {
-	if (dev)
+	if (dev) {
 		dev->arena_mutex.lock();
+		dev->arena_epoch++;
+	}
 }
 
 extern "C" void acmhip_arena_unlock(acmhip_device *dev)
@@ -374,6 +476,19 @@ extern "C" int acmhip_memset(acmhip_device *dev, void *dptr, int byte, size_t by
 
 namespace {
 
+/* fill mode: a block on its way into a plan - one a destroyed plan handed back (idle: acmhip_plan_destroy waits for its plan's
+ * launches and uploads first), or a fresh one - is zeroed on the upload stream, in front of the tables that are queued there next; a
+ * plan's launches wait for that stream (upload_done).  Tables, stream lists, planes and the sink hold offsets, places and bounds: zero
+ * is a valid one everywhere.  Blocks of live plans are not on the spare list and are never touched */
+int fill_block(acmhip_device *dev, void *p, size_t bytes)
+{
+	std::lock_guard<std::mutex> g(dev->upload_mutex);
+	if (!dev->upload)
+		HIPTRY(hipStreamCreateWithFlags(&dev->upload, hipStreamNonBlocking));
+	HIPTRY(hipMemsetAsync(p, 0, bytes, dev->upload));
+	return ACMHIP_OK;
+}
+
 /* device memory for a plan: a spare block of a destroyed plan if one fits (no more than twice the size), else hipMalloc */
 int plan_malloc(acmhip_plan *pl, void **out, size_t bytes)
 {
@@ -394,14 +509,14 @@ int plan_malloc(acmhip_plan *pl, void **out, size_t bytes)
 			dev->spare_bytes -= b.bytes;
 			pl->blocks.push_back(b);
 			*out = b.ptr;
-			return ACMHIP_OK;
+			return dev->fill ? fill_block(dev, b.ptr, b.bytes) : ACMHIP_OK;
 		}
 	}
 	void *p = nullptr;
 	HIPTRY(hipMalloc(&p, bytes));
 	pl->blocks.push_back(acmhip_device::Block{ p, bytes });
 	*out = p;
-	return ACMHIP_OK;
+	return dev->fill ? fill_block(dev, p, bytes) : ACMHIP_OK;
 }
 
 template <typename T>

@@ -5,6 +5,19 @@ import oracle_api as O
 from libacm_amd import capi, synth
 
 
+# The GPU tests never compare against memory a previous call wrote: every module of them imports this one, and with the switch on the capi
+# helpers turn the fill mode of whatever device handle they are given on (acmhip_device_set_fill: reused staging arenas and recycled plan
+# blocks start each call filled) and capi.synth poisons its PCM buffer.  bench.py and the measurement scripts under profiles/ do not
+# import this module (the fuzzers there do: they are checks like these)
+capi.FILL_MODE = True
+
+
+def poison_pcm(dev, d_pcm, words, f32=False):
+    """what a test that launches a plan into a PCM buffer of its own does before EVERY launch: 0xA5 bytes under `words` 16-bit samples,
+    0xFF bytes under `words` floats (capi.POISON16 / POISON32 per word) - a sample no kernel wrote is then not the previous launch's"""
+    dev.memset(d_pcm, 0xFF if f32 else 0xA5, words * (4 if f32 else 2))
+
+
 def make_stream(seed, level, rows, nblocks, channels=1, cut=0, **kw):
     """One synthetic file; `cut` trims total_values so it is not block aligned."""
     total = max(1, nblocks * rows * (1 << level) - cut)

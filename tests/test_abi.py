@@ -93,3 +93,19 @@ def test_oracle_is_not_linked_into_the_product():
     """the shipped library must not contain or reference the test oracle"""
     blob = open(capi.lib_path(), "rb").read()
     assert b"acmo_" not in blob and b"acm_oracle" not in blob and b"libacm_ref" not in blob
+
+
+def test_gpu_tests_run_with_the_fill_mode_on():
+    """capi.FILL_MODE is off as the module is written (bench.py and the measurement scripts run the library as shipped) and on once tests/helpers.py has
+    been imported, which every module of GPU tests does: no GPU test compares against memory a previous call wrote"""
+    import helpers  # noqa: F401
+    assert capi.FILL_MODE is True
+    src = open(os.path.join(ROOT, "libacm_amd", "capi.py")).read()
+    assert re.search(r"^FILL_MODE = False$", src, flags=re.M)
+    tests = os.path.join(ROOT, "tests")
+    gpu_modules = [f for f in sorted(os.listdir(tests)) if re.match(r"test_gpu_.*\.py$", f)] + ["test_plan_api.py", "test_distributed.py"]
+    assert len(gpu_modules) >= 15
+    for f in gpu_modules:
+        assert re.search(r"^(import helpers|from helpers import )", open(os.path.join(tests, f)).read(), flags=re.M), f
+    for f in ("bench.py", os.path.join("libacm_amd", "batch.py"), os.path.join("libacm_amd", "workload.py")):
+        assert "FILL_MODE" not in open(os.path.join(ROOT, f)).read() and "helpers" not in open(os.path.join(ROOT, f)).read(), f

@@ -5,7 +5,7 @@ the host stager (acmhip_mform_rows, acm_pack.cpp) against the CPU oracle, bit-ex
 import numpy as np
 import pytest
 
-from helpers import fmt_args, make_stream, oracle_pcm, plan_rows
+from helpers import fmt_args, make_stream, oracle_pcm, plan_rows, poison_pcm
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -240,7 +240,7 @@ def test_byteplane_and_int16_launches_of_one_plan_agree(dev, force_k2):
     outs = []
     for bind in (d_mf, (None, None), d_mf):
         plan.bind_mform(*bind)
-        dev.upload(d_pcm, np.zeros(ar.pcm_words, dtype=np.uint16))
+        poison_pcm(dev, d_pcm, ar.pcm_words)
         plan.launch(d_idx, d_hdr, d_pcm)
         o = np.zeros(ar.pcm_words, dtype=np.uint16)
         dev.download(o, d_pcm)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import damaged_streams as D
+import helpers  # noqa: F401  (GPU tests run with the fill mode on: helpers sets the switch)
 import oracle_api as O
 from decode_index import decode_both, index_info
 from libacm_amd import capi

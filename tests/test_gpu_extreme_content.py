@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import extreme_content as X
+import helpers  # noqa: F401  (GPU tests run with the fill mode on: helpers sets the switch)
 from libacm_amd import capi
 from test_gpu_pcm_f32 import f32_bits, run_f32
 

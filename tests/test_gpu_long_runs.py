@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import helpers  # noqa: F401  (GPU tests run with the fill mode on: helpers sets the switch)
 import oracle_api as O
 from libacm_amd import capi, synth, workload
 

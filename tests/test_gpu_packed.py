@@ -5,7 +5,7 @@
 import numpy as np
 import pytest
 
-from helpers import fmt_args, make_stream, oracle_pcm
+from helpers import fmt_args, make_stream, oracle_pcm, poison_pcm
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -94,7 +94,7 @@ def test_packed_and_int16_launches_of_one_plan_agree(dev, force_k2):
     outs = []
     for bind in (ptrs, (None, None), ptrs):
         plan.bind_packed(*bind)
-        dev.upload(d_pcm, np.zeros(ar.pcm_words, dtype=np.uint16))
+        poison_pcm(dev, d_pcm, ar.pcm_words)
         plan.launch(d_idx, d_hdr, d_pcm)
         o = np.zeros(ar.pcm_words, dtype=np.uint16)
         dev.download(o, d_pcm)

@@ -6,7 +6,7 @@ Bit-exact is the bar (integer path).  Reference behaviour cited: /root/reference
 import numpy as np
 import pytest
 
-from helpers import fmt_args, make_stream, oracle_pcm
+from helpers import fmt_args, make_stream, oracle_pcm, poison_pcm
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -331,6 +331,7 @@ def test_corpus_shaped_batch(dev):
     bufs = b.upload(dev)
     plan = capi.Plan(dev, b.descs)
     assert plan.stats().launches in (3, 6) and plan.stats().fused_streams == len(shapes)
+    poison_pcm(dev, bufs[2], b.pcm_words)
     plan.launch(*bufs)
     out = np.zeros(b.pcm_words, dtype=np.uint16)
     dev.download(out, bufs[2])
@@ -360,6 +361,7 @@ def test_many_short_streams_stress_shape(dev):
     dev.free(d_pcm0)
     d_pcm = dev.malloc(len(descs) * pad * 2)
     plan = capi.Plan(dev, descs)
+    poison_pcm(dev, d_pcm, len(descs) * pad)
     plan.launch(d_idx, d_hdr, d_pcm)
     out = np.zeros(len(descs) * pad, dtype=np.uint16)
     dev.download(out, d_pcm)

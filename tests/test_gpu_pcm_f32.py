@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import make_stream, oracle_pcm
+from helpers import make_stream, oracle_pcm, poison_pcm
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -204,11 +204,13 @@ def test_packed_form_is_refused(dev):
         with pytest.raises(capi.AcmHipError):
             plan.launch_f32(d_idx, d_hdr, d_pcm)
         assert "packed" in capi.lib().acmhip_last_error().decode()
+        poison_pcm(dev, d_pcm, ar.pcm_words)
         plan.launch(d_idx, d_hdr, d_pcm)
         h = np.empty(ar.pcm_words, np.uint16)
         dev.download(h, d_pcm)
         assert np.array_equal(h[:ar.descs[0].n_emit], oracle_pcm(f)[0])
         plan.bind_packed(None, None)            # unbound: the float launch runs
+        poison_pcm(dev, d_pcm, ar.pcm_words, f32=True)
         plan.launch_f32(d_idx, d_hdr, d_pcm)
         h32 = np.empty(ar.pcm_words, np.uint32)
         dev.download(h32, d_pcm)

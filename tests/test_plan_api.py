@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import make_stream, oracle_pcm
+from helpers import make_stream, oracle_pcm, poison_pcm
 from libacm_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +53,7 @@ def test_plan_is_reusable_and_format_is_per_launch(dev):
     plan = capi.Plan(dev, ar.descs)
     out = np.zeros(ar.pcm_words, dtype=np.uint16)
     for fmt in (0, 1, 2, 3, 0):
+        poison_pcm(dev, d_pcm, ar.pcm_words)
         plan.launch(d_idx, d_hdr, d_pcm, fmt)
         dev.download(out, d_pcm)
         want, _ = oracle_pcm(f, 0, fmt & 1, 0 if fmt & 2 else 1)
@@ -90,6 +91,7 @@ def test_more_streams_than_grid_y(dev):
     dev.upload(d_idx, idx)
     dev.upload(d_hdr, s.hdr)
     plan = capi.Plan(dev, descs)
+    poison_pcm(dev, d_pcm, n * per)
     plan.launch(d_idx, d_hdr, d_pcm)
     out = np.zeros(n * per, dtype=np.uint16)
     dev.download(out, d_pcm)
