@@ -622,6 +622,46 @@ int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, s
 			      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, acm_window_timing *timing);
 
 /* ------------------------------------------------------------------------
+ * Dense crop batches (csrc/acm_batch_windows.cpp over csrc/acm_dense_layout.cpp, kernel: csrc/acm_dense.hip): the windows of
+ * acm_batch_decode_windows as ONE tensor of equally spaced, zero-padded rows - what a training step consumes - instead of slots at
+ * arbitrary 2-byte alignments with ragged lengths and interleaved channels.
+ *
+ * The output is opts->d_pcm (device memory, required): nwin rows of R = frames * channels samples, row k at sample k * R; int16, or
+ * float32 with ACM_BATCH_PCM_F32 (the int16 sample times 2^-15 exactly, as acmhip_plan_launch_f32 writes it).  opts->d_pcm_words
+ * counts samples of the output type and is at least nwin * R.  With `whole` and `words` as acm_batch_decode_windows defines them,
+ * element e of row k is whole[first_word + j] where j < words and zero (int16 0, float +0.0) elsewhere;
+ *   interleaved (default)   j = e:                          the row is [frames][channels]
+ *   ACM_DENSE_PLANAR        j = (e % frames) * channels + e / frames: the row is [channels][frames]
+ * Every element of all nwin rows is written, the rows of windows that deliver nothing included; nothing outside [0, nwin * R) is.
+ *
+ * wins[k].words and .status are what acm_batch_decode_windows reports for the same window - also for one the host stager turns
+ * away during the call (a stale or damaged index): its error status, a row of zeros.  dev_off = slot_off = k * R, slot_words = R.
+ * A window whose item has, in effect (after force_chans), another channel count than dense->channels is turned away softly, as a
+ * file that is not ACM is: words = 0, status = ACMHIP_ERR_ARG, a row of zeros; nothing of it is parsed, uploaded or synthesised
+ * (timing->blocks_parsed shows it) and the call does not fail.
+ *
+ * ACMHIP_ERR_ARG before anything is written: dense == NULL, frames == 0, channels other than 1 or 2, unknown dense->flags;
+ * opts->d_pcm == NULL or too small; a fmt other than ACMHIP_FMT_S16LE (padding has no single meaning in the other writers);
+ * prestaged or ACM_BATCH_STAGE_PACKED; a window with max_words > R, or with first_word or max_words that is no multiple of
+ * channels.  dev == NULL: ACMHIP_ERR_NO_DEVICE.
+ *
+ * The windows are synthesised as by acm_batch_decode_windows - one plan over int16 rows, float output too - into an arena of the
+ * handle's own; nothing is read back.  One launch of acm_dense_rows behind the plan's, on the same stream, reads a row table of 16
+ * bytes per window and copies, splits the channels, widens and pads; the call returns with the stream drained.
+ * timing->kernel_s covers synthesis and that launch.
+ * ---------------------------------------------------------------------- */
+#define ACM_DENSE_PLANAR 1u              /* row k is [channels][frames]; default [frames][channels] */
+typedef struct acm_dense_opts {
+	uint64_t frames;                 /* T >= 1 */
+	uint32_t channels;               /* C: 1 or 2 (all an ACM header can say) */
+	uint32_t flags;                  /* ACM_DENSE_* */
+} acm_dense_opts;
+
+int  acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+				    acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts,
+				    const acm_dense_opts *dense, acm_window_timing *timing);
+
+/* ------------------------------------------------------------------------
  * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs
  * before its first crop.  acm_index_file parses a whole file to get it, decoding every filler index and dropping it; the device
  * only WALKS the stream (acm_index_scan_wave, csrc/acm_parse.hip: one stream per wavefront, the walk of acm_batch_decode's device

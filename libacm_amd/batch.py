@@ -180,6 +180,32 @@ class GpuDecoder:
             self.dev, files, index, windows, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
         return d_pcm, offsets, words, statuses
 
+    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None):
+        """Random-access crops as one batch tensor: windows = (file_no, first_frame, n_frames) triples with n_frames <= frames, index as
+        for crop().  -> (batch, frames_delivered, statuses): batch is a tensor of this decoder's dtype shaped [N, channels, frames]
+        (planar) or [N, frames, channels], row k the crop's frames with zeros behind them - also where a window is clipped by the end of
+        its stream, starts behind it, or is turned away: a file that is not ACM, a stale index, a file whose channel count is not
+        `channels` (status capi.ERR_ARG).  One copy kernel behind the synthesis lays the rows out (acm_batch_decode_windows_dense); no
+        per-window slicing on the torch side.  out: a contiguous tensor of this decoder's dtype with at least N * channels * frames
+        elements is written into (the batch is a view of its first elements) instead of a new one, as in crop()."""
+        torch = self.torch
+        files = [_load(f) for f in files]
+        if index is None:
+            index = self.build_index(files)
+        n = len(windows)
+        shape = (n, channels, frames) if planar else (n, frames, channels)
+        need = n * channels * frames
+        if out is not None and out.dtype != self.dtype:
+            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
+        fits = out is not None and out.numel() >= need and out.is_contiguous()
+        d_pcm = out if fits else torch.empty(max(need, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
+        torch.cuda.current_stream().synchronize()
+        statuses, words, self.timing = capi.batch_decode_windows_dense(
+            self.dev, files, index, [(f, first * channels, count * channels) for f, first, count in windows], d_pcm.data_ptr(), d_pcm.numel(),
+            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
+        # the call returns with its stream drained: the batch is complete and visible to torch's streams
+        return d_pcm.reshape(-1)[:need].view(shape), [w // channels for w in words], statuses
+
 
 def _trace(trace, *ev):
     if trace is not None:

@@ -135,6 +135,13 @@ class WindowTiming(C.Structure):
                 ("h2d_bytes", C.c_uint64), ("blocks_parsed", C.c_uint64)]
 
 
+class DenseOpts(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("channels", C.c_uint32), ("flags", C.c_uint32)]
+
+
+DENSE_PLANAR = 1
+
+
 class BatchIndexOut(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("max_blocks", C.c_size_t), ("blocks", C.c_uint32), ("end_status", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_uint32)]
@@ -161,7 +168,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_plan_create_packed", "acmhip_plan_bind_packed",
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
-    "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows",
+    "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info",
 ]
@@ -257,6 +264,8 @@ def lib():
     L.acm_batch_window_pcm_words.restype = C.c_uint64
     L.acm_batch_decode_windows.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
                                            C.POINTER(BatchOpts), C.POINTER(WindowTiming)]
+    L.acm_batch_decode_windows_dense.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                                 C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(WindowTiming)]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -1043,6 +1052,28 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
     _check(lib().acm_batch_decode_windows(dev.h, items, len(files), ix, wins, nw, C.byref(opts), C.byref(tm)), "acm_batch_decode_windows")
     return ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], [int(wins[k].dev_off) for k in range(nw)],
             [(int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)], tm)
+
+
+def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
+                               fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
+                               check=True):
+    """acm_batch_decode_windows_dense: the windows as len(windows) rows of frames * channels samples in d_pcm (int16, or float32 with
+    f32=True), row k at sample k * frames * channels - interleaved, or a plane per channel with planar=True - zeros behind what a window
+    delivers.  Returns (statuses, words, WindowTiming).  check=False (tests of the refusals): the return code instead of an exception, as a
+    fourth element; dense_flags: the raw acm_dense_opts.flags instead of planar; frames None: no acm_dense_opts at all; dev None: the call's
+    own answer to a missing handle."""
+    bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
+    nw = len(windows)
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
+    dense = None if frames is None else DenseOpts(frames, channels, (DENSE_PLANAR if planar else 0) if dense_flags is None else dense_flags)
+    tm = WindowTiming()
+    _fill(dev)
+    rc = lib().acm_batch_decode_windows_dense(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
+                                              C.byref(dense) if dense is not None else None, C.byref(tm))
+    if check:
+        _check(rc, "acm_batch_decode_windows_dense")
+    res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], tm)
+    return res if check else res + (rc,)
 
 
 # --------------------------------------------------------------------------- the block index of a batch

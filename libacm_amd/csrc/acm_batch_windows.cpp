@@ -14,6 +14,10 @@
  * Which blocks, where everything sits and who parses is acm_window_layout.cpp's, decided before the device is touched; this file
  * drives the device over that layout.  The call is a straight line, not acm_batch.cpp's pipeline: a batch of windows is small by
  * construction.
+ *
+ * acm_batch_decode_windows_dense is the same run with another end: the windows are synthesised into the handle's own PCM arena, nothing
+ * is read back, and one launch of acm_dense_rows (acm_dense.hip) lays them out as the rows of the caller's tensor.  What that call
+ * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -21,6 +25,7 @@
 #include <vector>
 
 #include "acm_batch_common.h"
+#include "acm_dense_layout.h"
 #include "acm_device.h"
 #include "acm_hip.h"
 #include "acm_stage.h"
@@ -36,8 +41,9 @@ using namespace acmbatch;
 class WinRun {
 public:
 	WinRun(acmhip_device *dev_, const acm_batch_item *items_, acm_batch_window *wins_, const acm_batch_opts &opts_,
-	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_)
-		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_),
+	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseLayout *dense_ = nullptr,
+	       void *dense_out_ = nullptr)
+		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), dense(dense_), dense_out(dense_out_),
 		  st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
 		  pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
 	{
@@ -53,6 +59,7 @@ public:
 	int parse_on_host();
 	int parse_on_device();
 	int synthesise_and_deliver();
+	int synthesise_and_gather();
 
 private:
 	/* what a call changes about a window: the host stager rejects it, or finds H1 patches */
@@ -64,6 +71,9 @@ private:
 	void stage_one(size_t k);
 	void stage_on_host(const std::vector<size_t> &ids);
 	int upload_slices(const std::vector<size_t> &ids);
+	void collect(PlanStreams &ps);
+	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, and behind them a dense call's row table */
+	size_t jobs_bytes() const { return dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes(); }
 
 	ArenaLock lock;
 	acmhip_device *const dev;
@@ -74,6 +84,8 @@ private:
 	const WindowLayout &L;
 	Pool &pool;
 	acm_window_timing &tm;
+	const DenseLayout *const dense;         /* a dense call (then opts are its inner ones: int16 rows, no caller memory), else null */
+	void *const dense_out;                  /* ... and its output tensor */
 	const hipStream_t st;
 	const bool out_f32, keep_on_device;
 	const size_t pcm_unit;
@@ -98,7 +110,7 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 			ACM_TRY(host_arenas(dev, L.idx_total, L.hdr_total, &h_idx, &h_hdr));
 		if (keep_on_device) {
 			d_pcm = static_cast<int16_t *>(opts.d_pcm);
-		} else {
+		} else if (!dense) {
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, L.pcm_total * pcm_unit, (void **)&d_pcm));
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_PCM, L.pcm_total * pcm_unit, (void **)&h_pcm));
 		}
@@ -106,11 +118,16 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_FILES, L.files_total, (void **)&h_files));
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_FILES, L.files_total, (void **)&d_files));
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_COLPOS, L.cols_total * sizeof(uint32_t), (void **)&d_colpos));
-			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, L.job_arena_bytes(), (void **)&h_jobs));
-			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, L.job_arena_bytes(), (void **)&d_jobs));
 		}
-		ACM_TRY(make_events(ev, 6));
 	}
+	if (dense)              /* the intermediate PCM; a call without a window to decode still writes every row */
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, dense->pcm_arena_words(L.pcm_total) * sizeof(int16_t), (void **)&d_pcm));
+	if (dense || !L.dev_ids.empty()) {
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes(), (void **)&h_jobs));
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes(), (void **)&d_jobs));
+	}
+	if (dense || !L.act.empty())
+		ACM_TRY(make_events(ev, 6));
 	t_alloc = clk::now();
 	tm.alloc_s = secs(t_hdr, t_alloc);
 	return ACMHIP_OK;
@@ -221,10 +238,9 @@ int WinRun::parse_on_device()
 	return ACMHIP_OK;
 }
 
-/* one plan over every window that has samples: a pseudo-stream over its blocks, emitting from the row of its first sample */
-int WinRun::synthesise_and_deliver()
+/* every window that has samples as a stream of the call's plan: a pseudo-stream over its blocks, emitting from the row of its first sample */
+void WinRun::collect(PlanStreams &ps)
 {
-	PlanStreams ps;
 	for (size_t k : L.act) {
 		const WindowSlot &s = L.slots[k];
 		if (!live[k].active)
@@ -232,6 +248,13 @@ int WinRun::synthesise_and_deliver()
 		ps.add(info_of(k), s.idx_off, s.hdr_off, s.slot_off, s.nb * info_of(k).rows, s.row_begin, s.lead + s.words, live[k].patches);
 		tm.samples += s.words;
 	}
+}
+
+/* one plan over those streams */
+int WinRun::synthesise_and_deliver()
+{
+	PlanStreams ps;
+	collect(ps);
 	if (ps.descs.empty())
 		return ACMHIP_OK;
 	ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
@@ -257,6 +280,35 @@ int WinRun::synthesise_and_deliver()
 			if (live[L.act[a]].active && w.pcm && w.words)
 				memcpy(w.pcm, h_pcm + w.dev_off, std::min<uint64_t>(w.words, w.pcm_cap) * sizeof(int16_t));
 		});
+	return ACMHIP_OK;
+}
+
+/* a dense call: the same plan into the handle's PCM arena, then the row table - what staging left of every window - up through the jobs
+ * arena and one launch that writes every row of the caller's tensor.  Nothing comes back but the timings */
+int WinRun::synthesise_and_gather()
+{
+	PlanStreams ps;
+	collect(ps);
+	if (!ps.descs.empty())
+		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
+	const size_t at = dense->table_off(L), bytes = dense->table_bytes();
+	acm_dense_rows(*dense, L.slots.data(), wins, reinterpret_cast<AcmDenseRow *>(h_jobs + at));
+	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
+	tm.h2d_bytes += bytes;
+	ACM_HIP_TRY(hipEventRecord(ev[2], st));
+	if (plan)
+		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
+	const int e = acmk_launch_dense_rows(d_pcm, reinterpret_cast<const AcmDenseRow *>(d_jobs + at), L.slots.size(), dense_out, dense->frames,
+					     dense->channels, dense->planar, dense->f32, st);
+	if (e != 0)
+		return acmhip_report_hip(e, "acmk_launch_dense_rows");
+	ACM_HIP_TRY(hipEventRecord(ev[3], st));
+	ACM_HIP_TRY(hipStreamSynchronize(st));
+	float ms = 0;
+	if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+		tm.h2d_s = ms * 1e-3;
+	if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
+		tm.kernel_s = ms * 1e-3;
 	return ACMHIP_OK;
 }
 
@@ -349,6 +401,55 @@ static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
 	return run.synthesise_and_deliver();
+}
+
+/* the dense call without its wall clock */
+static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
+				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm)
+{
+	if (!dev)
+		return ACMHIP_ERR_NO_DEVICE;
+	if ((n && (!items || !index)) || (nwin && !wins))
+		return ACMHIP_ERR_ARG;
+	acm_batch_opts opts{};
+	if (opts_in)
+		opts = *opts_in;
+	const int threads_wanted = opts.threads > 0 ? opts.threads : default_threads();
+	Pool pool((int)std::min<size_t>((size_t)threads_wanted, std::max<size_t>(1, std::max(n, nwin))));
+
+	const std::vector<WindowItem> its = probe_items(pool, items, n, index, opts.force_chans);
+	DenseLayout D;
+	if (acm_dense_prepare(its.data(), n, wins, nwin, opts, dense, &D) != ACMHIP_OK) {
+		acmhip_set_error_text("acm_batch_decode_windows_dense: a call the dense writer does not take (include/acm_hip.h)");
+		return ACMHIP_ERR_ARG;
+	}
+	WindowLayout layout;
+	ACM_TRY(acm_window_layout(its.data(), n, D.wins.data(), nwin, D.inner, &layout, &pool));
+	for (size_t k = 0; k < nwin; k++)
+		acm_dense_report(D, layout.slots[k], k, &wins[k]);
+	tm.blocks_parsed = layout.blocks_parsed;
+	if (!nwin)
+		return ACMHIP_OK;
+
+	const auto t_hdr = clk::now();
+	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm);
+	ACM_TRY(run.fetch_arenas(t_hdr));
+	if (!layout.act.empty())
+		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
+	return run.synthesise_and_gather();
+}
+
+extern "C" int acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+					      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
+					      acm_window_timing *timing)
+{
+	acm_window_timing tm{};
+	const auto t0 = clk::now();
+	ACM_TRY(decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm));
+	tm.total_s = secs(t0, clk::now());
+	if (timing)
+		*timing = tm;
+	return ACMHIP_OK;
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,

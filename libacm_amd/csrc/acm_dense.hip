@@ -1,0 +1,196 @@
+/*
+ * acm_dense.hip - the last mile of a windowed decode (acm_batch_decode_windows_dense, acm_batch_windows.cpp): the crops of a call,
+ * which the synthesis kernels leave at arbitrary 2-byte alignments of padded slots, laid out as equally spaced rows of one tensor.
+ *
+ * No counterpart in the reference.  acm_dense_rows is a pure copy: per row it reads `count` int16 samples from the PCM arena,
+ * writes frames * channels output samples - the samples, then zeros - and on the way splits stereo pairs into a plane per channel
+ * (STRIDE 2) and widens to float32 (the int16 sample times 2^-15, exactly what acmhip_plan_launch_f32 stores).
+ *
+ * A row is cut into sub-rows (one, or one per plane) and a sub-row into units of 256 vectors of 8 output samples, a workgroup
+ * each; the grid is flat over (row, plane, unit) and strides.  The body of a sub-row starts where the OUTPUT is 16-byte aligned,
+ * so every lane stores whole 16-byte lines (one of int16, two of float32).  The source of such a vector sits `sh` bytes into an
+ * aligned 16-byte line, the same sh for every vector of the sub-row: the lane loads the aligned lines that hold its 16 * STRIDE
+ * bytes and funnels them - whole dwords by selects, the odd half dword by v_alignbyte.  A line is loaded only if it holds a
+ * sample of the vector, so every load lies inside the row's own samples rounded out to 16 bytes, which a window's 64-sample
+ * slot contains.  Narrow accesses: the up to 7 samples in front of the body, the up to 7 behind it, and the one vector in which a
+ * short row's samples end.  No LDS, no scratch (every register array is indexed by constants after unrolling).
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "acm_device.h"
+
+namespace {
+
+constexpr int DENSE_BLOCK = 256;        /* lanes per workgroup = vectors per unit */
+constexpr int DENSE_VEC = 8;            /* output samples per lane and body access */
+constexpr uint32_t DENSE_MAX_GRID = 1u << 20;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <bool NT, typename V> __device__ __forceinline__ void store_line(V *at, V v)
+{
+	if (NT)
+		__builtin_nontemporal_store(v, at);
+	else
+		*at = v;
+}
+
+/* 8 samples from p on, every STRIDE-th: p lies sh (even, wavefront-uniform) bytes into an aligned 16-byte line */
+template <int STRIDE> __device__ __forceinline__ void load_vec(const int16_t *p, uint32_t sh, int (&s)[DENSE_VEC])
+{
+	constexpr int LINES = STRIDE + 1;                               /* aligned lines that can hold a part of the vector's bytes ... */
+	constexpr uint32_t USED = STRIDE == 1 ? 16 : 30;                /* ... bytes [sh, sh + USED) counted from the first line */
+	const u32x4 *line = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(p) - sh);
+	uint32_t d[4 * LINES];
+#pragma unroll
+	for (int v = 0; v < LINES; v++) {
+		u32x4 x = { 0, 0, 0, 0 };
+		if (16u * v < sh + USED)                                /* a line behind the vector's last sample is not touched */
+			x = line[v];
+		d[4 * v] = x.x;
+		d[4 * v + 1] = x.y;
+		d[4 * v + 2] = x.z;
+		d[4 * v + 3] = x.w;
+	}
+	/* whole dwords of the shift: d[i] <- d[i + (sh >> 2)], for the 4 * STRIDE + 1 dwords the funnel reads */
+	if (sh & 4) {
+#pragma unroll
+		for (int i = 0; i + 1 < 4 * LINES; i++)
+			d[i] = d[i + 1];
+	}
+	if (sh & 8) {
+#pragma unroll
+		for (int i = 0; i + 2 < 4 * LINES; i++)
+			d[i] = d[i + 2];
+	}
+	const uint32_t r = sh & 3;                                      /* 0 or 2 */
+#pragma unroll
+	for (int j = 0; j < 4 * STRIDE; j++) {
+		const uint32_t e = __builtin_amdgcn_alignbyte(d[j + 1], d[j], r);
+		if (STRIDE == 1) {
+			s[2 * j] = (int16_t)(e & 0xFFFFu);
+			s[2 * j + 1] = (int16_t)(e >> 16);
+		} else {
+			s[j] = (int16_t)(e & 0xFFFFu);                  /* the other channel's sample is the high half */
+		}
+	}
+}
+
+template <bool NT> __device__ __forceinline__ void store_vec(int16_t *at, const int (&s)[DENSE_VEC])
+{
+	u32x4 w;
+	w.x = ((uint32_t)s[0] & 0xFFFFu) | ((uint32_t)s[1] << 16);
+	w.y = ((uint32_t)s[2] & 0xFFFFu) | ((uint32_t)s[3] << 16);
+	w.z = ((uint32_t)s[4] & 0xFFFFu) | ((uint32_t)s[5] << 16);
+	w.w = ((uint32_t)s[6] & 0xFFFFu) | ((uint32_t)s[7] << 16);
+	store_line<NT>(reinterpret_cast<u32x4 *>(at), w);
+}
+
+__device__ __forceinline__ float to_out(float *, int s) { return (float)s * 0x1p-15f; }
+__device__ __forceinline__ int16_t to_out(int16_t *, int s) { return (int16_t)s; }
+
+template <bool NT> __device__ __forceinline__ void store_vec(float *at, const int (&s)[DENSE_VEC])
+{
+	f32x4 a, b;
+	a.x = to_out(at, s[0]);
+	a.y = to_out(at, s[1]);
+	a.z = to_out(at, s[2]);
+	a.w = to_out(at, s[3]);
+	b.x = to_out(at, s[4]);
+	b.y = to_out(at, s[5]);
+	b.z = to_out(at, s[6]);
+	b.w = to_out(at, s[7]);
+	store_line<NT>(reinterpret_cast<f32x4 *>(at), a);
+	store_line<NT>(reinterpret_cast<f32x4 *>(at) + 1, b);
+}
+
+/* sub_len: output samples of a sub-row (frames with STRIDE 2, else the whole row); units: workgroups per sub-row */
+template <typename OUT, int STRIDE, bool NT>
+__global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_rows(const int16_t *__restrict__ src, const AcmDenseRow *__restrict__ rows, uint64_t nwork,
+							       uint32_t units, OUT *__restrict__ out, uint64_t row_len, uint64_t sub_len)
+{
+	const uint32_t per_row = units * STRIDE;
+	for (uint64_t work = blockIdx.x; work < nwork; work += gridDim.x) {
+		const uint64_t k = work / per_row;
+		const uint32_t rem = (uint32_t)(work - k * per_row);
+		const uint32_t plane = STRIDE == 2 ? rem / units : 0;
+		const uint32_t unit = rem - plane * units;
+		const AcmDenseRow row = rows[k];
+		/* samples this sub-row has: every STRIDE-th of row.count, from sample `plane` on */
+		const uint64_t have = STRIDE == 2 ? (row.count + 1 - plane) / 2 : row.count;
+		const int16_t *sub = src + row.src + plane;
+		OUT *o = out + k * row_len + (uint64_t)plane * sub_len;
+		/* [0, head) in front of the first aligned output line, nvec whole vectors, [tail, sub_len) behind them */
+		const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
+		const uint64_t head = to_line < sub_len ? to_line : sub_len;
+		const uint64_t nvec = (sub_len - head) / DENSE_VEC;
+		const uint64_t tail = head + nvec * DENSE_VEC;
+		const uint32_t sh = (uint32_t)reinterpret_cast<uintptr_t>(sub + STRIDE * head) & 15u;
+
+		const uint64_t v = (uint64_t)unit * DENSE_BLOCK + threadIdx.x;
+		if (v < nvec) {
+			const uint64_t e = head + v * DENSE_VEC;
+			int s[DENSE_VEC];
+			if (e + DENSE_VEC <= have) {
+				load_vec<STRIDE>(sub + STRIDE * e, sh, s);
+			} else {
+#pragma unroll
+				for (int i = 0; i < DENSE_VEC; i++)
+					s[i] = e + i < have ? sub[STRIDE * (e + i)] : 0;
+			}
+			store_vec<NT>(o + e, s);
+		}
+		if (unit == 0 && threadIdx.x < head) {
+			const uint64_t e = threadIdx.x;
+			o[e] = to_out(o, e < have ? sub[STRIDE * e] : 0);
+		}
+		if (unit == units - 1 && tail + threadIdx.x < sub_len) {
+			const uint64_t e = tail + threadIdx.x;
+			o[e] = to_out(o, e < have ? sub[STRIDE * e] : 0);
+		}
+	}
+}
+
+template <typename OUT, int STRIDE>
+int launch(bool nt, uint32_t grid, hipStream_t st, const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nwork, uint32_t units, void *d_out,
+	   uint64_t row_len, uint64_t sub_len)
+{
+	if (nt)
+		hipLaunchKernelGGL((acm_dense_rows<OUT, STRIDE, true>), dim3(grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, nwork, units,
+				   static_cast<OUT *>(d_out), row_len, sub_len);
+	else
+		hipLaunchKernelGGL((acm_dense_rows<OUT, STRIDE, false>), dim3(grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, nwork, units,
+				   static_cast<OUT *>(d_out), row_len, sub_len);
+	return (int)hipGetLastError();
+}
+
+} // namespace
+
+extern "C" int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
+				      int planar, int f32, void *stream)
+{
+	if (nrows == 0)
+		return 0;
+	const int stride = planar && channels == 2 ? 2 : 1;
+	const uint64_t row_len = frames * channels, sub_len = stride == 2 ? frames : row_len;
+	const uint64_t units = std::max<uint64_t>(1, (sub_len / DENSE_VEC + DENSE_BLOCK - 1) / DENSE_BLOCK);
+	if (units > 0x7FFFFFFFull || nrows > ~0ull / (units * stride))
+		return (int)hipErrorInvalidValue;
+	const uint64_t nwork = nrows * units * stride;
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
+	/* Temporal stores: the batch is read by the next kernel of the caller's step (profiles/dense_crop_notes.txt).  The other variant is
+	 * reachable for measurements only, like every kernel switch (acm_device.h: ACM_TUNING_ENV) */
+	const char *env = ACM_TUNING_ENV("ACM_DENSE_NT");
+	const bool nt = env && atoi(env) != 0;
+	hipStream_t st = (hipStream_t)stream;
+	if (f32)
+		return stride == 2 ? launch<float, 2>(nt, grid, st, d_src, d_rows, nwork, (uint32_t)units, d_out, row_len, sub_len)
+				   : launch<float, 1>(nt, grid, st, d_src, d_rows, nwork, (uint32_t)units, d_out, row_len, sub_len);
+	return stride == 2 ? launch<int16_t, 2>(nt, grid, st, d_src, d_rows, nwork, (uint32_t)units, d_out, row_len, sub_len)
+			   : launch<int16_t, 1>(nt, grid, st, d_src, d_rows, nwork, (uint32_t)units, d_out, row_len, sub_len);
+}

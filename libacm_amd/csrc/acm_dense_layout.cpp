@@ -1,0 +1,120 @@
+/*
+ * acm_dense_layout.cpp - the device-free half of acm_batch_decode_windows_dense (acm_batch_windows.cpp): the call's validation, its
+ * soft rejections, the output size and the gather kernel's row table.  No HIP call here.
+ */
+#include "acm_dense_layout.h"
+
+namespace acmbatch {
+
+int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window *wins, size_t nwin, const acm_batch_opts &opts,
+		      const acm_dense_opts *dense, DenseLayout *out)
+{
+	DenseLayout &D = *out;
+	D = DenseLayout();
+	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) || (dense->flags & ~ACM_DENSE_PLANAR))
+		return ACMHIP_ERR_ARG;
+	/* padding has one meaning in the signed little-endian writer only; the staged forms of a prestaged or packed batch are not a window's */
+	if (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE || opts.parse > ACM_BATCH_PARSE_AUTO || opts.prestaged || (opts.flags & ACM_BATCH_STAGE_PACKED))
+		return ACMHIP_ERR_ARG;
+	if (dense->frames > ~0ull / dense->channels)
+		return ACMHIP_ERR_ARG;
+	D.frames = dense->frames;
+	D.channels = dense->channels;
+	D.row_words = D.frames * D.channels;
+	D.planar = (dense->flags & ACM_DENSE_PLANAR) != 0;
+	D.f32 = (opts.flags & ACM_BATCH_PCM_F32) != 0;
+	if (nwin && D.row_words > ~0ull / nwin)
+		return ACMHIP_ERR_ARG;
+	D.out_words = nwin * D.row_words;
+	if (opts.d_pcm_words < D.out_words)
+		return ACMHIP_ERR_ARG;
+	for (size_t k = 0; k < nwin; k++)
+		if (wins[k].max_words > D.row_words || wins[k].first_word % D.channels || wins[k].max_words % D.channels)
+			return ACMHIP_ERR_ARG;
+
+	D.wins.assign(wins, wins + nwin);
+	D.rejected.assign(nwin, 0);
+	for (size_t k = 0; k < nwin; k++) {
+		const acm_batch_window &w = wins[k];
+		/* an item that is not ACM, or whose index it cannot have, has no channel count to compare: its windows deliver nothing anyway */
+		if (w.item < n && items[w.item].ok && items[w.item].info.channels != D.channels) {
+			D.rejected[k] = 1;
+			D.wins[k].max_words = 0;
+		}
+	}
+	D.inner = opts;
+	D.inner.d_pcm = nullptr;
+	D.inner.d_pcm_words = 0;
+	D.inner.flags &= ~ACM_BATCH_PCM_F32;
+	return ACMHIP_OK;
+}
+
+void acm_dense_report(const DenseLayout &D, const WindowSlot &s, size_t k, acm_batch_window *w)
+{
+	w->status = D.rejected[k] ? ACMHIP_ERR_ARG : s.status;
+	w->words = s.words;
+	w->dev_off = w->slot_off = k * D.row_words;
+	w->slot_words = D.row_words;
+}
+
+void acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows)
+{
+	for (size_t k = 0; k < D.wins.size(); k++) {
+		const uint64_t count = slots[k].active ? std::min(final[k].words, slots[k].words) : 0;
+		rows[k] = AcmDenseRow{ count ? slots[k].dev_off : 0, count };
+	}
+}
+
+} // namespace acmbatch
+
+extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status,
+				       const uint64_t *whole, const acm_block_mark *const *marks, const uint32_t *blocks, size_t n,
+				       const uint64_t *win3, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+				       const uint64_t *final_words, acmk_window_layout_visit_fn visit, void *ctx)
+{
+	using namespace acmbatch;
+	std::vector<WindowItem> items(n);
+	for (size_t i = 0; i < n; i++) {
+		items[i].info = info[i];
+		items[i].len = len[i];
+		items[i].ok = ok[i] != 0;
+		items[i].end_status = end_status[i];
+		items[i].whole = whole[i];
+		items[i].marks = marks[i];
+		items[i].blocks = blocks[i];
+	}
+	std::vector<acm_batch_window> wins(nwin);
+	for (size_t k = 0; k < nwin; k++) {
+		wins[k] = acm_batch_window{};
+		wins[k].item = (uint32_t)win3[3 * k];
+		wins[k].first_word = win3[3 * k + 1];
+		wins[k].max_words = win3[3 * k + 2];
+	}
+	DenseLayout D;
+	WindowLayout L;
+	int rc = acm_dense_prepare(items.data(), n, wins.data(), nwin, *opts, dense, &D);
+	if (rc == ACMHIP_OK)
+		rc = acm_window_layout(items.data(), n, D.wins.data(), nwin, D.inner, &L);
+	if (rc == ACMHIP_OK) {
+		std::vector<uint64_t> w, rej(D.rejected.begin(), D.rejected.end()), rep;
+		for (size_t k = 0; k < nwin; k++) {
+			w.insert(w.end(), { (uint64_t)D.wins[k].item, D.wins[k].first_word, D.wins[k].max_words });
+			acm_dense_report(D, L.slots[k], k, &wins[k]);
+			rep.insert(rep.end(), { (uint64_t)(int64_t)wins[k].status, wins[k].words, wins[k].dev_off, wins[k].slot_off, wins[k].slot_words });
+			if (final_words)
+				wins[k].words = final_words[k];
+		}
+		std::vector<AcmDenseRow> rows(nwin);
+		acm_dense_rows(D, L.slots.data(), wins.data(), rows.data());
+		if (nwin) {
+			visit(ctx, "wins", w.data(), 3 * sizeof(uint64_t), nwin);
+			visit(ctx, "rejected", rej.data(), sizeof(uint64_t), nwin);
+			visit(ctx, "report", rep.data(), 5 * sizeof(uint64_t), nwin);
+			visit(ctx, "rows", rows.data(), sizeof(AcmDenseRow), nwin);
+		}
+	}
+	const uint64_t totals[] = { D.frames, D.row_words, D.channels, (uint64_t)D.planar, (uint64_t)D.f32, D.out_words, D.pcm_arena_words(L.pcm_total),
+				    L.blocks_parsed, D.table_off(L), D.table_bytes(), (uint64_t)(int64_t)rc };
+	visit(ctx, "totals", totals, sizeof(uint64_t), sizeof(totals) / sizeof(totals[0]));
+	return rc;
+}

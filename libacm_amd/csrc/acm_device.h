@@ -100,6 +100,12 @@ struct AcmBlockJob {
 	uint32_t pad;
 };
 
+/* dense crop batches (acm_dense.hip): row k of the output is `count` samples from sample `src` of the int16 PCM arena on, zeros behind them */
+struct AcmDenseRow {
+	uint64_t src;
+	uint64_t count;        /* 0: the row is all zeros and src is not read */
+};
+
 /* levels the fused tile kernel covers; its tile geometry is owned by acm_kernels.hip (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
 #define ACM_K1_MAX_LEVEL 12
@@ -258,6 +264,12 @@ int acmk_launch_small_f32(uint32_t level, const AcmDevStream *d_streams, const u
 			  const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_emit_f32(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
 			 const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream);
+/* acm_dense.hip: nrows rows of frames * channels samples each into d_out (int16, or float32 = the int16 sample times 2^-15 with f32), row k at
+ * element k * frames * channels: d_rows[k].count samples from d_src + d_rows[k].src, interleaved as they are or (planar, channels == 2) split
+ * into a plane per channel, zeros behind them.  d_src: 16-byte aligned; the kernel loads whole aligned 16-byte lines and only lines that hold
+ * at least one of a row's samples.  d_out: aligned to its element.  One launch, nothing allocated, nothing waited for */
+int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
+			   int planar, int f32, void *stream);
 #ifdef __cplusplus
 }
 #endif
