@@ -160,6 +160,10 @@ void acmhip_plan_destroy(acmhip_plan *plan);
  * the plan: replaces decode.c:592-600 (table), :174-177 (lookup), :528-577
  * (juggle_block), :657-677 (output_values).  d_idx / d_hdr / d_pcm are device
  * pointers; fmt is ACMHIP_FMT_*.  Asynchronous on the device's stream.
+ * The launches of one plan follow each other there, and they must: the plan owns small device state that a launch uses and
+ * hands on as it found it (the word in which the chunk kernel's wavefronts count the runs of the chunk table they claim - one per
+ * level group, zero between launches).  A launch captured into a graph may be replayed any number of times, one replay behind
+ * the other; two replays, or a replay and a launch, that could run at the same time need a plan each.
  */
 int  acmhip_plan_launch(acmhip_plan *plan, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 			int16_t *d_pcm, unsigned fmt);

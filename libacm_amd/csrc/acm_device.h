@@ -188,11 +188,22 @@ int acmk_launch_tile2p(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_
 /* the byte-plane staged form: the same tile records as acm_tile2 except that idx_off is the pair-table entry of the row pair in front of the tile */
 int acmk_tile2m_rows(uint32_t level);                           /* = acmk_tile2_rows, 0 if the level has no such build */
 int acmk_tile2m_lead_in(uint32_t level);                        /* tiles of this build in front of a window into a stream (ACM_TILE_DISCARD records) */
-int acmk_tile2m_run_waves(uint32_t level, int cus);             /* wavefronts that share a launch's table (the chunk kernel: one contiguous run each), else 0 */
+int acmk_tile2m_run_waves(uint32_t level, int cus);             /* wavefronts that share a launch's table (the chunk kernel), else 0 */
+/* how those W wavefronts share a table of ntiles chunks: wavefront w takes the chunks [w * static_per, (w + 1) * static_per) - below the
+ * threshold (acm_kernels.hip states the rule) that is the whole table, static_per = ceil(ntiles / W), nclaimed = 0, as ever -, and the
+ * chunks behind W * static_per are nclaimed runs of run_chunks (the last one may be shorter) which the wavefronts claim in ascending
+ * order as they come free.  Device-free.  -1: the level has no chunk kernel */
+int acmk_tile2m_split(uint32_t level, int cus, uint32_t ntiles, uint32_t *static_per, uint32_t *run_chunks, uint32_t *nclaimed);
+/* process-wide policy of that split in place of the levels' compiled-in ones (tests, sweeps): chunks per claimed run (0: none are claimed)
+ * and the static share in thousandths; a negative argument restores the default.  Hands back the values in force before (negative: default) */
+void acmk_tile2m_claim_config(int run_chunks, int static_permille, int *old_run_chunks, int *old_static_permille);
 int acmk_tile2m_grid(uint32_t level, int cus);                  /* persistent workgroups of its launch at most */
 int acmk_tile2m_stages(uint32_t level);                         /* stages of its first pass (3 or 4): the form keeps 2^stages columns of a residue class side by side */
+/* d_claim (the chunk kernel; null: the static split whatever the table's size): ONE zeroed word that the launch's wavefronts count their
+ * claims in and leave at zero again.  Two launches that may run at the same time need a word each; launches on one stream - all launches of
+ * a plan: it launches on its device's one stream - follow each other and share one */
 int acmk_launch_tile2m(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
-		       const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
+		       const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, uint32_t *d_claim, void *stream);
 int acmk_launch_unpack(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
 		       const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_x, uint32_t shift, void *stream);
 int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
@@ -257,7 +268,7 @@ int acmk_launch_fused_f32(uint32_t level, int variant, int cus, int carry, const
 int acmk_launch_tile2_f32(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 			  int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
 int acmk_launch_tile2m_f32(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
-			   const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
+			   const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, uint32_t *d_claim, void *stream);
 int acmk_launch_fused_plane_f32(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
 				const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_small_f32(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,

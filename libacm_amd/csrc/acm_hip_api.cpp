@@ -101,6 +101,7 @@ struct LevelGroup {
 	/* the same for streams that came with a byte-plane form (acm_tile2's matrix-core build) */
 	AcmTile2 *d_tiles2m = nullptr, *d_tiles2m_plain = nullptr;
 	uint32_t ntiles2m = 0, ntiles2m_plain = 0;      /* the matrix-core build may cut the same rows into smaller tiles */
+	uint32_t *d_claim = nullptr;                    /* the chunk kernel's claim word for d_tiles2m (acmk_launch_tile2m): zero between launches */
 	AcmTile *d_tiles_extra = nullptr;   /* halo-flavour tiles that must not join a carry run (clean tiles of patched streams) */
 	uint32_t ntiles_extra = 0;
 	uint32_t *d_list = nullptr;
@@ -613,6 +614,13 @@ int upload_group(acmhip_plan *pl, const AcmCutGroup &c, LevelGroup *g)
 	up(c.tiles2m, &g->d_tiles2m);
 	up(c.tiles2m_plain, &g->d_tiles2m_plain);
 	up(c.list, &g->d_list);
+	/* the word in which the chunk kernel's wavefronts count the runs they claim: one per group is enough, a plan's launches follow each
+	 * other on the device's one stream.  Zeroed once, on the upload stream with the tables; every launch leaves it at zero */
+	if (rc == ACMHIP_OK && g->ntiles2m && acmk_tile2m_run_waves(g->level, pl->dev->cus) > 0) {
+		rc = plan_malloc(pl, (void **)&g->d_claim, 256);
+		if (rc == ACMHIP_OK && !pl->dev->fill)
+			rc = fill_block(pl->dev, g->d_claim, 256);
+	}
 	return rc;
 }
 
@@ -796,7 +804,7 @@ static int plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhd
 		else
 			LAUNCHTRY(acmk_launch_tile2(g.level, pl->dev->cus, g.d_tiles2p_plain, g.ntiles2p, d_idx, d_hdr, d_pcm, pl->d_sink, fmt, st));
 		if (pl->mform)
-			LAUNCHTRY(acmk_launch_tile2m(g.level, pl->dev->cus, g.d_tiles2m, g.ntiles2m, pl->mform, pl->mform_pairs, d_hdr, d_pcm, pl->d_sink, fmt, st));
+			LAUNCHTRY(acmk_launch_tile2m(g.level, pl->dev->cus, g.d_tiles2m, g.ntiles2m, pl->mform, pl->mform_pairs, d_hdr, d_pcm, pl->d_sink, fmt, g.d_claim, st));
 		else
 			LAUNCHTRY(acmk_launch_tile2(g.level, pl->dev->cus, g.d_tiles2m_plain, g.ntiles2m_plain, d_idx, d_hdr, d_pcm, pl->d_sink, fmt, st));
 	}

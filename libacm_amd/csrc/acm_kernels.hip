@@ -980,6 +980,23 @@ __device__ __forceinline__ unsigned long long stamp_now()
 	return t;
 }
 #define ACM_STAMP(k) do { const unsigned long long n_ = stamp_now(); acc_[k] += n_ - last_; last_ = n_; } while (0)
+/* ... and, for the chunk kernel (profiles/ubench/phases_k3.hip), when every wavefront of a launch begins and ends its share of the chunk
+ * table: { s_memtime, the constant-rate counter } at entry, the same at exit, chunks executed (replays included), where it ran
+ * (HW_ID | XCC_ID << 32), runs taken (the static one included), - */
+#define ACM_WAVE_STAMPS_MAX 8192
+__device__ unsigned long long g_acm_wave_stamps[ACM_WAVE_STAMPS_MAX][8];
+__device__ __forceinline__ void stamp_both(unsigned long long &shader, unsigned long long &real)
+{
+	__builtin_amdgcn_sched_barrier(0);
+	asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(shader), "=s"(real) :: "memory");
+	__builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ unsigned long long stamp_where()
+{
+	uint32_t hw, xcc;
+	asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
+	return (unsigned long long)hw | (unsigned long long)xcc << 32;
+}
 #else
 #define ACM_STAMP(k) do { } while (0)
 #endif
@@ -3045,7 +3062,8 @@ struct FirstPassZ {
 template <int L_, int ABL, int... Gs>
 __global__ void __launch_bounds__(64 * FirstPassZ<L_>::NW, 1)
 ACM_K_CHUNK(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int16_t *__restrict__ idx, const uint32_t *__restrict__ pairs,
-	  const acmhip_blkhdr *__restrict__ hdr, int16_t *__restrict__ pcm, int16_t *__restrict__ sink, const unsigned fmt)
+	  const acmhip_blkhdr *__restrict__ hdr, int16_t *__restrict__ pcm, int16_t *__restrict__ sink, const unsigned fmt,
+	  uint32_t *__restrict__ claim, const uint32_t static_per, const uint32_t run_chunks, const uint32_t nclaimed)
 {
 	constexpr bool F32 = ACM_OUT_F32;
 
@@ -3063,28 +3081,76 @@ ACM_K_CHUNK(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int
 	const int lane0 = threadIdx.x & 63;
 	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	FP::fill_tables(tables, threadIdx.x, NW * 64);
+
+	/* a wavefront is a workgroup of its own behind the barrier below: contiguous runs of the chunk table.  The table's first nvw * per
+	 * chunks are one static run per wavefront; what lies behind them (nclaimed != 0: acmk_tile2m_split) is cut into nclaimed runs of
+	 * run_chunks, which the wavefronts take in ascending order as they come free, each by ONE returning atomic increment of claim[0]
+	 * made by one lane.  Nobody waits for anybody: a wavefront whose claim finds the table exhausted returns.  The increment wraps at
+	 * nclaimed + nvw - 1, and every wavefront of the launch claims until it is refused, exactly once: nclaimed + nvw increments per
+	 * launch, which leave the word at zero for the next launch (a replay of a captured one included) - no second word, nobody has
+	 * to be the last one out.
+	 * What a run's end needs of all this waits in LDS (split_mem): scalar registers are what THIS loop is short of (level 8 uses all
+	 * of them), and seven more held through it for something looked at every run_chunks chunks were spilled into vector registers */
+	enum { SPLIT_CLAIM_LO, SPLIT_CLAIM_HI, SPLIT_WRAP, SPLIT_NCLAIMED, SPLIT_NSTATIC, SPLIT_RUN_CHUNKS, SPLIT_NTILES, SPLIT_WORDS };
+	__shared__ __attribute__((aligned(8))) uint32_t split_mem[SPLIT_WORDS + 1];
+	const uint32_t nvw = gridDim.x * NW, vw = blockIdx.x * NW + wave;
+	const uint32_t per = nclaimed ? static_per : (ntiles + nvw - 1) / nvw;
+	const uint32_t nstatic = nclaimed ? nvw * static_per : ntiles;
+	if (threadIdx.x == 0) {
+		const uint64_t c = nclaimed ? reinterpret_cast<uint64_t>(claim) : 0ull;          /* (null: the static split, nobody claims) */
+		split_mem[SPLIT_CLAIM_LO] = (uint32_t)c;
+		split_mem[SPLIT_CLAIM_HI] = (uint32_t)(c >> 32);
+		split_mem[SPLIT_WRAP] = nclaimed + nvw - 1;
+		split_mem[SPLIT_NCLAIMED] = nclaimed;
+		split_mem[SPLIT_NSTATIC] = nstatic;
+		split_mem[SPLIT_RUN_CHUNKS] = run_chunks;
+		split_mem[SPLIT_NTILES] = ntiles;
+	}
 	__syncthreads();                                /* the only one: the coefficient tables are shared */
 
 	uint32_t *const tile = tile_mem[wave] + 8;
 	uint32_t *const carry_mem = carry_all[wave];
 
-	/* a wavefront is a workgroup of its own from here on: a contiguous run of the chunk table */
-	const uint32_t nvw = gridDim.x * NW, vw = blockIdx.x * NW + wave;
-	const uint32_t per = (ntiles + nvw - 1) / nvw;
 	uint32_t t = vw * per;
-	const uint32_t t_end = t + per < ntiles ? t + per : ntiles;
-	if (t >= t_end)
-		return;
-	bool discard = false;
-	{
-		const uint32_t f0 = tiles[__builtin_amdgcn_readfirstlane(t)].flags;
-		if (f0 & ACM_TILE_DISCARD) {
-			discard = true;                 /* the lead-in record of a window into a stream: the table names the chunk in front itself */
-		} else if (!(f0 & ACM_TILE_FRESH)) {
-			discard = true;                 /* a run that starts inside a stream replays the chunk in front of it without storing PCM */
-			t--;
-		}
+	uint32_t t_end = t + per < nstatic ? t + per : nstatic;
+	if (t >= t_end) {
+		if (!nclaimed)
+			return;
+		/* no static run: the first claim, before anything is issued by hand (the compiler's own wait) */
+		uint32_t k = 0;
+		if (lane0 == 0)
+			k = atomicInc(claim, nclaimed + nvw - 1);
+		k = __builtin_amdgcn_readfirstlane(k);
+		if (k >= nclaimed)
+			return;
+		t = nstatic + k * run_chunks;
+		t_end = t + run_chunks < ntiles ? t + run_chunks : ntiles;
 	}
+	/* every later claim is made in the LAST iteration of the run in hand, in front of that chunk's PCM stores: the end-of-iteration wait,
+	 * which leaves only those stores in flight, has waited for it like for the loads issued beside it - no wait of its own, none
+	 * in flight across a run's start, and its latency (one to three microseconds under load) behind the LDS passes.  One statement
+	 * writes the register, whichever way its scalar branches go (see fetch_val); lane 0 alone is active in it: it fetches the word's
+	 * address and the wrap from split_mem (the register that takes the answer serves as LDS address and as the increment's operand on
+	 * the way) and leaves the increment out where the address is null */
+	auto claim_next = [&](uint32_t v, const uint32_t more) -> uint32_t {
+		uint64_t exec_was, at;
+		asm volatile("s_cmp_lg_u32 %[more], 0\n\ts_cbranch_scc1 .Lacm_cl_%=\n\t"
+			     "s_mov_b64 %[was], exec\n\ts_mov_b64 exec, 1\n\t"
+			     "v_mov_b32 %[v], %[lds]\n\t"
+			     "ds_read_b64 %[at], %[v]\n\tds_read_b32 %[v], %[v] offset:8\n\t"
+			     "s_waitcnt lgkmcnt(0)\n\t"
+			     "v_cmp_ne_u64 vcc, 0, %[at]\n\ts_cbranch_vccz .Lacm_cn_%=\n\t"
+			     "global_atomic_inc %[v], %[at], %[v], off sc0\n"
+			     ".Lacm_cn_%=:\n\t"
+			     "s_mov_b64 exec, %[was]\n"
+			     ".Lacm_cl_%=:"
+			     : [v] "+v"(v), [was] "=&s"(exec_was), [at] "=&v"(at)
+			     : [lds] "s"((uint32_t)reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint32_t *)&split_mem[SPLIT_CLAIM_LO])), [more] "s"(__builtin_amdgcn_readfirstlane(more))
+			     : "memory", "scc", "vcc");
+		return v;
+	};
+	static_assert(SPLIT_CLAIM_HI == SPLIT_CLAIM_LO + 1 && SPLIT_WRAP == SPLIT_CLAIM_LO + 2, "the claim statement reads these three as it finds them");
+	auto split_word = [&](const int k) -> uint32_t { return __builtin_amdgcn_readfirstlane(split_mem[k]); };
 
 	/* rows of the stream in front of a chunk: 0, 1 (chunks of one row only), or 2 for "two or more" */
 	auto rows_in_front = [](const AcmTile2 &r) -> uint32_t { return (r.flags & ACM_TILE_FRESH) ? 0u : (r.flags & ACM_TILE_ROW1) ? 1u : 2u; };
@@ -3137,124 +3203,165 @@ ACM_K_CHUNK(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int
 		return FP::template mode_of<MODE_J0>(r.flags, d, sval);
 	};
 #endif
-	AcmTile2 cur = record_at(t);
-	typename FP::Desc dcur = FP::fetch_desc(pairs, cur);
-	typename FP::Raw raw;
-	{
-		const v4u_t z = { 0, 0, 0, 0 };
-#pragma unroll
-		for (int g = 0; g < FP::NG; g++)
-#pragma unroll
-			for (int k = 0; k < FP::NX; k++)
-				raw.hi[g][k] = z;               /* (the load statement of the high bytes reads the register it may leave alone) */
-	}
-	/* a run's first chunk asks for all its rows, the ones in front included, and for its row values: the general path */
-	uint32_t mode_cur = 0u, sv_cur = val_of(cur);
-	uint32_t hv = fetch_val(cur, lane0, 0u, 0u);
-	FP::template issue<false>(raw, arena, dcur, lane0, (cur.flags & ACM_TILE_ODD) ? 1u : 0u, 0u);
-	k2_wait<0>();
-	bool fresh = true, first_of_run = true;
-	AcmTile2 nxt = record_at(t + 1), nx2 = record_at(t + 2);
-	typename FP::Desc dnxt = FP::fetch_desc(pairs, nxt);
-	uint32_t sv_nxt = val_of(nxt);
-	uint32_t mode_nxt = mode_of(nxt, dnxt, sv_nxt);
 #ifdef ACM_STAMPS
 	unsigned long long acc_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-	unsigned long long last_ = stamp_now();
+	unsigned long long wave_c0_, wave_r0_;
+	stamp_both(wave_c0_, wave_r0_);
+	unsigned long long last_ = wave_c0_;
+	uint32_t wave_chunks_ = 0, wave_runs_ = 0;
 #endif
+	uint32_t claimed = 0;                           /* the next claim's answer, lane 0 */
+	/* one trip per run: the static one first, then the claimed ones */
 	for (;;) {
-		const uint32_t tn = t + 1;
-		const bool more = tn < t_end;
-		/* whatever a lane works out from its number is worked out per chunk: registers are what the LDS passes are short of, and a
-		 * loop-invariant value would sit in one through all of them */
-		int lane = lane0;
-#ifdef ACM_K3_OPAQUE_LANE
-		asm volatile("" : "+v"(lane));
-#endif
-		if (fresh)
-			for (int k = lane; k < NCARRY_WORDS; k += 64)
-				carry_mem[k] = 0u;
-		const uint32_t hvs = hv << OutScale<L>::SHIFT;
-		ACM_STAMP(0);
-		phase_prio<true, PRIO_FIRST_PASS>();
-		FP::run(raw, tile, tables, lane, hvs, dcur, rows_in_front(cur), (cur.flags & ACM_TILE_ODD) ? 1u : 0u, mode_cur, sv_cur, first_of_run);
-		first_of_run = false;
-		phase_prio<true, PRIO_IDLE>();
-		ACM_STAMP(1);
-
-		hv = fetch_val(nxt, lane, hv, mode_nxt);              /* the last chunk of a run fetches its own again: no branch around the loads */
-		if constexpr (FP::HISTORY_IN_REGISTERS) {
-			/* the rows in front of the next chunk's walk are in this lane's registers already - unless that chunk starts a stream
-			 * (nothing in front of it: zeros).  (The last chunk of a run, which names itself, is never looked at again.) */
-			/* (the first lead-in chunk of a window - ACM_TILE_DISCARD, not the successor of this chunk - finds another stream's rows there:
-			 * its output is wrong and dropped, and the planner puts enough lead-in chunks in front of a window that the last of them has
-			 * its own stream's rows in front of it, acmk_tile2m_lead_in.  A second load sequence for that case, in a branch, makes the
-			 * compiler join the two with copies of registers whose loads are still in flight: tests/test_isa_invariants.py) */
-			FP::shift_history(raw);
-			if (nxt.flags & ACM_TILE_FRESH)
-				FP::zero_history(raw);
-			FP::template issue<true>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
-		} else if constexpr (FP::HISTORY_BY_DPP) {
-			/* (the same with two walkers: walker 0's rows in front come from walker 1's lanes now, walker 1's from walker 0's in front of
-			 * the next first pass - FirstPassZ::run.  A window's first lead-in chunk: as above) */
-			FP::hand_history_on(raw);
-			if (nxt.flags & ACM_TILE_FRESH)
-				FP::zero_history(raw);
-			FP::template issue<true>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
-		} else {
-			FP::template issue<false>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
-		}
-		/* (asked for here, looked at from the end of this iteration on: behind the LDS passes' own waits) */
-		const AcmTile2 nx3 = record_at(t + 3);
-		const typename FP::Desc dnx2 = FP::fetch_desc(pairs, nx2);
-		const uint32_t sv_nx2 = val_of(nx2);
-		ACM_STAMP(2);
-		phase_prio<true, PRIO_LDS_PASSES>();
-		run_lds_passes<C, PASS_ABL, true, FP::G, Gs...>(tile, lane, F32 ? (unsigned)ACMHIP_FMT_S16LE : fmt, carry_mem);
-		tile_barrier<MODE_WAVE>();
-		ACM_STAMP(3);
-		if constexpr (F32) {
-			float *out = discard ? reinterpret_cast<float *>(sink) : reinterpret_cast<float *>(pcm) + cur.pcm_off;
-			lean_store_f32<C, 64, NSTORE, ABL>(tile, lane, out);
-		} else {
-			typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-			v4u *out = discard ? reinterpret_cast<v4u *>(sink) : reinterpret_cast<v4u *>(reinterpret_cast<uint16_t *>(pcm) + cur.pcm_off);
-#pragma unroll
-			for (int k = 0; k < NSTORE; k++) {
-				const int vec = lane + k * 64;
-				const uint32_t *q = tile + lds_at<C::PS>((vec / PER_OWNER) * NJ_LAST) + (vec % PER_OWNER) * park_piece<NJ_LAST>();
-				const v4u o = { q[0], q[1], q[2], q[3] };
-#ifdef ACM_K3_ST_MOD            /* (A/B builds: another cache policy for the PCM stores - "", " sc1", " sc0 sc1", " sc1 nt" ...; the shipped one is nt) */
-				asm volatile("global_store_dwordx4 %0, %1, %2" ACM_K3_ST_MOD :: "v"((uint32_t)(vec * 16)), "v"(o), "s"(sgpr_u64(reinterpret_cast<uint64_t>(out))) : "memory");
-#else
-				__builtin_nontemporal_store(o, &out[vec]);
-#endif
+		bool discard = false;
+		{
+			const uint32_t f0 = tiles[__builtin_amdgcn_readfirstlane(t)].flags;
+			if (f0 & ACM_TILE_DISCARD) {
+				discard = true;                 /* the lead-in record of a window into a stream: the table names the chunk in front itself */
+			} else if (!(f0 & ACM_TILE_FRESH)) {
+				discard = true;                 /* a run that starts inside a stream replays the chunk in front of it without storing PCM */
+				t--;
 			}
 		}
-		ACM_STAMP(5);
-		phase_prio<true, PRIO_IDLE>();
-		k2_wait<F32 ? 2 * NSTORE : NSTORE>();           /* the next chunk's indices are here; only this chunk's PCM stores may still be on their way */
-		ACM_STAMP(6);
-		tile_barrier<MODE_WAVE>();                      /* (the next first pass overwrites what the stores have just read) */
-		if (!more)
-			break;
-		fresh = (nxt.flags & (ACM_TILE_FRESH | ACM_TILE_DISCARD)) != 0;
-		discard = (nxt.flags & ACM_TILE_DISCARD) != 0;
-		cur = nxt;
-		dcur = dnxt;
-		sv_cur = sv_nxt;
-		mode_cur = mode_nxt;
-		t = tn;
-		nxt = nx2;
-		dnxt = dnx2;
-		sv_nxt = sv_nx2;
-		mode_nxt = mode_of(nxt, dnxt, sv_nxt);
-		nx2 = nx3;
+		AcmTile2 cur = record_at(t);
+		typename FP::Desc dcur = FP::fetch_desc(pairs, cur);
+		typename FP::Raw raw;
+		{
+			const v4u_t z = { 0, 0, 0, 0 };
+#pragma unroll
+			for (int g = 0; g < FP::NG; g++)
+#pragma unroll
+				for (int k = 0; k < FP::NX; k++)
+					raw.hi[g][k] = z;               /* (the load statement of the high bytes reads the register it may leave alone) */
+		}
+		/* a run's first chunk asks for all its rows, the ones in front included, and for its row values: the general path */
+		uint32_t mode_cur = 0u, sv_cur = val_of(cur);
+		/* (as in the loop below: what these loads work out from the lane's number is worked out per run, not once in front of all runs
+		 * and kept - level 8 has no register to keep it in) */
+		int lane_run = lane0;
+		asm volatile("" : "+v"(lane_run));
+		uint32_t hv = fetch_val(cur, lane_run, 0u, 0u);
+		FP::template issue<false>(raw, arena, dcur, lane_run, (cur.flags & ACM_TILE_ODD) ? 1u : 0u, 0u);
+		k2_wait<0>();
+		bool fresh = true, first_of_run = true;
+		AcmTile2 nxt = record_at(t + 1), nx2 = record_at(t + 2);
+		typename FP::Desc dnxt = FP::fetch_desc(pairs, nxt);
+		uint32_t sv_nxt = val_of(nxt);
+		uint32_t mode_nxt = mode_of(nxt, dnxt, sv_nxt);
+		ACM_STAMP(4);                                   /* (the start of a run: its first loads, waited for) */
+#ifdef ACM_STAMPS
+		wave_runs_++;
+#endif
+		for (;;) {
+			const uint32_t tn = t + 1;
+			const bool more = tn < t_end;
+#ifdef ACM_STAMPS
+			wave_chunks_++;
+#endif
+			/* whatever a lane works out from its number is worked out per chunk: registers are what the LDS passes are short of, and a
+			 * loop-invariant value would sit in one through all of them */
+			int lane = lane0;
+#ifdef ACM_K3_OPAQUE_LANE
+			asm volatile("" : "+v"(lane));
+#endif
+			if (fresh)
+				for (int k = lane; k < NCARRY_WORDS; k += 64)
+					carry_mem[k] = 0u;
+			const uint32_t hvs = hv << OutScale<L>::SHIFT;
+			ACM_STAMP(0);
+			phase_prio<true, PRIO_FIRST_PASS>();
+			FP::run(raw, tile, tables, lane, hvs, dcur, rows_in_front(cur), (cur.flags & ACM_TILE_ODD) ? 1u : 0u, mode_cur, sv_cur, first_of_run);
+			first_of_run = false;
+			phase_prio<true, PRIO_IDLE>();
+			ACM_STAMP(1);
+
+			hv = fetch_val(nxt, lane, hv, mode_nxt);              /* the last chunk of a run fetches its own again: no branch around the loads */
+			if constexpr (FP::HISTORY_IN_REGISTERS) {
+				/* the rows in front of the next chunk's walk are in this lane's registers already - unless that chunk starts a stream
+				 * (nothing in front of it: zeros).  (The last chunk of a run, which names itself, is never looked at again.) */
+				/* (the first lead-in chunk of a window - ACM_TILE_DISCARD, not the successor of this chunk - finds another stream's rows there:
+				 * its output is wrong and dropped, and the planner puts enough lead-in chunks in front of a window that the last of them has
+				 * its own stream's rows in front of it, acmk_tile2m_lead_in.  A second load sequence for that case, in a branch, makes the
+				 * compiler join the two with copies of registers whose loads are still in flight: tests/test_isa_invariants.py) */
+				FP::shift_history(raw);
+				if (nxt.flags & ACM_TILE_FRESH)
+					FP::zero_history(raw);
+				FP::template issue<true>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
+			} else if constexpr (FP::HISTORY_BY_DPP) {
+				/* (the same with two walkers: walker 0's rows in front come from walker 1's lanes now, walker 1's from walker 0's in front of
+				 * the next first pass - FirstPassZ::run.  A window's first lead-in chunk: as above) */
+				FP::hand_history_on(raw);
+				if (nxt.flags & ACM_TILE_FRESH)
+					FP::zero_history(raw);
+				FP::template issue<true>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
+			} else {
+				FP::template issue<false>(raw, arena, dnxt, lane, (nxt.flags & ACM_TILE_ODD) ? 1u : 0u, mode_nxt);
+			}
+			claimed = claim_next(claimed, more ? 1u : 0u);          /* the last chunk of a run asks for the next run */
+			/* (asked for here, looked at from the end of this iteration on: behind the LDS passes' own waits) */
+			const AcmTile2 nx3 = record_at(t + 3);
+			const typename FP::Desc dnx2 = FP::fetch_desc(pairs, nx2);
+			const uint32_t sv_nx2 = val_of(nx2);
+			ACM_STAMP(2);
+			phase_prio<true, PRIO_LDS_PASSES>();
+			run_lds_passes<C, PASS_ABL, true, FP::G, Gs...>(tile, lane, F32 ? (unsigned)ACMHIP_FMT_S16LE : fmt, carry_mem);
+			tile_barrier<MODE_WAVE>();
+			ACM_STAMP(3);
+			if constexpr (F32) {
+				float *out = discard ? reinterpret_cast<float *>(sink) : reinterpret_cast<float *>(pcm) + cur.pcm_off;
+				lean_store_f32<C, 64, NSTORE, ABL>(tile, lane, out);
+			} else {
+				typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+				v4u *out = discard ? reinterpret_cast<v4u *>(sink) : reinterpret_cast<v4u *>(reinterpret_cast<uint16_t *>(pcm) + cur.pcm_off);
+#pragma unroll
+				for (int k = 0; k < NSTORE; k++) {
+					const int vec = lane + k * 64;
+					const uint32_t *q = tile + lds_at<C::PS>((vec / PER_OWNER) * NJ_LAST) + (vec % PER_OWNER) * park_piece<NJ_LAST>();
+					const v4u o = { q[0], q[1], q[2], q[3] };
+#ifdef ACM_K3_ST_MOD            /* (A/B builds: another cache policy for the PCM stores - "", " sc1", " sc0 sc1", " sc1 nt" ...; the shipped one is nt) */
+					asm volatile("global_store_dwordx4 %0, %1, %2" ACM_K3_ST_MOD :: "v"((uint32_t)(vec * 16)), "v"(o), "s"(sgpr_u64(reinterpret_cast<uint64_t>(out))) : "memory");
+#else
+					__builtin_nontemporal_store(o, &out[vec]);
+#endif
+				}
+			}
+			ACM_STAMP(5);
+			phase_prio<true, PRIO_IDLE>();
+			k2_wait<F32 ? 2 * NSTORE : NSTORE>();           /* the next chunk's indices are here; only this chunk's PCM stores may still be on their way */
+			ACM_STAMP(6);
+			tile_barrier<MODE_WAVE>();                      /* (the next first pass overwrites what the stores have just read) */
+			if (!more)
+				break;
+			fresh = (nxt.flags & (ACM_TILE_FRESH | ACM_TILE_DISCARD)) != 0;
+			discard = (nxt.flags & ACM_TILE_DISCARD) != 0;
+			cur = nxt;
+			dcur = dnxt;
+			sv_cur = sv_nxt;
+			mode_cur = mode_nxt;
+			t = tn;
+			nxt = nx2;
+			dnxt = dnx2;
+			sv_nxt = sv_nx2;
+			mode_nxt = mode_of(nxt, dnxt, sv_nxt);
+			nx2 = nx3;
+		}
+		const uint32_t k = __builtin_amdgcn_readfirstlane(claimed);
+		if (k >= split_word(SPLIT_NCLAIMED))
+			break;                          /* the table is exhausted (the static split: it has no such part): nobody to wait for or to tell */
+		const uint32_t run = split_word(SPLIT_RUN_CHUNKS), end = split_word(SPLIT_NTILES);
+		t = split_word(SPLIT_NSTATIC) + k * run;
+		t_end = t + run < end ? t + run : end;
 	}
 #ifdef ACM_STAMPS
 	if (lane0 == 0 && vw < 2048)
 		for (int k = 0; k < 8; k++)
 			g_acm_stamps[vw][k] = acc_[k];
+	if (lane0 == 0 && vw < ACM_WAVE_STAMPS_MAX) {
+		unsigned long long c1, r1;
+		stamp_both(c1, r1);
+		unsigned long long *const o = g_acm_wave_stamps[vw];
+		o[0] = wave_c0_, o[1] = wave_r0_, o[2] = c1, o[3] = r1, o[4] = wave_chunks_, o[5] = stamp_where(), o[6] = wave_runs_, o[7] = 0;
+	}
 #endif
 }
 
@@ -3336,7 +3443,10 @@ constexpr Tile2Entry entry_k2mw()
  * The library ships ONE of them per level, the measured better one (profiles/r4_mfma_first_pass.txt, 2.1 Gsamples per level, one box:
  * level 8 equal, level 9 three stages +1.6 %, levels 10 / 11 / 12 four stages +5.5 / +6.6 / +5 %: one LDS pass, or one of its stages, less);
  * the other depth is a tuning build (-DACM_TUNING, chosen per process with ACM_K2M_G0=3|4) */
-struct Tile2MEntry { Tile2Entry e; int g0; };
+/* (chunk: the chunk kernel, which takes the split of its table - acmk_tile2m_split - and the claim word behind acm_tile2's arguments) */
+typedef void (*ChunkFn)(const AcmTile2 *, uint32_t, const int16_t *, const uint32_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned, uint32_t *, uint32_t,
+			uint32_t, uint32_t);
+struct Tile2MEntry { Tile2Entry e; int g0; ChunkFn chunk; };
 #ifdef ACM_TUNING
 #define ACM_K2M_ALT(...) __VA_ARGS__
 #else
@@ -3368,7 +3478,7 @@ constexpr int g_tile2m_default[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = { 3,
 template <int L, int... Gs>
 constexpr Tile2MEntry entry_k3()
 {
-	return Tile2MEntry{ Tile2Entry{ ACM_K_CHUNK<L, 0, Gs...>, 64 * FirstPassZ<L>::NW, FirstPassZ<L>::TR, 1 }, 6 };
+	return Tile2MEntry{ Tile2Entry{ nullptr, 64 * FirstPassZ<L>::NW, FirstPassZ<L>::TR, 1 }, 6, ACM_K_CHUNK<L, 0, Gs...> };
 }
 const Tile2MEntry g_chunk[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = {
 	/* level 7 (two classes per row: eight row walkers per matrix set, a lane's four outputs belong to two of them) was built, is bit-exact
@@ -3985,6 +4095,62 @@ extern "C" int acmk_tile2m_grid(uint32_t level, int cus)
 	return (cus > 0 ? cus : 256) * tile2m_entry(level).e.wg_per_cu;
 }
 
+/* How a launch of the chunk kernel hands its table of ntiles chunks to the W = acmk_tile2m_run_waves wavefronts (device-free: the launcher
+ * and the tests call it).  The first W * static_per chunks are static runs, wavefront w's the chunks [w * static_per, (w + 1) *
+ * static_per); the rest is cut into nclaimed runs of run_chunks (the last one may be shorter), run k at chunk W * static_per + k *
+ * run_chunks, which the wavefronts claim in ascending k as they come free.
+ * The rule: under the compiled-in policy of the level (g_claim_default: run_chunks - 0: the level keeps the static split - and the static
+ * share in thousandths of the table) a table is split this way from ACM_CLAIM_MIN_PER chunks per wavefront on; a policy set through
+ * acmk_tile2m_claim_config holds for every table of at least as many chunks as a launch has workgroups at most.  Either way static_per =
+ * floor(ntiles * share / 1000 / W), and a table that leaves nothing behind its static runs is not split.
+ * Every other table stays wholly static exactly as before: nclaimed = 0, run_chunks = 0, static_per = ceil(ntiles / W), one contiguous
+ * run per wavefront.  Returns 0, or -1 for a level without the chunk kernel */
+#define ACM_CLAIM_MIN_PER 32u
+#ifndef ACM_CLAIM_DEFAULTS
+#define ACM_CLAIM_DEFAULTS { 16, 900 }, { 16, 800 }, { 16, 800 }, { 16, 800 }, { 16, 900 }
+#endif
+/* (levels 8-12, measured on 1024 streams of 2 Mi samples, profiles/claimed_runs_notes.txt 2: the oldest wavefront of a SIMD is done
+ * with an equal share at 0.8 of the launch, so a fifth of the table is what there is to hand out; runs of 8 replay too many chunks, runs
+ * of 32 and more leave too long a tail) */
+static const struct { int run_chunks, static_permille; } g_claim_default[5] = { ACM_CLAIM_DEFAULTS };
+static int g_claim_run_chunks = -1, g_claim_static_permille = -1;         /* < 0: the level's default */
+
+extern "C" int acmk_tile2m_split(uint32_t level, int cus, uint32_t ntiles, uint32_t *static_per, uint32_t *run_chunks, uint32_t *nclaimed)
+{
+	const uint32_t W = (uint32_t)acmk_tile2m_run_waves(level, cus);
+	if (!W)
+		return -1;
+	const bool set = g_claim_run_chunks >= 0 || g_claim_static_permille >= 0;
+	const uint32_t R = (uint32_t)(g_claim_run_chunks >= 0 ? g_claim_run_chunks : g_claim_default[level - 8].run_chunks);
+	uint32_t share = (uint32_t)(g_claim_static_permille >= 0 ? g_claim_static_permille : g_claim_default[level - 8].static_permille);
+	if (share > 1000u)
+		share = 1000u;
+	*static_per = (ntiles + W - 1) / W;
+	*run_chunks = *nclaimed = 0;
+	if (!R || ntiles < (set ? (uint32_t)acmk_tile2m_grid(level, cus) : W * ACM_CLAIM_MIN_PER))
+		return 0;
+	const uint32_t sp = (uint32_t)((uint64_t)ntiles * share / 1000u / W);
+	const uint32_t rest = ntiles - W * sp;
+	if (!rest)
+		return 0;
+	*static_per = sp;
+	*run_chunks = R;
+	*nclaimed = (rest + R - 1) / R;
+	return 0;
+}
+
+/* process-wide policy for every level, for tests and sweeps: run_chunks (0: no claimed runs) and the static share in thousandths; a
+ * negative argument puts that value back to the levels' defaults.  Hands back what was set before (negative: the defaults) */
+extern "C" void acmk_tile2m_claim_config(int run_chunks, int static_permille, int *old_run_chunks, int *old_static_permille)
+{
+	if (old_run_chunks)
+		*old_run_chunks = g_claim_run_chunks;
+	if (old_static_permille)
+		*old_static_permille = g_claim_static_permille;
+	g_claim_run_chunks = run_chunks < 0 ? -1 : run_chunks;
+	g_claim_static_permille = static_permille < 0 ? -1 : static_permille;
+}
+
 extern "C" int acmk_tile2m_stages(uint32_t level)
 {
 	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
@@ -3994,11 +4160,11 @@ extern "C" int acmk_tile2m_stages(uint32_t level)
 
 #endif
 extern "C" int ACMK_OUT(acmk_launch_tile2m)(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
-				  const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream)
+				  const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, uint32_t *d_claim, void *stream)
 {
 #if !ACM_OUT_F32
 	if (fmt & ACMK_FMT_F32)
-		return acmk_launch_tile2m_f32(level, cus, d_tiles, ntiles, d_mform, d_pairs, d_hdr, d_pcm, d_sink, fmt & 3u, stream);
+		return acmk_launch_tile2m_f32(level, cus, d_tiles, ntiles, d_mform, d_pairs, d_hdr, d_pcm, d_sink, fmt & 3u, d_claim, stream);
 #endif
 	if (ntiles == 0)
 		return 0;
@@ -4010,6 +4176,16 @@ extern "C" int ACMK_OUT(acmk_launch_tile2m)(uint32_t level, int cus, const AcmTi
 	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * e.wg_per_cu);
 	if (grid > ntiles)
 		grid = ntiles;
+	if (const ChunkFn chunk = tile2m_entry(level).chunk) {
+		/* (d_claim: one zeroed word that no other launch in flight uses; the launch leaves it at zero again.  Null: the static split) */
+		uint32_t static_per = 0, run_chunks = 0, nclaimed = 0;
+		if (d_claim && acmk_tile2m_split(level, cus, ntiles, &static_per, &run_chunks, &nclaimed))
+			return -1;
+		hipLaunchKernelGGL(chunk, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
+				   reinterpret_cast<const uint32_t *>(d_pairs), d_hdr, d_pcm, d_sink, fmt, d_claim, static_per, run_chunks, nclaimed);
+		ACMK_CHECK_LAUNCH();
+		return 0;
+	}
 	hipLaunchKernelGGL(e.fn, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
 			   reinterpret_cast<const uint32_t *>(d_pairs), d_hdr, d_pcm, d_sink, fmt);
 	ACMK_CHECK_LAUNCH();

@@ -9,6 +9,9 @@ command line is dlopen()ed privately (its own device handle, plan and kernels - 
 pointers, so the same HBM buffers serve all of them), then the libraries are timed in interleaved rounds with
 acmhip_plan_time (HIP events on the launch stream).  After its first launch every library's PCM is compared with
 the first library's, word for word (CRC of the whole arena); timing-only builds are named in --allow-wrong.
+A library may be named with settings that hold around its launches only: lib.so@VAR=value,... sets environment variables (tuning
+builds), lib.so@claim=R:S the chunk kernel's claim policy (R chunks per claimed run, static share S in thousandths; 0:1000 = the
+static split) through acmk_tile2m_claim_config - one library can stand in the list once per policy.
 Prints one line per library: median launch ms, frac of the 8 TB/s roofline (4 B/sample), per-round values.
 """
 import argparse
@@ -80,6 +83,12 @@ class Variant:
 
     def setenv(self, on):
         for k, v in self.env.items():
+            if k == "claim":
+                # lib.so@claim=16:800: the chunk kernel's claim policy (chunks per claimed run : static share in thousandths) through the
+                # library's own override, acmk_tile2m_claim_config, in force around this variant's launches (the split is made at launch)
+                r, p = (int(x) for x in v.split(":"))
+                self.L.acmk_tile2m_claim_config(r if on else -1, p if on else -1, None, None)
+                continue
             if on:
                 os.environ[k] = v
             else:
