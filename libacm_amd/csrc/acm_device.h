@@ -106,7 +106,7 @@ struct AcmDenseRow {
 	uint64_t count;        /* 0: the row is all zeros and src is not read */
 };
 
-/* levels the fused tile kernel covers; its tile geometry is owned by acm_kernels.hip (acmk_fused_tile_rows) */
+/* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
 #define ACM_K1_MAX_LEVEL 12
 /* levels the lean tile kernel (acm_tile2) covers (measured: 32 KB tiles lose to the 64-128 KB tiles of acm_fused_tile from level 10 on) */
@@ -159,18 +159,28 @@ int acmhip_aux_stream(acmhip_device *dev, int k, void **out);    /* batch pipeli
 int acmhip_report_hip(int hip_error, const char *what);
 void acmhip_set_error_text(const char *text);                    /* what acmhip_last_error() returns on this thread */          /* records the text, returns ACMHIP_ERR_HIP */
 
-/* launchers implemented in acm_kernels.hip; `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
+/* Two kinds of acmk_* functions.  The ones that launch nothing - a build's tile rows, threads, grid, first-pass depth, lead-in, packed
+ * slots, the split of a chunk table, what the device parser accepts and where it cuts - live in acm_kernel_geo.cpp: plain C++ over the
+ * tables of acm_kernel_geo.h, linkable without a device or a kernel.  The launchers (acmk_launch_*, acmk_warmup) live with their kernels in
+ * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip and acm_dense.hip, and take block size and grid from the queries.
+ * `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
  * d_pcm (and d_sink) then hold floats and the streams' pcm_off / n_emit count them (acmhip_plan_launch_f32) */
 #define ACMK_FMT_F32 0x100u
+/* one number over every table of acm_kernel_geo.h, as the planner's half (acm_kernel_geo.cpp) and the kernels' half (acm_kernels.hip) of
+ * the library were compiled: acmhip_device_open refuses a library in which they differ */
+uint64_t acmk_geo_digest(void);
+uint64_t acmk_geo_digest_kernels(void);
 int acmk_tuning_build(void);                                     /* 1 if the library was built with -DACM_TUNING (its environment switches are live) */
 int acmk_warmup(void *stream);                                   /* an empty launch: makes the runtime load the kernels' code object */
 int acmk_fused_variants(void);                                   /* number of fused-kernel variants built in */
 int acmk_fused_tile_rows(uint32_t level, int variant);           /* tile rows incl. the 2 halo rows, 0 if unsupported */
 int acmk_fused_has_carry(uint32_t level, int variant);           /* does a carry-mode build of this geometry exist? */
+int acmk_fused_threads(uint32_t level, int variant);             /* threads of a workgroup */
 int acmk_fused_grid(uint32_t level, int variant, int cus);       /* persistent workgroups the launch uses at most */
 int acmk_launch_fused(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
 		      uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_tile2_rows(uint32_t level);                            /* rows per acm_tile2 tile, 0 if the level is not covered */
+int acmk_tile2_threads(uint32_t level);
 int acmk_tile2_grid(uint32_t level, int cus);
 #define ACM_K2_SINK_BYTES 65536                               /* >= one tile of PCM: where lead-in tiles put theirs */
 #define ACM_K2_SINK_F32_BYTES (2 * ACM_K2_SINK_BYTES)         /* ... of float32 PCM */
@@ -183,14 +193,16 @@ int acmk_tile2p_group_rows(uint32_t level);                     /* rows that sha
 int acmk_tile2p_slots(uint32_t level);                          /* chunk descriptors per tile: waves x descriptors per wave */
 int acmk_tile2p_waves(uint32_t level);
 int acmk_tile2p_pad_shift(uint32_t level);                      /* the tile's LDS rows carry one pad dword per 2^shift elements */
+int acmk_tile2p_grid(uint32_t level, int cus);                  /* persistent workgroups of its launch at most */
 int acmk_launch_tile2p(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const acmhip_packed_chunk *d_chunks, const uint8_t *d_blob,
 		       const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream);
 /* the byte-plane staged form: the same tile records as acm_tile2 except that idx_off is the pair-table entry of the row pair in front of the tile */
 int acmk_tile2m_rows(uint32_t level);                           /* = acmk_tile2_rows, 0 if the level has no such build */
+int acmk_tile2m_threads(uint32_t level);
 int acmk_tile2m_lead_in(uint32_t level);                        /* tiles of this build in front of a window into a stream (ACM_TILE_DISCARD records) */
 int acmk_tile2m_run_waves(uint32_t level, int cus);             /* wavefronts that share a launch's table (the chunk kernel), else 0 */
 /* how those W wavefronts share a table of ntiles chunks: wavefront w takes the chunks [w * static_per, (w + 1) * static_per) - below the
- * threshold (acm_kernels.hip states the rule) that is the whole table, static_per = ceil(ntiles / W), nclaimed = 0, as ever -, and the
+ * threshold (acm_kernel_geo.cpp states the rule) that is the whole table, static_per = ceil(ntiles / W), nclaimed = 0, as ever -, and the
  * chunks behind W * static_per are nclaimed runs of run_chunks (the last one may be shorter) which the wavefronts claim in ascending
  * order as they come free.  Device-free.  -1: the level has no chunk kernel */
 int acmk_tile2m_split(uint32_t level, int cus, uint32_t ntiles, uint32_t *static_per, uint32_t *run_chunks, uint32_t *nclaimed);
@@ -198,7 +210,8 @@ int acmk_tile2m_split(uint32_t level, int cus, uint32_t ntiles, uint32_t *static
  * and the static share in thousandths; a negative argument restores the default.  Hands back the values in force before (negative: default) */
 void acmk_tile2m_claim_config(int run_chunks, int static_permille, int *old_run_chunks, int *old_static_permille);
 int acmk_tile2m_grid(uint32_t level, int cus);                  /* persistent workgroups of its launch at most */
-int acmk_tile2m_stages(uint32_t level);                         /* stages of its first pass (3 or 4): the form keeps 2^stages columns of a residue class side by side */
+int acmk_tile2m_stages(uint32_t level);                         /* stages of the first pass of the build this process uses (3, 4 or 6): the form keeps 2^stages columns of a
+                                                                 * residue class side by side, and acmk_launch_tile2m picks its kernel by it */
 /* d_claim (the chunk kernel; null: the static split whatever the table's size): ONE zeroed word that the launch's wavefronts count their
  * claims in and leave at zero again.  Two launches that may run at the same time need a word each; launches on one stream - all launches of
  * a plan: it launches on its device's one stream - follow each other and share one */
@@ -209,12 +222,15 @@ int acmk_launch_unpack(const AcmDevStream *d_streams, const uint32_t *d_list, ui
 int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
 		       uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, void *stream);   /* levels 13-15: unpack + level-12 stages */
 int acmk_plane_tile_rows(void);                                 /* tile rows (incl. 2 halo rows) of the level-12 plane kernel */
+int acmk_plane_threads(void);
 int acmk_plane_grid(int cus);                                   /* persistent workgroups of that kernel */
 int acmk_launch_fused_plane(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
 			    const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_patch(const AcmDevPatch *d_patches, uint64_t n, int32_t *d_x, void *stream);
 int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
 		      uint32_t level, uint32_t k, const int32_t *d_in, int32_t *d_out, uint32_t shift, void *stream);
+/* acm_parse.hip's launchers; acmk_parse_supported, acmk_stripe_bound and acmk_range_bound: acm_kernel_geo.cpp (acm_parse_bounds.h is the text
+ * the kernels and the host share) */
 int acmk_parse_supported(uint32_t level, uint32_t rows, uint64_t file_len, uint64_t blocks);
 /* d_marks (here and in the two launchers below; may be null): the block index as a by-product of the walk (acm_batch_decode_indexed) - an arena
  * of acm_block_mark indexed like d_hdr; every block the walk completes leaves d_marks[hdr_off + b] = { its first bit, val, pwr }.  The entry

@@ -160,6 +160,13 @@ extern "C" int acmhip_device_open(int ordinal, void *hip_stream, acmhip_device *
 {
 	if (!out)
 		return ACMHIP_ERR_ARG;
+	/* a library whose kernels and whose planner were compiled with different -D flags (profiles/build_variant.sh) would cut tables for
+	 * other tiles than its kernels walk */
+	if (acmk_geo_digest() != acmk_geo_digest_kernels()) {
+		set_err("mixed build: the kernels were compiled for another launch geometry than the planner (acm_kernel_geo.h digest %016llx, kernels %016llx)",
+			(unsigned long long)acmk_geo_digest(), (unsigned long long)acmk_geo_digest_kernels());
+		return ACMHIP_ERR_ARG;
+	}
 	int n = acmhip_device_count();
 	if (n <= 0) {
 		set_err("no usable HIP device (hipGetDeviceCount found none); this library has no CPU synthesis path");

@@ -44,6 +44,7 @@
 #include <utility>
 
 #include "acm_device.h"
+#include "acm_kernel_geo.h"     /* every build's tile, threads and workgroups per CU: the tables the host's queries answer from */
 
 #ifndef ACM_L14_GROUPS
 #define ACM_L14_GROUPS 3, 3, 3, 3, 2
@@ -422,20 +423,8 @@ ACM_K_SMALL(const AcmDevStream *__restrict__ streams, const uint32_t *__restrict
 // ---------------------------------------------------------------------------
 // fused tile kernel
 // ---------------------------------------------------------------------------
-/* tile configuration: level, threads per workgroup, tile elements held in LDS */
-template <int L_, int NT_, int NELEM_>
-struct TileCfg {
-	static constexpr int L = L_;
-	static constexpr int NT = NT_;
-	static constexpr int NELEM = NELEM_;
-	static constexpr int COLS = 1 << L_;
-	static constexpr int TR = NELEM_ / COLS;          // tile rows incl. the 2 halo rows
-	static constexpr int NJ_LAST = NELEM_ / NT_;      // samples per thread in the last pass
-	static constexpr int PS = NJ_LAST >= 64 ? 6 : 5;  // LDS pad: one dword per 2^PS elements (= one last-pass walk)
-	static_assert(NJ_LAST == 64 || NJ_LAST == 32 || NJ_LAST == 128, "walk length of the last pass");
-	static_assert(TR >= 1, "whole rows");
-	static constexpr bool ROW_PAIRS = TR >= 2 && (TR % 2) == 0;     /* what the first passes fed from HBM work on (the halo flavour of acm_fused_tile needs four rows: two of them are halo) */
-};
+/* tile configuration (acm_kernel_geo.h): level, threads per workgroup, tile elements held in LDS */
+using acm_geo::TileCfg;
 
 /* t - 2*z: one VALU op when 25 result bits suffice (level <= 9: the write-out
  * only looks at bits [level, level+16) and every op here is add/shift, so bit
@@ -1288,62 +1277,46 @@ ACM_K_FUSED(const AcmDevStream *__restrict__ streams, const AcmTile *__restrict_
 #endif
 }
 
-/*
- * Kernel variants (ACM_K1_VARIANT=n picks one; tuning aid, see profiles/sweep_variants.py):
- *   0  default: per level the fastest measured geometry
- *   1  256 threads, 16K-element tiles, 2-byte first-pass loads (64 samples per thread per pass)
- *   2  512 threads (32 samples per thread per pass, 16 waves per CU)
- *   3  256 threads on half-size tiles (4 workgroups per CU)
- *   4  as 1 with 4-byte first-pass loads (two adjacent columns per lane)
- *   5  as 1 with fewer, deeper LDS passes
- *   6, 7  alternative stage groupings;  8  128-thread workgroups (128 samples per thread per pass)
- */
+/* The builds of a variant (acm_kernel_geo.h: FusedBuild<variant, level> - the tile, W and whether the geometry has a carry-mode build) with
+ * their stage groupings; fn_carry: the carry-mode build (no halo rows; see ACM_TILE_*), null where the variant has none */
+using acm_geo::FusedBuild;
+using acm_geo::NVARIANTS;
 struct FusedEntry {
 	void (*fn)(const AcmDevStream *, const AcmTile *, uint32_t, const int16_t *, const acmhip_blkhdr *, int16_t *, unsigned);
-	int threads;
-	int tile_rows;
-	int wg_per_cu;       /* resident workgroups per CU (LDS-limited) */
 	void (*fn_carry)(const AcmDevStream *, const AcmTile *, uint32_t, const int16_t *, const acmhip_blkhdr *, int16_t *, unsigned);
 };
 
-template <class C, int W, int... Gs>
-constexpr FusedEntry entry() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+template <class B, int ABL, int PAIR, int... Gs>
+constexpr FusedEntry fused_entry()
+{
+	if constexpr (B::CARRY)
+		return FusedEntry{ ACM_K_FUSED<typename B::C, B::W, ABL, PAIR, false, Gs...>, ACM_K_FUSED<typename B::C, B::W, ABL, PAIR, true, Gs...> };
+	else
+		return FusedEntry{ ACM_K_FUSED<typename B::C, B::W, ABL, PAIR, false, Gs...>, nullptr };
+}
+template <class B, int... Gs>
+constexpr FusedEntry entry() { return fused_entry<B, 0, 1, Gs...>(); }
 /* same with two adjacent columns per lane in the first pass (4-byte HBM loads) */
-template <class C, int W, int... Gs>
-constexpr FusedEntry entry2() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
-/* ... plus the carry-mode build of the same geometry (no halo rows; see ACM_TILE_*) */
-template <class C, int W, int... Gs>
-constexpr FusedEntry entry2c() { return FusedEntry{ ACM_K_FUSED<C, W, 0, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT,
-						     ACM_K_FUSED<C, W, 0, 2, true, Gs...> }; }
+template <class B, int... Gs>
+constexpr FusedEntry entry2() { return fused_entry<B, 0, 2, Gs...>(); }
 #ifdef ACM_ABLATION
 /* timing-only builds of the level-7 and level-9 kernels with parts removed (wrong output by design) */
-template <class C, int W, int ABL, int... Gs>
-constexpr FusedEntry abl2() { return FusedEntry{ ACM_K_FUSED<C, W, ABL, 2, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
-template <class C, int W, int ABL, int... Gs>
-constexpr FusedEntry abl() { return FusedEntry{ ACM_K_FUSED<C, W, ABL, 1, false, Gs...>, C::NT, C::TR, W * 256 / C::NT, nullptr }; }
+template <class B, int ABL, int... Gs>
+constexpr FusedEntry abl2() { return fused_entry<B, ABL, 2, Gs...>(); }
+template <class B, int ABL, int... Gs>
+constexpr FusedEntry abl() { return fused_entry<B, ABL, 1, Gs...>(); }
 #endif
 
-/* variants 1.. are tuning aids (geometry sweeps: -DACM_TUNING; timing-only ablations: -DACM_ABLATION, which implies it) */
-#if defined(ACM_ABLATION) && !defined(ACM_TUNING)
-#define ACM_TUNING 1
-#endif
-#ifdef ACM_ABLATION
-constexpr int NVARIANTS = 20;
-#elif defined(ACM_TUNING)
-constexpr int NVARIANTS = 10;
-#else
-constexpr int NVARIANTS = 1;
-#endif
 const FusedEntry g_fused[NVARIANTS][ACM_K1_MAX_LEVEL - ACM_K1_MIN_LEVEL + 1] = {
 	{	/* variant 0 (default): per level the fastest measured geometry (profiles/sweep_variants.py) */
-		entry2c<TileCfg<5, 128, 8192>, 2, 2, 3>(),
-		entry2c<TileCfg<6, 256, 16384>, 2, 2, 2, 2>(),
-		entry2c<TileCfg<7, 256, 16384>, 2, 2, 2, 3>(),
-		entry2c<TileCfg<8, 256, 16384>, 2, 3, 3, 2>(),
-		entry2c<TileCfg<9, 256, 16384>, 2, 3, 3, 3>(),
-		entry2c<TileCfg<10, 256, 16384>, 2, 3, 3, 4>(),
-		entry2c<TileCfg<11, 512, 32768>, 2, 3, 4, 4>(),
-		entry2c<TileCfg<12, 512, 32768>, 2, 3, 3, 3, 3>(),
+		entry2<FusedBuild<0, 5>, 2, 3>(),
+		entry2<FusedBuild<0, 6>, 2, 2, 2>(),
+		entry2<FusedBuild<0, 7>, 2, 2, 3>(),
+		entry2<FusedBuild<0, 8>, 3, 3, 2>(),
+		entry2<FusedBuild<0, 9>, 3, 3, 3>(),
+		entry2<FusedBuild<0, 10>, 3, 3, 4>(),
+		entry2<FusedBuild<0, 11>, 3, 4, 4>(),
+		entry2<FusedBuild<0, 12>, 3, 3, 3, 3>(),
 	},
 #include "acm_kernels_tuning.inc"     /* variants 1.. (-DACM_TUNING) and the timing-only ablation builds (-DACM_ABLATION) */
 };
@@ -2386,23 +2359,12 @@ ACM_K_TILE2(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int
 
 template <int L_>
 struct FirstPassZ {
-	/* what ONE wavefront holds in LDS: 2048 elements (32 per lane in the last pass), or one row where a row is longer (levels 12 and 13:
-	 * 4096 / 8192 elements, eight / four wavefronts per workgroup with twice / four times the registers each) */
-	static constexpr int NELEM = (1 << L_) > 2048 ? (1 << L_) : 2048;
-	using C = TileCfg<L_, 64, NELEM>;
-	static constexpr int NW = 32768 / NELEM;                /* wavefronts per workgroup = per CU */
-	static constexpr int L = L_, COLS = C::COLS, TR = C::TR, PS = C::PS;
-	static constexpr int G = 6, QN = 1 << G, SIGMA = COLS / QN;            /* QN columns of a residue class per row, SIGMA classes */
-	static_assert(SIGMA >= 2 && TR >= 1, "sixteen instances per matrix instruction: sixteen classes of one row, or all the classes of 2 / 4 / 8 rows");
-	static constexpr int RR = SIGMA >= 16 ? 1 : 16 / SIGMA; /* row walkers among the sixteen instances */
-	static constexpr int NG = SIGMA >= 16 ? SIGMA / 16 : 1; /* groups of sixteen classes per row */
-	static constexpr int NSW = TR / RR;                     /* rows a walker walks */
-	static constexpr int NX = NSW + 2;                      /* rows a lane loads per group: its walk and the two rows in front of it */
-	static constexpr int NSET = NSW * NG;                   /* matrix "sets" (sixteen instances x 64 outputs) per chunk: 2048 / 1024 */
-	static constexpr int NE = (((TR & 1) + (RR - 1) * NSW + NX - 1) >> 1) + 1;      /* pair-table entries a chunk may read, from the pair in front of it on
-										 * (a chunk of one row may start on the second row of a pair) */
-	static constexpr int NM = QN / 16;                      /* output tiles per row */
-	static_assert(NSW * RR == TR && NSET * 1024 == NELEM, "a chunk is whole sets");
+	/* what ONE wavefront works on - the chunk, its walkers and sets, which rows stay in registers: acm_kernel_geo.h, where the planner reads it too */
+	using Geo = acm_geo::ChunkGeo<L_>;
+	using C = typename Geo::C;
+	static constexpr int NELEM = Geo::NELEM, NW = Geo::NW, L = L_, COLS = Geo::COLS, TR = Geo::TR, PS = Geo::PS, G = Geo::G, QN = Geo::QN, SIGMA = Geo::SIGMA;
+	static constexpr int RR = Geo::RR, NG = Geo::NG, NSW = Geo::NSW, NX = Geo::NX, NSET = Geo::NSET, NE = Geo::NE, NM = Geo::NM;
+	static constexpr bool HISTORY_IN_REGISTERS = Geo::HISTORY_IN_REGISTERS, HISTORY_BY_DPP = Geo::HISTORY_BY_DPP, KEEPS_ROWS = Geo::KEEPS_ROWS;
 	static constexpr int VARIANT = StageKind<L, G - 1>::N ? 0 : 1;          /* a P stage leaves odd positions negated */
 	/*
 	 * Which class instance i of a set stands for.  A lane receives four consecutive instances of one output (instances 4 h .. 4 h + 3,
@@ -2478,19 +2440,7 @@ struct FirstPassZ {
 	/* the loads of one chunk: lane l = (instance i = l % 16: class and walker; columns 16 (l / 16) .. + 15 of the class) asks for 16 low bytes
 	 * and, 64 bytes on, 16 high bytes of each of its rows (a pair at 8 bits has no high bytes: what comes back instead is never
 	 * used, see run_t()).  odd: the chunk starts on the second row of a pair (chunks of one row only) */
-	/* KEEP (one walker only: the rows in front of a lane's walk are rows the SAME lane loaded for the chunk in front): only the walk's own
-	 * rows are asked for, the two rows in front stay in their registers (shift_history) - a third (level 11) or half of the requests */
-	static constexpr bool HISTORY_IN_REGISTERS = RR == 1;
-	/* two walkers of two rows each (level 9): the rows in front of walker 1 are walker 0's own rows of the same chunk, the rows in front of
-	 * walker 0 are walker 1's own rows of the chunk before - both sit eight lanes away in the same row of sixteen, one v_mov_b32_dpp per
-	 * register instead of a second request for bytes the partner lane has just loaded (half the load instructions of a chunk) */
-#ifndef ACM_K3_DPP_HISTORY
-#define ACM_K3_DPP_HISTORY 1
-#endif
-	/* (round 6: the same with four walkers of two rows each, level 8 - walker w's rows in front are walker w - 1's own, SIGMA lanes down
-	 * the row of sixteen; walker 0's are the last walker's of the chunk before, 16 - SIGMA lanes up) */
-	static constexpr bool HISTORY_BY_DPP = ACM_K3_DPP_HISTORY && RR >= 2 && NSW == 2 && RR * SIGMA == 16 && SIGMA >= 4;
-	static constexpr bool KEEPS_ROWS = HISTORY_IN_REGISTERS || HISTORY_BY_DPP;
+	/* (HISTORY_IN_REGISTERS, HISTORY_BY_DPP, KEEPS_ROWS: ChunkGeo says when the rows in front of a walk are not asked for again) */
 	template <int CTRL, int BANKS>
 	static __device__ __forceinline__ v4u_t dpp4(const v4u_t old, const v4u_t src)
 	{
@@ -3365,154 +3315,98 @@ ACM_K_CHUNK(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const int
 #endif
 }
 
-struct Tile2Entry {
-	typedef void (*Fn)(const AcmTile2 *, uint32_t, const int16_t *, const uint32_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned);
-	Fn fn;
-	int threads, tile_rows, wg_per_cu;
-};
-template <class C, int... Gs>
-constexpr Tile2Entry entry_k2()
+/* The tables below hold kernels and nothing else: a build's tile, threads and workgroups per CU come from its trait in acm_kernel_geo.h
+ * (Tile2Build<level>, Tile2MBuild<level, first-pass depth>, Tile2PBuild<level>; the comments on why a geometry was chosen are there),
+ * what stands here is the stage grouping.  A launcher asks acm_kernel_geo.cpp's queries, which read the same tables, for block and grid */
+using acm_geo::Tile2Build;
+using acm_geo::Tile2MBuild;
+typedef void (*Tile2Fn)(const AcmTile2 *, uint32_t, const int16_t *, const uint32_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned);
+template <class B, int... Gs>
+constexpr Tile2Fn entry_k2()
 {
-	return Tile2Entry{ ACM_K_TILE2<C, 4, 0, false, Gs...>, C::NT, C::TR, 1024 / C::NT };
-}
-/* bigger tiles: WPC workgroups per CU */
-template <class C, int WPC, int... Gs>
-constexpr Tile2Entry entry_k2w()
-{
-	return Tile2Entry{ ACM_K_TILE2<C, WPC * C::NT / 256, 0, false, Gs...>, C::NT, C::TR, WPC };
+	return ACM_K_TILE2<typename B::C, B::W, 0, false, Gs...>;
 }
 #ifdef ACM_ABLATION
 /* timing-only builds of the level-9 kernel with parts removed (wrong output by design): ACM_K2_ABL=<mask> */
 template <int ABL>
-constexpr Tile2Entry abl_k2() { return Tile2Entry{ ACM_K_TILE2<TileCfg<9, 256, 8192>, 4, ABL, false, 3, 3, 3>, 256, 16, 4 }; }
-const struct { int mask; Tile2Entry e; } g_tile2_abl[] = {
+constexpr Tile2Fn abl_k2() { return ACM_K_TILE2<Tile2Build<9>::C, Tile2Build<9>::W, ABL, false, 3, 3, 3>; }
+const struct { int mask; Tile2Fn fn; } g_tile2_abl[] = {
 	{ 1, abl_k2<1>() }, { 2, abl_k2<2>() }, { 4, abl_k2<4>() }, { 6, abl_k2<6>() }, { 8, abl_k2<8>() }, { 16, abl_k2<16>() },
 	{ 17, abl_k2<17>() }, { 23, abl_k2<23>() }, { 32, abl_k2<32>() }, { 25, abl_k2<25>() }, { 31, abl_k2<31>() }, { 12, abl_k2<12>() },
 };
 #endif
-/* per level the fastest measured geometry and stage grouping (profiles/r2_sweep_levels.txt): 32 KB tiles at four workgroups
- * per CU up to level 10, 64 KB tiles of 512 threads (two workgroups, still four waves per SIMD) above; passes of at most
- * three stages, because with 32-element walks the warm-up of a four-stage pass costs as much as a pass */
-/* per level the fastest measured geometry and stage grouping with the phase priorities on (profiles/r2_sweep_levels.txt;
- * alternatives built and timed on one box, all CRC-verified: level 7 (2,2,3) and (2,3,2) -2 %; level 8 (2,3,3), (3,2,3)
- * equal; level 9 as 64 KB tiles of 512 threads -0.4 %; level 10 (2,3,3,2) -1.5 %, (2,2,3,3) -2.5 %, 64 KB tiles -1.5 %;
- * level 11 as 64 KB tiles of 512 threads, two per CU, (2,3,3,3): -2.7 %, which had been the best without priorities) */
-const Tile2Entry g_tile2[ACM_K2_MAX_LEVEL - ACM_K2_MIN_LEVEL + 1] = {
-	entry_k2<TileCfg<6, 256, 8192>, 2, 2, 2>(),
-	entry_k2<TileCfg<7, 256, 8192>, 3, 2, 2>(),
-	entry_k2<TileCfg<8, 256, 8192>, 3, 3, 2>(),
-	entry_k2<TileCfg<9, 256, 8192>, 3, 3, 3>(),
-	entry_k2<TileCfg<10, 256, 8192>, 3, 3, 2, 2>(),
-	entry_k2<TileCfg<11, 256, 8192>, 3, 3, 3, 2>(),
-	entry_k2w<TileCfg<12, 512, 16384>, 2, 3, 3, 3, 3>(),   /* two 64 KB tiles per CU (127 registers): +19 % over one 128 KB tile, whose waves are all in the same phase */
-	/* level 13: four rows are 128 KB - one workgroup of sixteen waves per CU (still four per SIMD), no plane, no prefix sweep:
-	 * 4 B of HBM traffic per sample instead of the 12 B of the prefix + plane pair.  A two-stage first pass makes the
-	 * whole tile ONE segment (1024 threads x two adjacent columns = the 2048 residues of stride 2048): two warm-up rows per
-	 * four rows instead of per two, 24 instead of 32 prefetch registers: +8 % over (3,2,3,3,2) (2.94 against 3.18 ms for
-	 * 2.1 Gsamples; at levels 10 and 11 the same trade loses 3 %: an LDS-pass stage costs more than a first-pass stage) */
-	entry_k2w<TileCfg<13, 1024, 32768>, 1, ACM_L13_GROUPS>(),
-	/* level 14: one row pair is the 128 KB tile (the first pass's body is two rows: the least a tile can be), 155 KB of LDS
-	 * with the carries of the first LDS pass (two bodies of stride 256 = 4096 elements) */
-	entry_k2w<TileCfg<14, 1024, 32768>, 1, ACM_L14_GROUPS>(),
+/* per level the fastest measured stage grouping: passes of at most three stages, because with 32-element walks the warm-up of a four-stage
+ * pass costs as much as a pass (level 13: a two-stage first pass makes the whole tile ONE segment) */
+const Tile2Fn g_tile2[ACM_K2_MAX_LEVEL - ACM_K2_MIN_LEVEL + 1] = {
+	entry_k2<Tile2Build<6>, 2, 2, 2>(),
+	entry_k2<Tile2Build<7>, 3, 2, 2>(),
+	entry_k2<Tile2Build<8>, 3, 3, 2>(),
+	entry_k2<Tile2Build<9>, 3, 3, 3>(),
+	entry_k2<Tile2Build<10>, 3, 3, 2, 2>(),
+	entry_k2<Tile2Build<11>, 3, 3, 3, 2>(),
+	entry_k2<Tile2Build<12>, 3, 3, 3, 3>(),
+	entry_k2<Tile2Build<13>, ACM_L13_GROUPS>(),
+	entry_k2<Tile2Build<14>, ACM_L14_GROUPS>(),
 };
-inline const Tile2Entry &tile2_entry(uint32_t level)
+/* the same geometries with the first pass on the matrix cores (levels whose first pass has three stages): the first pass of B::G0 stages,
+ * then the LDS passes Gs */
+template <class B, int... Gs>
+constexpr Tile2Fn entry_k2m()
 {
-	return g_tile2[level - ACM_K2_MIN_LEVEL];
+	return ACM_K_TILE2<typename B::C, B::W, 0, true, B::G0, Gs...>;
 }
-/* the same geometries with the first pass on the matrix cores (levels whose first pass has three stages) */
-template <class C, int... Gs>
-constexpr Tile2Entry entry_k2m()
-{
-	return Tile2Entry{ ACM_K_TILE2<C, 4, 0, true, Gs...>, C::NT, C::TR, 1024 / C::NT };
-}
-template <class C, int WPC, int... Gs>
-constexpr Tile2Entry entry_k2mw()
-{
-	return Tile2Entry{ ACM_K_TILE2<C, WPC * C::NT / 256, 0, true, Gs...>, C::NT, C::TR, WPC };
-}
-#ifndef ACM_K2M_L11
-#define ACM_K2M_L11 entry_k2m<TileCfg<11, 256, 8192>, 4, 3, 2, 2>(), 4
+/* (what an override of a tile - ACM_K2M_L11_TILE ..., acm_kernel_geo.h - needs beside it: the LDS passes behind the first pass) */
+#ifndef ACM_K2M_L11_GROUPS
+#define ACM_K2M_L11_GROUPS 3, 2, 2
 #endif
-#ifndef ACM_K2M_L12
-#define ACM_K2M_L12 entry_k2mw<TileCfg<12, 512, 16384>, 2, 4, 3, 3, 2>(), 4
+#ifndef ACM_K2M_L12_GROUPS
+#define ACM_K2M_L12_GROUPS 3, 3, 2
 #endif
-#ifndef ACM_K2M_L13
-#define ACM_K2M_L13 entry_k2mw<TileCfg<13, 512, 16384>, 2, 4, 3, 3, 3>(), 4
+#ifndef ACM_K2M_L13_GROUPS
+#define ACM_K2M_L13_GROUPS 3, 3, 3
 #endif
-/* [level][first pass of three / four stages]; the staged form differs between the two (8 or 16 columns of a residue class side by side).
- * The library ships ONE of them per level, the measured better one (profiles/r4_mfma_first_pass.txt, 2.1 Gsamples per level, one box:
- * level 8 equal, level 9 three stages +1.6 %, levels 10 / 11 / 12 four stages +5.5 / +6.6 / +5 %: one LDS pass, or one of its stages, less);
- * the other depth is a tuning build (-DACM_TUNING, chosen per process with ACM_K2M_G0=3|4) */
-/* (chunk: the chunk kernel, which takes the split of its table - acmk_tile2m_split - and the claim word behind acm_tile2's arguments) */
-typedef void (*ChunkFn)(const AcmTile2 *, uint32_t, const int16_t *, const uint32_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned, uint32_t *, uint32_t,
-			uint32_t, uint32_t);
-struct Tile2MEntry { Tile2Entry e; int g0; ChunkFn chunk; };
+#ifndef ACM_K3_L13_GROUPS
+#define ACM_K3_L13_GROUPS 4, 3
+#endif
+#ifndef ACM_K3_L14_GROUPS
+#define ACM_K3_L14_GROUPS 3, 3, 2
+#endif
+/* [level][first pass of three / four stages]: acm_tile2's matrix builds.  The library ships one depth per level, the other is a tuning build */
 #ifdef ACM_TUNING
 #define ACM_K2M_ALT(...) __VA_ARGS__
 #else
-#define ACM_K2M_ALT(...) Tile2Entry{ nullptr, 0, 0, 0 }, 0
+#define ACM_K2M_ALT(...) nullptr
 #endif
-const Tile2MEntry g_tile2m[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1][2] = {
-	{ { entry_k2m<TileCfg<7, 256, 8192>, 3, 2, 2>(), 3 }, { Tile2Entry{ nullptr, 0, 0, 0 }, 0 } },        /* 8 residue classes of stride 8: less than one operand tile */
-	{ { entry_k2m<TileCfg<8, 256, 8192>, 3, 3, 2>(), 3 }, { ACM_K2M_ALT(entry_k2m<TileCfg<8, 256, 8192>, 4, 2, 2>(), 4) } },
-	{ { entry_k2m<TileCfg<9, 256, 8192>, 3, 3, 3>(), 3 }, { ACM_K2M_ALT(entry_k2m<TileCfg<9, 256, 8192>, 4, 3, 2>(), 4) } },
-	{ { ACM_K2M_ALT(entry_k2m<TileCfg<10, 256, 8192>, 3, 3, 2, 2>(), 3) }, { entry_k2m<TileCfg<10, 256, 8192>, 4, 3, 3>(), 4 } },
-	{ { ACM_K2M_ALT(entry_k2m<TileCfg<11, 256, 8192>, 3, 3, 3, 2>(), 3) }, { ACM_K2M_L11 } },
-	{ { ACM_K2M_ALT(entry_k2mw<TileCfg<12, 512, 16384>, 2, 3, 3, 3, 3>(), 3) }, { ACM_K2M_L12 } },
-	/* level 13: the vector-ALU build needs 128 KB tiles (its first pass re-runs two rows per segment); here the rows in front cost a second
-	 * read through L2 and nothing else, so a tile may be one row pair.  Level 14: a row pair IS 128 KB, sixteen waves of 128 registers;
-	 * (4,3,3,2,2) and (4,3,2,3,2) spill seven of them, (4,2,3,3,2) none */
-	{ { Tile2Entry{ nullptr, 0, 0, 0 }, 0 }, { ACM_K2M_L13 } },
-	{ { Tile2Entry{ nullptr, 0, 0, 0 }, 0 }, { entry_k2mw<TileCfg<14, 1024, 32768>, 1, 4, 2, 3, 3, 2>(), 4 } },
+const Tile2Fn g_tile2m[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1][2] = {
+	{ entry_k2m<Tile2MBuild<7, 3>, 2, 2>(), nullptr },
+	{ entry_k2m<Tile2MBuild<8, 3>, 3, 2>(), ACM_K2M_ALT(entry_k2m<Tile2MBuild<8, 4>, 2, 2>()) },
+	{ entry_k2m<Tile2MBuild<9, 3>, 3, 3>(), ACM_K2M_ALT(entry_k2m<Tile2MBuild<9, 4>, 3, 2>()) },
+	{ ACM_K2M_ALT(entry_k2m<Tile2MBuild<10, 3>, 3, 2, 2>()), entry_k2m<Tile2MBuild<10, 4>, 3, 3>() },
+	{ ACM_K2M_ALT(entry_k2m<Tile2MBuild<11, 3>, 3, 3, 2>()), entry_k2m<Tile2MBuild<11, 4>, ACM_K2M_L11_GROUPS>() },
+	{ ACM_K2M_ALT(entry_k2m<Tile2MBuild<12, 3>, 3, 3, 3>()), entry_k2m<Tile2MBuild<12, 4>, ACM_K2M_L12_GROUPS>() },
+	{ nullptr, entry_k2m<Tile2MBuild<13, 4>, ACM_K2M_L13_GROUPS>() },
+	{ nullptr, entry_k2m<Tile2MBuild<14, 4>, 2, 3, 3, 2>() },       /* (4,3,3,2,2) and (4,3,2,3,2) spill seven of the 128 registers, (4,2,3,3,2) none */
 };
-constexpr int g_tile2m_default[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = { 3, 3, 3, 4, 4, 4, 4, 4 };
-/* levels whose byte-plane tiles go to the chunk kernel (acm_chunk: six stages on the matrix cores, a wavefront per chunk of 2048 samples)
- * unless ACM_K3=0 asks for acm_tile2's matrix build; the staged form follows the choice (64 columns of a residue class side by side) */
-/* ... and the six-stage first pass inside acm_tile2 (FirstPassZW): a row pair per tile, LDS passes with barriers behind it */
-#ifndef ACM_K3_L13
-#define ACM_K3_L13 entry_k2mw<TileCfg<13, 512, 16384>, 2, 6, 4, 3>(), 6
-#endif
-#ifndef ACM_K3_L14
-#define ACM_K3_L14 entry_k2mw<TileCfg<14, 1024, 32768>, 1, 6, 3, 3, 2>(), 6
-#endif
+/* [level] the six-stage builds: the chunk kernel, which takes the split of its table - acmk_tile2m_split - and the claim word behind
+ * acm_tile2's arguments (levels 8-12), or FirstPassZW inside acm_tile2 (levels 13, 14: fn) */
+typedef void (*ChunkFn)(const AcmTile2 *, uint32_t, const int16_t *, const uint32_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned, uint32_t *, uint32_t,
+			uint32_t, uint32_t);
+struct SixEntry { Tile2Fn fn; ChunkFn chunk; };
 template <int L, int... Gs>
-constexpr Tile2MEntry entry_k3()
+constexpr ChunkFn entry_k3()
 {
-	return Tile2MEntry{ Tile2Entry{ nullptr, 64 * FirstPassZ<L>::NW, FirstPassZ<L>::TR, 1 }, 6, ACM_K_CHUNK<L, 0, Gs...> };
+	return ACM_K_CHUNK<L, 0, Gs...>;
 }
-const Tile2MEntry g_chunk[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = {
-	/* level 7 (two classes per row: eight row walkers per matrix set, a lane's four outputs belong to two of them) was built, is bit-exact
-	 * (tests/test_gpu_byteplane.py at the time) and SLOWER than acm_tile2's matrix build, 0.616 against 0.680: the matrix work per sample
-	 * is the same at every level while the LDS passes it replaces are few at level 7.  Level 8 (four walkers): 0.680 against 0.668. */
-	{ Tile2Entry{ nullptr, 0, 0, 0 }, 0 },
-	entry_k3<8, 2>(),
-	entry_k3<9, 3>(),
-	entry_k3<10, 2, 2>(),
-	entry_k3<11, 3, 2>(),
-	entry_k3<12, 3, 3>(),
-	/* (level 13 as a chunk kernel: a row of 8192 per wavefront is four wavefronts of 350 registers - the staged rows of a chunk alone are
-	 * 192 - and past 256 the compiler parks what the hand-issued loads have just asked for in accumulation registers BEFORE the wait,
-	 * i.e. copies what is not there yet: tests/test_isa_invariants.py refuses the build.)  Levels 13 and 14: the same first pass shared
-	 * by the wavefronts of a workgroup, in acm_tile2 */
-	{ ACM_K3_L13 },
-	{ ACM_K3_L14 },
+const SixEntry g_chunk[ACM_K2M_MAX_LEVEL - ACM_K2M_MIN_LEVEL + 1] = {
+	{ nullptr, nullptr },
+	{ nullptr, entry_k3<8, 2>() },
+	{ nullptr, entry_k3<9, 3>() },
+	{ nullptr, entry_k3<10, 2, 2>() },
+	{ nullptr, entry_k3<11, 3, 2>() },
+	{ nullptr, entry_k3<12, 3, 3>() },
+	{ entry_k2m<Tile2MBuild<13, 6>, ACM_K3_L13_GROUPS>(), nullptr },
+	{ entry_k2m<Tile2MBuild<14, 6>, ACM_K3_L14_GROUPS>(), nullptr },
 };
-inline const Tile2MEntry &tile2m_entry(uint32_t level)
-{
-	/* (tuning builds: ACM_K3=0 puts levels 8-12 back on acm_tile2's three / four-stage matrix build - and on ITS form: process-wide,
-	 * read once, because the staged form follows the kernel, acmhip_mform_group) */
-	static const bool k3 = !(ACM_TUNING_ENV("ACM_K3") && atoi(ACM_TUNING_ENV("ACM_K3")) == 0);
-	if (k3 && g_chunk[level - ACM_K2M_MIN_LEVEL].g0)
-		return g_chunk[level - ACM_K2M_MIN_LEVEL];
-	const Tile2MEntry *row = g_tile2m[level - ACM_K2M_MIN_LEVEL];
-#ifdef ACM_TUNING
-	static const int forced = getenv("ACM_K2M_G0") ? atoi(getenv("ACM_K2M_G0")) : 0;
-#else
-	constexpr int forced = 0;
-#endif
-	const int want = forced ? forced : g_tile2m_default[level - ACM_K2M_MIN_LEVEL];
-	return ((want == 4 || row[0].g0 == 0) && row[1].g0 == 4) ? row[1] : row[0];
-}
 
 // ---------------------------------------------------------------------------
 // K2P: the lean tile kernel on the packed staged form
@@ -3532,24 +3426,14 @@ inline const Tile2MEntry &tile2m_entry(uint32_t level)
  * The chunk loads of the next tile are issued by hand before the LDS passes of this one and waited for with the tile's PCM
  * stores in flight (k2_wait); which slot holds what is scalar state (the chunk descriptors' second word).
  */
+/* (groups, chunks and slots of a packed tile: acm_geo::PackGeo, which the packed stager's queries read too) */
 template <class C, int GR_>
-struct PackGeo {
-	static constexpr int GR = GR_;                          /* rows per group: one width class per column pair */
-	static constexpr int NQ = GR / 4;                       /* row quads per group */
-	static constexpr int RPC = 64 / NQ;                     /* column pairs (ranks) per chunk */
-	static constexpr int PERMB = RPC * 2;                   /* bytes of a chunk's column-pair list */
-	static constexpr int NG = C::TR / GR;
-	static constexpr int P = C::COLS / 2;
-	static constexpr int MAXCHUNKS = NG * (P * NQ / 64 + 3);   /* four classes per group, each rounded up to whole chunks */
-	static constexpr int NW = C::NT / 64;
-	static constexpr int NSLOT = (MAXCHUNKS + NW - 1) / NW; /* chunk descriptors per wave and tile */
-	static constexpr int RS = C::COLS + (C::COLS >> C::PS); /* dwords between (row, c) and (row + 1, c) in the padded tile */
-	static_assert(GR % 4 == 0 && 64 % NQ == 0 && C::TR % GR == 0 && (P * NQ) % 64 == 0 && PERMB % 16 == 0, "packed geometry");
-	static_assert(C::COLS % (1 << C::PS) == 0, "rows are whole pad groups");
+struct PackGeo : acm_geo::PackGeo<C, GR_> {
 	/* where the row value of tile row `row` sits in LDS: a unit's four rows (q, q + NQ, q + 2 NQ, q + 3 NQ of their group)
 	 * side by side, one 16-byte read per lane */
 	static __device__ __forceinline__ int rowval_pos(const int row)
 	{
+		constexpr int GR = GR_, NQ = GR_ / 4;
 		const int g = row / GR, rr = row % GR;
 		return g * GR + 4 * (rr % NQ) + rr / NQ;
 	}
@@ -3805,32 +3689,28 @@ acm_tile2p(const AcmTile2 *__restrict__ tiles, const uint32_t ntiles, const uint
 	}
 }
 
-struct Tile2PEntry {
-	typedef void (*Fn)(const AcmTile2 *, uint32_t, const uint2 *, const uint8_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned);
-	Fn fn;
-	int threads, tile_rows, wg_per_cu, group_rows, slots, pad_shift;
-};
-template <class C, int GR, int... Gs>
-constexpr Tile2PEntry entry_k2p()
+typedef void (*Tile2PFn)(const AcmTile2 *, uint32_t, const uint2 *, const uint8_t *, const acmhip_blkhdr *, int16_t *, int16_t *, unsigned);
+template <class B, int... Gs>
+constexpr Tile2PFn entry_k2p()
 {
-	return Tile2PEntry{ acm_tile2p<C, 4, GR, Gs...>, C::NT, C::TR, 1024 / C::NT, GR, PackGeo<C, GR>::NW * PackGeo<C, GR>::NSLOT, C::PS };
+	return acm_tile2p<typename B::C, B::W, B::GR, Gs...>;
 }
-/* the tile geometries and stage groupings of acm_tile2 (g_tile2); groups of 16 rows = one block of the usual acm_rows = 16
- * (level 6: 32, or a wave would hold ten chunks).  (int16 only: the packed form has no float32 build) */
+/* the tiles (Tile2PBuild: acm_tile2's, and the rows of a group) and stage groupings of acm_tile2 (g_tile2).  (int16 only: the packed form
+ * has no float32 build) */
 #if !ACM_OUT_F32
-const Tile2PEntry g_tile2p[ACM_K2P_MAX_LEVEL - ACM_K2P_MIN_LEVEL + 1] = {
-	entry_k2p<TileCfg<6, 256, 8192>, 32, 2, 2, 2>(),
-	entry_k2p<TileCfg<7, 256, 8192>, 16, 3, 2, 2>(),
-	entry_k2p<TileCfg<8, 256, 8192>, 16, 3, 3, 2>(),
-	entry_k2p<TileCfg<9, 256, 8192>, 16, 3, 3, 3>(),
+using acm_geo::Tile2PBuild;
+const Tile2PFn g_tile2p[ACM_K2P_MAX_LEVEL - ACM_K2P_MIN_LEVEL + 1] = {
+	entry_k2p<Tile2PBuild<6>, 2, 2, 2>(),
+	entry_k2p<Tile2PBuild<7>, 3, 2, 2>(),
+	entry_k2p<Tile2PBuild<8>, 3, 3, 2>(),
+	entry_k2p<Tile2PBuild<9>, 3, 3, 3>(),
 };
 #endif
 
-/* levels 13-15: the stage-wise kernels apply the first level-12 stages into an int32 plane, this level-12 build of the tile
- * kernel (one 128 KB tile per CU - two 64 KB tiles spill with the 64 prefetch registers of a plane; halo or carry flavour like
- * every other group) reads the plane and does the other twelve */
-const FusedEntry g_fused_plane = { ACM_K_FUSED<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, false, 3, 3, 3, 3>, 512, 8, 1,
-				   ACM_K_FUSED<TileCfg<12, 512, 32768>, 2, MODE_PLANE, 2, true, 3, 3, 3, 3> };
+/* levels 13-15: the level-12 build of the tile kernel that reads an int32 plane (acm_geo::PlaneBuild), halo or carry flavour like every other group */
+using acm_geo::PlaneBuild;
+const FusedEntry g_fused_plane = { ACM_K_FUSED<PlaneBuild::C, PlaneBuild::W, MODE_PLANE, 2, false, 3, 3, 3, 3>,
+				   ACM_K_FUSED<PlaneBuild::C, PlaneBuild::W, MODE_PLANE, 2, true, 3, 3, 3, 3> };
 
 inline dim3 sw_grid(uint64_t max_elems, uint32_t nlist)
 {
@@ -3851,13 +3731,10 @@ namespace {
 __global__ void acm_warmup_kernel() {}
 }
 
-extern "C" int acmk_tuning_build(void)
+/* the geometry these kernels were compiled from (acmhip_device_open holds it against the planner's, acmk_geo_digest) */
+extern "C" uint64_t acmk_geo_digest_kernels(void)
 {
-#ifdef ACM_TUNING
-	return 1;
-#else
-	return 0;
-#endif
+	return acm_geo::digest();
 }
 
 extern "C" int acmk_warmup(void *stream)
@@ -3871,34 +3748,12 @@ extern "C" int acmk_warmup(void *stream)
 /* gridDim.y carries the stream index and is limited to 65535: walk long lists in slices */
 constexpr uint32_t SW_MAX_Y = 65535;
 
-#if !ACM_OUT_F32
-extern "C" int acmk_fused_variants(void)
+/* a persistent grid (acmk_*_grid: as many workgroups as the chip holds at once), never more than tiles */
+static inline dim3 grid_of(int most, uint32_t ntiles)
 {
-	return NVARIANTS;
+	return dim3((uint32_t)most > ntiles ? ntiles : (uint32_t)most);
 }
 
-extern "C" int acmk_fused_tile_rows(uint32_t level, int variant)
-{
-	if (level < ACM_K1_MIN_LEVEL || level > ACM_K1_MAX_LEVEL || variant < 0 || variant >= NVARIANTS)
-		return 0;
-	return g_fused[variant][level - ACM_K1_MIN_LEVEL].tile_rows;
-}
-
-extern "C" int acmk_fused_has_carry(uint32_t level, int variant)
-{
-	if (level < ACM_K1_MIN_LEVEL || level > ACM_K1_MAX_LEVEL || variant < 0 || variant >= NVARIANTS)
-		return 0;
-	return g_fused[variant][level - ACM_K1_MIN_LEVEL].fn_carry != nullptr;
-}
-
-extern "C" int acmk_fused_grid(uint32_t level, int variant, int cus)
-{
-	if (level < ACM_K1_MIN_LEVEL || level > ACM_K1_MAX_LEVEL || variant < 0 || variant >= NVARIANTS)
-		return 0;
-	return (cus > 0 ? cus : 256) * g_fused[variant][level - ACM_K1_MIN_LEVEL].wg_per_cu;
-}
-
-#endif
 extern "C" int ACMK_OUT(acmk_launch_fused)(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
 				 uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 				 int16_t *d_pcm, unsigned fmt, void *stream)
@@ -3912,15 +3767,11 @@ extern "C" int ACMK_OUT(acmk_launch_fused)(uint32_t level, int variant, int cus,
 	if (level < ACM_K1_MIN_LEVEL || level > ACM_K1_MAX_LEVEL || variant < 0 || variant >= NVARIANTS)
 		return -1;
 	const FusedEntry &e = g_fused[variant][level - ACM_K1_MIN_LEVEL];
-	/* persistent grid: as many workgroups as the chip holds at once, never more than tiles.  `cus` comes from
-	 * the device handle: nothing here queries or synchronises, so the launch can be captured into a hipGraph */
-	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * e.wg_per_cu);
-	if (grid > ntiles)
-		grid = ntiles;
-	if (carry && !e.fn_carry)
+	/* (`cus` comes from the device handle: nothing here queries or synchronises, so the launch can be captured into a hipGraph) */
+	if (!(carry ? e.fn_carry : e.fn))
 		return -1;
-	hipLaunchKernelGGL(carry ? e.fn_carry : e.fn, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream,
-			   d_streams, d_tiles, ntiles, d_idx, d_hdr, d_pcm, fmt);
+	hipLaunchKernelGGL(carry ? e.fn_carry : e.fn, grid_of(acmk_fused_grid(level, variant, cus), ntiles), dim3(acmk_fused_threads(level, variant)), 0,
+			   (hipStream_t)stream, d_streams, d_tiles, ntiles, d_idx, d_hdr, d_pcm, fmt);
 	ACMK_CHECK_LAUNCH();
 	return 0;
 }
@@ -4008,22 +3859,6 @@ extern "C" int ACMK_OUT(acmk_launch_emit)(const AcmDevStream *d_streams, const u
 	return 0;
 }
 
-#if !ACM_OUT_F32
-extern "C" int acmk_tile2_rows(uint32_t level)
-{
-	if (level < ACM_K2_MIN_LEVEL || level > ACM_K2_MAX_LEVEL)
-		return 0;
-	return tile2_entry(level).tile_rows;
-}
-
-extern "C" int acmk_tile2_grid(uint32_t level, int cus)
-{
-	if (level < ACM_K2_MIN_LEVEL || level > ACM_K2_MAX_LEVEL)
-		return 0;
-	return (cus > 0 ? cus : 256) * tile2_entry(level).wg_per_cu;
-}
-
-#endif
 extern "C" int ACMK_OUT(acmk_launch_tile2)(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
 				 int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream)
 {
@@ -4037,128 +3872,19 @@ extern "C" int ACMK_OUT(acmk_launch_tile2)(uint32_t level, int cus, const AcmTil
 		return -1;
 	if (level < ACM_K2_MIN_LEVEL || level > ACM_K2_MAX_LEVEL)
 		return -1;
-	Tile2Entry e = tile2_entry(level);
+	Tile2Fn fn = g_tile2[level - ACM_K2_MIN_LEVEL];
 #ifdef ACM_ABLATION
 	if (const char *a = getenv("ACM_K2_ABL"))
 		for (const auto &x : g_tile2_abl)
 			if (level == 9 && x.mask == atoi(a))
-				e = x.e;
+				fn = x.fn;
 #endif
-	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * e.wg_per_cu);
-	if (grid > ntiles)
-		grid = ntiles;
-	hipLaunchKernelGGL(e.fn, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, d_idx, (const uint32_t *)nullptr, d_hdr, d_pcm, d_sink, fmt);
+	hipLaunchKernelGGL(fn, grid_of(acmk_tile2_grid(level, cus), ntiles), dim3(acmk_tile2_threads(level)), 0, (hipStream_t)stream, d_tiles, ntiles, d_idx,
+			   (const uint32_t *)nullptr, d_hdr, d_pcm, d_sink, fmt);
 	ACMK_CHECK_LAUNCH();
 	return 0;
 }
 
-#if !ACM_OUT_F32
-extern "C" int acmk_tile2m_rows(uint32_t level)
-{
-	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
-		return 0;
-	return tile2m_entry(level).e.tile_rows;
-}
-
-/* tiles of this build the planner puts in front of a window into a stream (ACM_TILE_DISCARD records): one - every pass reaches back less
- * than a tile - except where the chunk kernel keeps the two rows in front of a walk in registers from the chunk before: there the
- * last lead-in chunk needs lead-in chunks of its own for those rows (levels 10: one more; 11, 12 - chunks of one row -: two more) */
-extern "C" int acmk_tile2m_lead_in(uint32_t level)
-{
-	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL || tile2m_entry(level).g0 != 6)
-		return 1;
-	switch (level) {
-	case 8: return FirstPassZ<8>::KEEPS_ROWS ? 1 + (2 + FirstPassZ<8>::NSW - 1) / FirstPassZ<8>::NSW : 1;
-	case 9: return FirstPassZ<9>::KEEPS_ROWS ? 1 + (2 + FirstPassZ<9>::NSW - 1) / FirstPassZ<9>::NSW : 1;
-	case 10: return FirstPassZ<10>::HISTORY_IN_REGISTERS ? 1 + (2 + FirstPassZ<10>::NSW - 1) / FirstPassZ<10>::NSW : 1;
-	case 11: return FirstPassZ<11>::HISTORY_IN_REGISTERS ? 1 + (2 + FirstPassZ<11>::NSW - 1) / FirstPassZ<11>::NSW : 1;
-	case 12: return FirstPassZ<12>::HISTORY_IN_REGISTERS ? 1 + (2 + FirstPassZ<12>::NSW - 1) / FirstPassZ<12>::NSW : 1;
-	case 13: case 14: return 2;             /* FirstPassZW: a row pair per tile, the pair in front of it in registers */
-	default: return 1;
-	}
-}
-
-/* wavefronts that share a launch of the chunk kernel's table among them (each takes one contiguous run of it); 0: not the chunk kernel */
-extern "C" int acmk_tile2m_run_waves(uint32_t level, int cus)
-{
-	if (level < ACM_K2M_MIN_LEVEL || level > 12 || tile2m_entry(level).g0 != 6)
-		return 0;
-	const Tile2Entry &e = tile2m_entry(level).e;
-	return (cus > 0 ? cus : 256) * e.wg_per_cu * (e.threads / 64);
-}
-
-/* workgroups of a launch of the byte-plane build at most (the same as acmk_tile2_grid except at level 13, whose tiles are half as tall) */
-extern "C" int acmk_tile2m_grid(uint32_t level, int cus)
-{
-	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
-		return 0;
-	return (cus > 0 ? cus : 256) * tile2m_entry(level).e.wg_per_cu;
-}
-
-/* How a launch of the chunk kernel hands its table of ntiles chunks to the W = acmk_tile2m_run_waves wavefronts (device-free: the launcher
- * and the tests call it).  The first W * static_per chunks are static runs, wavefront w's the chunks [w * static_per, (w + 1) *
- * static_per); the rest is cut into nclaimed runs of run_chunks (the last one may be shorter), run k at chunk W * static_per + k *
- * run_chunks, which the wavefronts claim in ascending k as they come free.
- * The rule: under the compiled-in policy of the level (g_claim_default: run_chunks - 0: the level keeps the static split - and the static
- * share in thousandths of the table) a table is split this way from ACM_CLAIM_MIN_PER chunks per wavefront on; a policy set through
- * acmk_tile2m_claim_config holds for every table of at least as many chunks as a launch has workgroups at most.  Either way static_per =
- * floor(ntiles * share / 1000 / W), and a table that leaves nothing behind its static runs is not split.
- * Every other table stays wholly static exactly as before: nclaimed = 0, run_chunks = 0, static_per = ceil(ntiles / W), one contiguous
- * run per wavefront.  Returns 0, or -1 for a level without the chunk kernel */
-#define ACM_CLAIM_MIN_PER 32u
-#ifndef ACM_CLAIM_DEFAULTS
-#define ACM_CLAIM_DEFAULTS { 16, 900 }, { 16, 800 }, { 16, 800 }, { 16, 800 }, { 16, 900 }
-#endif
-/* (levels 8-12, measured on 1024 streams of 2 Mi samples, profiles/claimed_runs_notes.txt 2: the oldest wavefront of a SIMD is done
- * with an equal share at 0.8 of the launch, so a fifth of the table is what there is to hand out; runs of 8 replay too many chunks, runs
- * of 32 and more leave too long a tail) */
-static const struct { int run_chunks, static_permille; } g_claim_default[5] = { ACM_CLAIM_DEFAULTS };
-static int g_claim_run_chunks = -1, g_claim_static_permille = -1;         /* < 0: the level's default */
-
-extern "C" int acmk_tile2m_split(uint32_t level, int cus, uint32_t ntiles, uint32_t *static_per, uint32_t *run_chunks, uint32_t *nclaimed)
-{
-	const uint32_t W = (uint32_t)acmk_tile2m_run_waves(level, cus);
-	if (!W)
-		return -1;
-	const bool set = g_claim_run_chunks >= 0 || g_claim_static_permille >= 0;
-	const uint32_t R = (uint32_t)(g_claim_run_chunks >= 0 ? g_claim_run_chunks : g_claim_default[level - 8].run_chunks);
-	uint32_t share = (uint32_t)(g_claim_static_permille >= 0 ? g_claim_static_permille : g_claim_default[level - 8].static_permille);
-	if (share > 1000u)
-		share = 1000u;
-	*static_per = (ntiles + W - 1) / W;
-	*run_chunks = *nclaimed = 0;
-	if (!R || ntiles < (set ? (uint32_t)acmk_tile2m_grid(level, cus) : W * ACM_CLAIM_MIN_PER))
-		return 0;
-	const uint32_t sp = (uint32_t)((uint64_t)ntiles * share / 1000u / W);
-	const uint32_t rest = ntiles - W * sp;
-	if (!rest)
-		return 0;
-	*static_per = sp;
-	*run_chunks = R;
-	*nclaimed = (rest + R - 1) / R;
-	return 0;
-}
-
-/* process-wide policy for every level, for tests and sweeps: run_chunks (0: no claimed runs) and the static share in thousandths; a
- * negative argument puts that value back to the levels' defaults.  Hands back what was set before (negative: the defaults) */
-extern "C" void acmk_tile2m_claim_config(int run_chunks, int static_permille, int *old_run_chunks, int *old_static_permille)
-{
-	if (old_run_chunks)
-		*old_run_chunks = g_claim_run_chunks;
-	if (old_static_permille)
-		*old_static_permille = g_claim_static_permille;
-	g_claim_run_chunks = run_chunks < 0 ? -1 : run_chunks;
-	g_claim_static_permille = static_permille < 0 ? -1 : static_permille;
-}
-
-extern "C" int acmk_tile2m_stages(uint32_t level)
-{
-	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
-		return 0;
-	return tile2m_entry(level).g0;
-}
-
-#endif
 extern "C" int ACMK_OUT(acmk_launch_tile2m)(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
 				  const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, uint32_t *d_claim, void *stream)
 {
@@ -4172,62 +3898,30 @@ extern "C" int ACMK_OUT(acmk_launch_tile2m)(uint32_t level, int cus, const AcmTi
 		return -1;
 	if (level < ACM_K2M_MIN_LEVEL || level > ACM_K2M_MAX_LEVEL)
 		return -1;
-	const Tile2Entry &e = tile2m_entry(level).e;
-	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * e.wg_per_cu);
-	if (grid > ntiles)
-		grid = ntiles;
-	if (const ChunkFn chunk = tile2m_entry(level).chunk) {
+	/* which build the level uses in this process is acm_kernel_geo.cpp's decision (the staged form and the planner follow it too): the depth
+	 * of its first pass names the kernel */
+	const int g0 = acmk_tile2m_stages(level);
+	const dim3 grid = grid_of(acmk_tile2m_grid(level, cus), ntiles), block(acmk_tile2m_threads(level));
+	if (const ChunkFn chunk = g0 == 6 ? g_chunk[level - ACM_K2M_MIN_LEVEL].chunk : nullptr) {
 		/* (d_claim: one zeroed word that no other launch in flight uses; the launch leaves it at zero again.  Null: the static split) */
 		uint32_t static_per = 0, run_chunks = 0, nclaimed = 0;
 		if (d_claim && acmk_tile2m_split(level, cus, ntiles, &static_per, &run_chunks, &nclaimed))
 			return -1;
-		hipLaunchKernelGGL(chunk, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
+		hipLaunchKernelGGL(chunk, grid, block, 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
 				   reinterpret_cast<const uint32_t *>(d_pairs), d_hdr, d_pcm, d_sink, fmt, d_claim, static_per, run_chunks, nclaimed);
 		ACMK_CHECK_LAUNCH();
 		return 0;
 	}
-	hipLaunchKernelGGL(e.fn, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
+	const Tile2Fn fn = g0 == 6 ? g_chunk[level - ACM_K2M_MIN_LEVEL].fn : g0 ? g_tile2m[level - ACM_K2M_MIN_LEVEL][g0 == 4] : nullptr;
+	if (!fn)
+		return -1;
+	hipLaunchKernelGGL(fn, grid, block, 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_mform),
 			   reinterpret_cast<const uint32_t *>(d_pairs), d_hdr, d_pcm, d_sink, fmt);
 	ACMK_CHECK_LAUNCH();
 	return 0;
 }
 
 #if !ACM_OUT_F32
-extern "C" int acmk_tile2p_rows(uint32_t level)
-{
-	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
-		return 0;
-	return g_tile2p[level - ACM_K2P_MIN_LEVEL].tile_rows;
-}
-
-extern "C" int acmk_tile2p_group_rows(uint32_t level)
-{
-	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
-		return 0;
-	return g_tile2p[level - ACM_K2P_MIN_LEVEL].group_rows;
-}
-
-extern "C" int acmk_tile2p_slots(uint32_t level)
-{
-	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
-		return 0;
-	return g_tile2p[level - ACM_K2P_MIN_LEVEL].slots;
-}
-
-extern "C" int acmk_tile2p_waves(uint32_t level)
-{
-	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
-		return 0;
-	return g_tile2p[level - ACM_K2P_MIN_LEVEL].threads / 64;
-}
-
-extern "C" int acmk_tile2p_pad_shift(uint32_t level)
-{
-	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
-		return 0;
-	return g_tile2p[level - ACM_K2P_MIN_LEVEL].pad_shift;
-}
-
 extern "C" int acmk_launch_tile2p(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const acmhip_packed_chunk *d_chunks, const uint8_t *d_blob,
 				  const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, void *stream)
 {
@@ -4237,29 +3931,15 @@ extern "C" int acmk_launch_tile2p(uint32_t level, int cus, const AcmTile2 *d_til
 		return -1;
 	if (level < ACM_K2P_MIN_LEVEL || level > ACM_K2P_MAX_LEVEL)
 		return -1;
-	const Tile2PEntry &e = g_tile2p[level - ACM_K2P_MIN_LEVEL];
-	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * e.wg_per_cu);
-	if (grid > ntiles)
-		grid = ntiles;
 	static_assert(sizeof(acmhip_packed_chunk) == sizeof(uint2), "a chunk descriptor is two words");
-	hipLaunchKernelGGL(e.fn, dim3(grid), dim3(e.threads), 0, (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const uint2 *>(d_chunks), d_blob, d_hdr,
-			   d_pcm, d_sink, fmt);
+	hipLaunchKernelGGL(g_tile2p[level - ACM_K2P_MIN_LEVEL], grid_of(acmk_tile2p_grid(level, cus), ntiles), dim3(64 * acmk_tile2p_waves(level)), 0,
+			   (hipStream_t)stream, d_tiles, ntiles, reinterpret_cast<const uint2 *>(d_chunks), d_blob, d_hdr, d_pcm, d_sink, fmt);
 	ACMK_CHECK_LAUNCH();
 	return 0;
 }
 
-extern "C" int acmk_plane_tile_rows(void)
-{
-	return g_fused_plane.tile_rows;
-}
-
-/* d_plane stands where the staged indices stand in acmk_launch_fused; the streams' idx_off count int32 units into it */
-extern "C" int acmk_plane_grid(int cus)
-{
-	return (cus > 0 ? cus : 256) * g_fused_plane.wg_per_cu;
-}
-
 #endif
+/* d_plane stands where the staged indices stand in acmk_launch_fused; the streams' idx_off count int32 units into it */
 extern "C" int ACMK_OUT(acmk_launch_fused_plane)(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
 				       const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream)
 {
@@ -4269,11 +3949,8 @@ extern "C" int ACMK_OUT(acmk_launch_fused_plane)(int cus, int carry, const AcmDe
 #endif
 	if (ntiles == 0)
 		return 0;
-	uint32_t grid = (uint32_t)((cus > 0 ? cus : 256) * g_fused_plane.wg_per_cu);
-	if (grid > ntiles)
-		grid = ntiles;
-	hipLaunchKernelGGL(carry ? g_fused_plane.fn_carry : g_fused_plane.fn, dim3(grid), dim3(g_fused_plane.threads), 0, (hipStream_t)stream,
-			   d_streams, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_plane), nullptr, d_pcm, fmt);
+	hipLaunchKernelGGL(carry ? g_fused_plane.fn_carry : g_fused_plane.fn, grid_of(acmk_plane_grid(cus), ntiles), dim3(acmk_plane_threads()), 0,
+			   (hipStream_t)stream, d_streams, d_tiles, ntiles, reinterpret_cast<const int16_t *>(d_plane), nullptr, d_pcm, fmt);
 	ACMK_CHECK_LAUNCH();
 	return 0;
 }

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "acm_device.h"
+#include "acm_parse_bounds.h"
 
 #pragma clang diagnostic ignored "-Winline-asm"         /* m0 on a clobber list: see WaveWalk */
 
@@ -179,23 +180,7 @@ __device__ __forceinline__ uint32_t k_table_for(uint32_t code)
 
 /* ---- kernel 1: walk the streams ---- */
 
-/* striped upload: stripe s of S of a file's arena slot (the file, padded to 16 bytes, + 16 zero bytes) starts here */
-__host__ __device__ __forceinline__ uint32_t acm_stripe_bound(uint32_t file_len, uint32_t s, uint32_t S)
-{
-	const uint32_t slot = ((file_len + 15u) & ~15u) + 16u;
-	return s >= S ? slot : (uint32_t)(((uint64_t)slot * s / S) & ~15ull);
-}
-
-/* first block of block range r of R of a stream of `blocks` blocks (r == R: its end).  Ranges are cut at multiples of `unit` blocks (0 / 1:
- * anywhere; acm_batch.cpp asks for whole tiles of the lean kernel where a stream has the byte-plane form, which also keeps every row pair
- * of an odd block height inside one range); a short stream may have empty ranges */
-__host__ __device__ __forceinline__ uint32_t acm_range_bound(uint32_t blocks, uint32_t r, uint32_t R, uint32_t unit)
-{
-	if (r >= R)
-		return blocks;
-	const uint32_t b = (uint32_t)((uint64_t)blocks * r / R);
-	return unit > 1u ? b / unit * unit : b;
-}
+/* (where stripes and block ranges are cut - acm_stripe_bound, acm_range_bound -: acm_parse_bounds.h, the text the host's layouts read too) */
 
 /* payload bits of a column by filler code for `rows` rows; K_WALK = step through it, BAD_CODE = stop */
 __device__ __forceinline__ uint32_t column_bits(uint32_t code, uint32_t rows)
@@ -983,13 +968,6 @@ acm_parse_columns(const AcmParseJob *__restrict__ jobs, const AcmParseResult *__
 
 #define ACMP_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
-extern "C" int acmk_parse_supported(uint32_t level, uint32_t rows, uint64_t file_len, uint64_t blocks)
-{
-	/* 32-bit bit offsets with headroom (a corrupt stream may step one column past the end of its file before
-	 * the walk notices, and must not wrap), 32-bit column counts */
-	return rows >= 1 && blocks >= 1 && file_len < 0x10000000ull && (blocks << level) < 0xFFFFFFFFull;
-}
-
 /*
  * d_flags[njobs] must be zero on entry; after the kernels a stream is clean iff
  * d_res[j].status == 0 && d_res[j].blocks_done == jobs[j].blocks && d_flags[j] == 0.
@@ -1010,16 +988,6 @@ acm_scatter_stripe(const AcmParseJob *__restrict__ jobs, const uint32_t njobs, c
 	for (uint32_t v = threadIdx.x; v < (hi - lo) / 16u; v += 256u)
 		dst[v] = src[v];
 }
-}
-
-extern "C" uint32_t acmk_stripe_bound(uint32_t file_len, uint32_t s, uint32_t S)
-{
-	return acm_stripe_bound(file_len, s, S);
-}
-
-extern "C" uint32_t acmk_range_bound(uint32_t blocks, uint32_t r, uint32_t R, uint32_t unit)
-{
-	return acm_range_bound(blocks, r, R, unit);
 }
 
 extern "C" int acmk_launch_scatter_stripe(const AcmParseJob *d_jobs, uint32_t njobs, const uint64_t *d_stripe_at, const uint8_t *d_stage,

@@ -1,5 +1,7 @@
 // How fast does the real pass_body (3 stages over a 16-element body, registers only) run?  Uses the product's
 // own device code (acm_kernels.hip) in a loop without LDS / HBM traffic.  cycles per butterfly per SIMD.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I libacm_amd/csrc -o profiles/ubench/butterfly.bin profiles/ubench/butterfly.hip \
+//         libacm_amd/csrc/acm_kernels_f32.hip libacm_amd/csrc/acm_kernel_geo.cpp    (the launchers' float32 twins; the launch geometry they ask for)
 #include "../../libacm_amd/csrc/acm_kernels.hip"
 #include <cstdio>
 template <int L, int K0, int G>

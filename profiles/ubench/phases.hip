@@ -1,6 +1,8 @@
 // Diagnostic: where do the cycles of acm_fused_tile's tile loop go?  Builds the real kernel source with
 // ACM_STAMPS (s_memtime stamps per phase, per wave) on synthetic staged data and prints phase shares.
-// Timing-only; never part of the product build.   hipcc -O3 --offload-arch=gfx950 -I include -I libacm_amd/csrc
+// Timing-only; never part of the product build.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I libacm_amd/csrc -o profiles/ubench/phases.bin profiles/ubench/phases.hip \
+//         libacm_amd/csrc/acm_kernels_f32.hip libacm_amd/csrc/acm_kernel_geo.cpp    (the launchers' float32 twins; the launch geometry they ask for)
 #define ACM_STAMPS 1
 #include "../../libacm_amd/csrc/acm_kernels.hip"
 #include <cstdio>
@@ -15,7 +17,7 @@ int main(int argc, char **argv) {
     AcmDevStream &d = ds[i]; d = AcmDevStream{};
     d.idx_off = i * per; d.hdr_off = (uint64_t)i * nblocks; d.pcm_off = i * per; d.n_emit = per;
     d.level = level; d.rows = rows; d.nrows = nblocks * rows; d.row_begin = 0; d.halo_row = 0;
-    for (uint32_t r = 0; r < d.nrows; r += T) tiles.push_back(AcmTile{i, r});
+    for (uint32_t r = 0; r < d.nrows; r += T) tiles.push_back(AcmTile{i, (int32_t)r, 0u, 0u});
   }
   int16_t *d_idx, *d_pcm; acmhip_blkhdr *d_hdr; AcmDevStream *d_s; AcmTile *d_t;
   (void)hipMalloc(&d_idx, per * nstreams * 2); (void)hipMalloc(&d_pcm, per * nstreams * 2);
@@ -27,7 +29,7 @@ int main(int argc, char **argv) {
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   for (int rep = 0; rep < 3; rep++) {
     (void)hipEventRecord(e0);
-    acmk_launch_fused(level, variant, 256, d_s, d_t, (uint32_t)tiles.size(), d_idx, d_hdr, d_pcm, 0, nullptr);
+    acmk_launch_fused(level, variant, 256, 0 /* the halo build */, d_s, d_t, (uint32_t)tiles.size(), d_idx, d_hdr, d_pcm, 0, nullptr);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
   }
   float ms; (void)hipEventElapsedTime(&ms, e0, e1);

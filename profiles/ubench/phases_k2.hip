@@ -1,12 +1,14 @@
-// Diagnostic: where do the cycles of acm_tile2 (argv[2] = 1: its matrix-core build) go?  Builds the real kernel source with ACM_STAMPS
+// Diagnostic: where do the cycles of acm_tile2 (its vector-ALU build, on the int16 form) go?  Builds the real kernel source with ACM_STAMPS
 // (s_memtime stamps per phase, per wave) on synthetic staged data and prints the phase shares.  Timing only.
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I libacm_amd/csrc -o phases_k2 profiles/ubench/phases_k2.hip
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I libacm_amd/csrc -o profiles/ubench/phases_k2.bin profiles/ubench/phases_k2.hip \
+//         libacm_amd/csrc/acm_kernels_f32.hip libacm_amd/csrc/acm_kernel_geo.cpp    (the launchers' float32 twins; the launch geometry they ask for)
 #define ACM_STAMPS 1
 #include "../../libacm_amd/csrc/acm_kernels.hip"
 #include <cstdio>
 #include <vector>
 int main(int argc, char **argv) {
-  const int level = argc > 1 ? atoi(argv[1]) : 9; const int mform = argc > 2 ? atoi(argv[2]) : 0;
+  const int level = argc > 1 ? atoi(argv[1]) : 9;
+  if (argc > 2 && atoi(argv[2])) { printf("the matrix-core builds read the byte-plane form with its pair table: profiles/ubench/phases_k3.hip stages one\n"); return 1; }
   const uint32_t rows = 16, nblocks = (uint32_t)((1u << 21) / (rows << level)), nstreams = 1024;
   const uint64_t cols = 1ull << level, per = (uint64_t)nblocks * rows * cols;
   const uint32_t TR = (uint32_t)acmk_tile2_rows(level);
@@ -26,7 +28,7 @@ int main(int argc, char **argv) {
   float ms = 0;
   for (int rep = 0; rep < 5; rep++) {
     (void)hipEventRecord(e0);
-    (mform ? acmk_launch_tile2m(level, 256, d_t, (uint32_t)tiles.size(), (const uint8_t *)d_idx, d_hdr, d_pcm, d_sink, 0, nullptr) : acmk_launch_tile2(level, 256, d_t, (uint32_t)tiles.size(), d_idx, d_hdr, d_pcm, d_sink, 0, nullptr));
+    acmk_launch_tile2(level, 256, d_t, (uint32_t)tiles.size(), d_idx, d_hdr, d_pcm, d_sink, 0, nullptr);
     (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     (void)hipEventElapsedTime(&ms, e0, e1);
   }
@@ -39,7 +41,7 @@ int main(int argc, char **argv) {
                           "issue of the next tile's loads", "LDS passes", "barrier before write-out", "write-out (LDS gather + PCM stores)",
                           "end-of-iteration wait for the prefetched loads"};
   printf("%s level %d: %.3f ms per launch with stamps (%.1f Gsamples/s), %zu tiles, %d waves sampled, s_memtime ticks per wave %.0f\n",
-         mform ? "matrix-core build," : "vector-ALU build,", level, ms, per * nstreams / ms / 1e6, tiles.size(), n, tot / n);
+         "vector-ALU build,", level, ms, per * nstreams / ms / 1e6, tiles.size(), n, tot / n);
   for (int k = 0; k < 7; k++) printf("  %-62s %5.1f %%  %8.0f ticks per tile\n", names[k], 100.0 * sum[k] / tot, sum[k] / n / (tiles.size() / 1024.0));
   return 0;
 }

@@ -2,7 +2,7 @@
 // phase, per wavefront) on synthetic byte-plane data and prints the phase shares, and when the wavefronts of the launch begin and end their
 // share of the chunk table (both clocks, every wavefront).  Timing only (the PCM is not looked at).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I libacm_amd/csrc -o profiles/ubench/phases_k3.bin profiles/ubench/phases_k3.hip \
-//         libacm_amd/csrc/acm_kernels_f32.hip        (the launchers name their float32 twins)
+//         libacm_amd/csrc/acm_kernels_f32.hip libacm_amd/csrc/acm_kernel_geo.cpp    (the launchers name their float32 twins and ask for the launch geometry)
 //   ./phases_k3 <level> [rows per block = 16] [percent of the blocks at 16 bits = 56] [percent at 12 bits = 0]
 //               [chunks per claimed run = -1: the level's default; 0: the static split] [static share in thousandths = -1: the default]
 #ifndef NO_STAMPS

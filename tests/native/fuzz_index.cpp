@@ -15,18 +15,7 @@
 #include "acm_hip.h"
 #include "libacm.h"
 
-extern "C" {
-/* tile geometries the stagers ask the kernels' translation unit for (acm_kernels.hip is not in this build): the shipped ones */
-int acmk_tile2_rows(uint32_t level) { return level >= 6 && level <= 11 ? 8192 >> level : level == 12 || level == 13 ? 4 : level == 14 ? 2 : 0; }
-int acmk_tile2m_rows(uint32_t level) { return level == 7 ? 64 : level >= 8 && level <= 11 ? 2048 >> level : level == 12 ? 1 : level == 13 || level == 14 ? 2 : 0; }
-int acmk_tile2m_stages(uint32_t level) { return level == 7 ? 3 : level >= 8 && level <= 14 ? 6 : 0; }
-int acmk_tile2m_lead_in(uint32_t) { return 1; }
-int acmk_tile2p_rows(uint32_t level) { return level >= 6 && level <= 9 ? 8192 >> level : 0; }
-int acmk_tile2p_group_rows(uint32_t level) { return level == 6 ? 32 : 16; }
-int acmk_tile2p_slots(uint32_t) { return 28; }
-int acmk_tile2p_waves(uint32_t) { return 4; }
-int acmk_tile2p_pad_shift(uint32_t) { return 5; }
-}
+/* (the tile geometries the stagers ask for are the library's own: this build links acm_kernel_geo.cpp, which needs no kernel) */
 
 static uint64_t rng = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (uint32_t)(rng >> 11); }

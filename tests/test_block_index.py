@@ -224,7 +224,7 @@ def test_index_and_stager_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "fuzz_index")
     csrc = os.path.join(ROOT, "libacm_amd", "csrc")
     src = [os.path.join(ROOT, "tests", "native", "fuzz_index.cpp")] + \
-          [os.path.join(csrc, f) for f in ("acm_stage.cpp", "acm_fill.cpp", "acm_pack.cpp")]
+          [os.path.join(csrc, f) for f in ("acm_stage.cpp", "acm_fill.cpp", "acm_pack.cpp", "acm_kernel_geo.cpp")]
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", exe] + src + ["-lpthread"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -1,4 +1,4 @@
-"""How a launch of the chunk kernel hands out its table (acmk_tile2m_split, libacm_amd/csrc/acm_kernels.hip): the first W *
+"""How a launch of the chunk kernel hands out its table (acmk_tile2m_split, libacm_amd/csrc/acm_kernel_geo.cpp): the first W *
 static_per chunks are one static run per wavefront, the rest is nclaimed runs of run_chunks that the wavefronts claim in ascending
 order.  Device-free: the function is pure host code, and so are the wavefront count and the override it rests on.
 
