@@ -640,9 +640,9 @@ int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, s
  *
  * wins[k].words and .status are what acm_batch_decode_windows reports for the same window - also for one the host stager turns
  * away during the call (a stale or damaged index): its error status, a row of zeros.  dev_off = slot_off = k * R, slot_words = R.
- * A window whose item has, in effect (after force_chans), another channel count than dense->channels is turned away softly, as a
- * file that is not ACM is: words = 0, status = ACMHIP_ERR_ARG, a row of zeros; nothing of it is parsed, uploaded or synthesised
- * (timing->blocks_parsed shows it) and the call does not fail.
+ * A window whose item has, in effect (after force_chans), another channel count than dense->channels is - without ACM_DENSE_MIX,
+ * below - turned away softly, as a file that is not ACM is: words = 0, status = ACMHIP_ERR_ARG, a row of zeros; nothing of it is
+ * parsed, uploaded or synthesised (timing->blocks_parsed shows it) and the call does not fail.
  *
  * ACMHIP_ERR_ARG before anything is written: dense == NULL, frames == 0, channels other than 1 or 2, unknown dense->flags;
  * opts->d_pcm == NULL or too small; a fmt other than ACMHIP_FMT_S16LE (padding has no single meaning in the other writers);
@@ -653,8 +653,31 @@ int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, s
  * handle's own; nothing is read back.  One launch of acm_dense_rows behind the plan's, on the same stream, reads a row table of 16
  * bytes per window and copies, splits the channels, widens and pads; the call returns with the stream drained.
  * timing->kernel_s covers synthesis and that launch.
+ *
+ * ACM_DENSE_MIX: mono and stereo files in one batch.  Without the flag nothing of the above changes.  With it, a window whose item
+ * has the OTHER channel count c_k (1 or 2, after force_chans) than C = dense->channels is decoded and converted instead of turned
+ * away.  Its first_word and max_words count the item's own interleaved samples, as in acm_batch_decode_windows, and so do `whole`
+ * and `words`; it delivers f = words / c_k frames, source frame i being whole[first_word + i * c_k + ch], and with T = frames its
+ * row holds, for i < f,
+ *   c_k == 2, C == 1                     (L_i + R_i) >> 1: the sum in 32 bits, the shift arithmetic - the floor, so 32767 + 32767
+ *                                        gives 32767 and -1 + 0 gives -1
+ *   c_k == 1, C == 2, interleaved        the sample in both channels: out[2i] = out[2i + 1] = s_i
+ *   c_k == 1, C == 2, ACM_DENSE_PLANAR   the sample in both planes:   out[i] = out[T + i] = s_i
+ * and zeros in the frames i >= f.  float32 is that int16 result times 2^-15: the down-mix is defined on integers, once.  Every
+ * element of every row is written and nothing outside [0, nwin * R), as without the flag.  A window whose item has C channels gets
+ * exactly the row it gets without the flag.
+ * The checks of such a window count in the item's own frames: first_word % c_k == 0, max_words % c_k == 0 and
+ * max_words <= T * c_k, else ACMHIP_ERR_ARG for the whole call before anything is written.  Windows without a channel count - of an
+ * item that is not ACM, whose index is unusable, or that does not exist - are checked against C and deliver a row of zeros, as
+ * without the flag.  wins[k].words (SOURCE samples) and .status are what acm_batch_decode_windows reports for the same window;
+ * dev_off = slot_off = k * R and slot_words = R; timing->blocks_parsed counts the blocks of converted windows too.  frames of 2^55
+ * and more: ACMHIP_ERR_ARG.
+ * Where no row of a call converts - every file has C channels, or the others' windows deliver nothing - the launch is
+ * acm_dense_rows as without the flag; else one launch of acm_dense_mixed (csrc/acm_dense_mix.hip) takes its place and writes the
+ * plain rows as well.
  * ---------------------------------------------------------------------- */
 #define ACM_DENSE_PLANAR 1u              /* row k is [channels][frames]; default [frames][channels] */
+#define ACM_DENSE_MIX    4u              /* windows of files with the other channel count are converted, not turned away */
 typedef struct acm_dense_opts {
 	uint64_t frames;                 /* T >= 1 */
 	uint32_t channels;               /* C: 1 or 2 (all an ACM header can say) */

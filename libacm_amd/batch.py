@@ -120,6 +120,7 @@ class GpuDecoder:
         self.parse = parse
         self.timing = None
         self.index_timing = None
+        self._chans = None              # crop_batch(mix=True): (the index object, channels per file of the files it belongs to)
         torch.cuda.set_device(ordinal)
         # the library runs on a stream of its own (torch's current stream is usually the null stream, which
         # acmhip_device_open does not adopt); __call__ orders the two around the torch-owned PCM tensor
@@ -180,19 +181,38 @@ class GpuDecoder:
             self.dev, files, index, windows, d_pcm.data_ptr(), d_pcm.numel(), fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
         return d_pcm, offsets, words, statuses
 
-    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None):
+    def _header_channels(self, files, index):
+        """[f]: 1 or 2, the channel count the header of files[f] says, 0 for a file without one.  Read once per index: the counts are
+        as permanent as the block index that belongs to the same files, so they are kept with the index object of the last call and a
+        step that crops the same files with the same index reads no header again"""
+        kept = self._chans
+        if kept is None or kept[0] is not index or len(kept[1]) != len(files):
+            found = capi.header_channels(files)
+            kept = self._chans = (index, [found[f] if found.get(f) in (1, 2) else 0 for f in range(len(files))])
+        return kept[1]
+
+    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False):
         """Random-access crops as one batch tensor: windows = (file_no, first_frame, n_frames) triples with n_frames <= frames, index as
         for crop().  -> (batch, frames_delivered, statuses): batch is a tensor of this decoder's dtype shaped [N, channels, frames]
         (planar) or [N, frames, channels], row k the crop's frames with zeros behind them - also where a window is clipped by the end of
         its stream, starts behind it, or is turned away: a file that is not ACM, a stale index, a file whose channel count is not
         `channels` (status capi.ERR_ARG).  One copy kernel behind the synthesis lays the rows out (acm_batch_decode_windows_dense); no
         per-window slicing on the torch side.  out: a contiguous tensor of this decoder's dtype with at least N * channels * frames
-        elements is written into (the batch is a view of its first elements) instead of a new one, as in crop()."""
+        elements is written into (the batch is a view of its first elements) instead of a new one, as in crop().
+        mix=True (ACM_DENSE_MIX): mono and stereo files in one batch.  Windows are (file_no, first_frame, n_frames) for any file; a file
+        with the other channel count is decoded and converted instead of turned away - stereo becomes (L + R) >> 1, a mono sample goes
+        into both channels - and frames_delivered counts its frames.  The channel counts are read from the headers once per `index`
+        object and kept with it: pass the index of the files, and a new one with new files, as crop() needs anyway."""
         torch = self.torch
         files = [_load(f) for f in files]
         if index is None:
             index = self.build_index(files)
         n = len(windows)
+        # samples per frame of every window's file: its own header's with mix (a file without one is checked as the batch's kind)
+        per = [channels] * n
+        if mix:
+            own = self._header_channels(files, index)
+            per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
         shape = (n, channels, frames) if planar else (n, frames, channels)
         need = n * channels * frames
         if out is not None and out.dtype != self.dtype:
@@ -201,10 +221,10 @@ class GpuDecoder:
         d_pcm = out if fits else torch.empty(max(need, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
         torch.cuda.current_stream().synchronize()
         statuses, words, self.timing = capi.batch_decode_windows_dense(
-            self.dev, files, index, [(f, first * channels, count * channels) for f, first, count in windows], d_pcm.data_ptr(), d_pcm.numel(),
-            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32)
+            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], d_pcm.data_ptr(), d_pcm.numel(),
+            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix)
         # the call returns with its stream drained: the batch is complete and visible to torch's streams
-        return d_pcm.reshape(-1)[:need].view(shape), [w // channels for w in words], statuses
+        return d_pcm.reshape(-1)[:need].view(shape), [w // c for w, c in zip(words, per)], statuses
 
 
 def _trace(trace, *ev):

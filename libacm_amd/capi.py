@@ -140,6 +140,7 @@ class DenseOpts(C.Structure):
 
 
 DENSE_PLANAR = 1
+DENSE_MIX = 4                   # windows of files with the other channel count are converted (mono <-> stereo), not turned away
 
 
 class BatchIndexOut(C.Structure):
@@ -326,6 +327,23 @@ def probe(data, force_chans=0):
     info = StageInfo()
     rc = lib().acm_stage_probe(a.ctypes.data, a.size, force_chans, C.byref(info))
     return rc, info
+
+
+def header_channels(files, which=None, force_chans=0):
+    """{file number: channels the header of files[number] says} for the numbers in `which` (default: all) whose file is ACM - the
+    probe of probe(); no file image is copied"""
+    probe_fn, info, out = lib().acm_stage_probe, StageInfo(), {}
+    ref = C.byref(info)
+    for f in range(len(files)) if which is None else which:
+        data = files[f]
+        if isinstance(data, bytes):
+            rc = probe_fn(data, len(data), force_chans, ref)
+        else:
+            a = _as_u8(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+            rc = probe_fn(a.ctypes.data, a.size, force_chans, ref)
+        if rc == 0:
+            out[f] = info.channels
+    return out
 
 
 def stage_file(data, force_chans=0, idx_out=None, hdr_out=None):
@@ -1056,16 +1074,18 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
 
 def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                               check=True):
+                               check=True, mix=False):
     """acm_batch_decode_windows_dense: the windows as len(windows) rows of frames * channels samples in d_pcm (int16, or float32 with
     f32=True), row k at sample k * frames * channels - interleaved, or a plane per channel with planar=True - zeros behind what a window
-    delivers.  Returns (statuses, words, WindowTiming).  check=False (tests of the refusals): the return code instead of an exception, as a
-    fourth element; dense_flags: the raw acm_dense_opts.flags instead of planar; frames None: no acm_dense_opts at all; dev None: the call's
+    delivers.  mix=True (ACM_DENSE_MIX): a window of a file with the other channel count counts that file's own samples and its row is
+    converted - stereo averaged into mono, mono repeated in both channels.  Returns (statuses, words, WindowTiming).  check=False (tests
+    of the refusals): the return code instead of an exception, as a fourth element; dense_flags: the raw acm_dense_opts.flags instead of planar and mix; frames None: no acm_dense_opts at all; dev None: the call's
     own answer to a missing handle."""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
-    dense = None if frames is None else DenseOpts(frames, channels, (DENSE_PLANAR if planar else 0) if dense_flags is None else dense_flags)
+    dense = None if frames is None else DenseOpts(frames, channels, ((DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0)) if dense_flags is None
+                                                      else dense_flags)
     tm = WindowTiming()
     _fill(dev)
     rc = lib().acm_batch_decode_windows_dense(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),

@@ -17,7 +17,8 @@
  *
  * acm_batch_decode_windows_dense is the same run with another end: the windows are synthesised into the handle's own PCM arena, nothing
  * is read back, and one launch of acm_dense_rows (acm_dense.hip) lays them out as the rows of the caller's tensor.  What that call
- * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's.
+ * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's - also whether, with ACM_DENSE_MIX, a row
+ * of the table converts between mono and stereo: then the launch is acm_dense_mixed's (acm_dense_mix.hip) instead.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -292,16 +293,17 @@ int WinRun::synthesise_and_gather()
 	if (!ps.descs.empty())
 		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
 	const size_t at = dense->table_off(L), bytes = dense->table_bytes();
-	acm_dense_rows(*dense, L.slots.data(), wins, reinterpret_cast<AcmDenseRow *>(h_jobs + at));
+	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX) */
+	const bool mixed = acm_dense_rows(*dense, L.slots.data(), wins, reinterpret_cast<AcmDenseRow *>(h_jobs + at));
 	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
 	tm.h2d_bytes += bytes;
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
-	const int e = acmk_launch_dense_rows(d_pcm, reinterpret_cast<const AcmDenseRow *>(d_jobs + at), L.slots.size(), dense_out, dense->frames,
-					     dense->channels, dense->planar, dense->f32, st);
+	const int e = (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, reinterpret_cast<const AcmDenseRow *>(d_jobs + at), L.slots.size(),
+										 dense_out, dense->frames, dense->channels, dense->planar, dense->f32, st);
 	if (e != 0)
-		return acmhip_report_hip(e, "acmk_launch_dense_rows");
+		return acmhip_report_hip(e, mixed ? "acmk_launch_dense_mixed" : "acmk_launch_dense_rows");
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
 	ACM_HIP_TRY(hipStreamSynchronize(st));
 	float ms = 0;

@@ -14,6 +14,9 @@
  * sample of the vector, so every load lies inside the row's own samples rounded out to 16 bytes, which a window's 64-sample
  * slot contains.  Narrow accesses: the up to 7 samples in front of the body, the up to 7 behind it, and the one vector in which a
  * short row's samples end.  No LDS, no scratch (every register array is indexed by constants after unrolling).
+ *
+ * The line loads, the funnel and the line stores are acm_dense_vec.h's, shared with acm_dense_mix.hip - the kernel that takes this
+ * one's place in a call whose rows convert between mono and stereo (ACM_DENSE_MIX).
  */
 #include <hip/hip_runtime.h>
 
@@ -21,93 +24,10 @@
 
 #include <algorithm>
 
+#include "acm_dense_vec.h"
 #include "acm_device.h"
 
 namespace {
-
-constexpr int DENSE_BLOCK = 256;        /* lanes per workgroup = vectors per unit */
-constexpr int DENSE_VEC = 8;            /* output samples per lane and body access */
-constexpr uint32_t DENSE_MAX_GRID = 1u << 20;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <bool NT, typename V> __device__ __forceinline__ void store_line(V *at, V v)
-{
-	if (NT)
-		__builtin_nontemporal_store(v, at);
-	else
-		*at = v;
-}
-
-/* 8 samples from p on, every STRIDE-th: p lies sh (even, wavefront-uniform) bytes into an aligned 16-byte line */
-template <int STRIDE> __device__ __forceinline__ void load_vec(const int16_t *p, uint32_t sh, int (&s)[DENSE_VEC])
-{
-	constexpr int LINES = STRIDE + 1;                               /* aligned lines that can hold a part of the vector's bytes ... */
-	constexpr uint32_t USED = STRIDE == 1 ? 16 : 30;                /* ... bytes [sh, sh + USED) counted from the first line */
-	const u32x4 *line = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(p) - sh);
-	uint32_t d[4 * LINES];
-#pragma unroll
-	for (int v = 0; v < LINES; v++) {
-		u32x4 x = { 0, 0, 0, 0 };
-		if (16u * v < sh + USED)                                /* a line behind the vector's last sample is not touched */
-			x = line[v];
-		d[4 * v] = x.x;
-		d[4 * v + 1] = x.y;
-		d[4 * v + 2] = x.z;
-		d[4 * v + 3] = x.w;
-	}
-	/* whole dwords of the shift: d[i] <- d[i + (sh >> 2)], for the 4 * STRIDE + 1 dwords the funnel reads */
-	if (sh & 4) {
-#pragma unroll
-		for (int i = 0; i + 1 < 4 * LINES; i++)
-			d[i] = d[i + 1];
-	}
-	if (sh & 8) {
-#pragma unroll
-		for (int i = 0; i + 2 < 4 * LINES; i++)
-			d[i] = d[i + 2];
-	}
-	const uint32_t r = sh & 3;                                      /* 0 or 2 */
-#pragma unroll
-	for (int j = 0; j < 4 * STRIDE; j++) {
-		const uint32_t e = __builtin_amdgcn_alignbyte(d[j + 1], d[j], r);
-		if (STRIDE == 1) {
-			s[2 * j] = (int16_t)(e & 0xFFFFu);
-			s[2 * j + 1] = (int16_t)(e >> 16);
-		} else {
-			s[j] = (int16_t)(e & 0xFFFFu);                  /* the other channel's sample is the high half */
-		}
-	}
-}
-
-template <bool NT> __device__ __forceinline__ void store_vec(int16_t *at, const int (&s)[DENSE_VEC])
-{
-	u32x4 w;
-	w.x = ((uint32_t)s[0] & 0xFFFFu) | ((uint32_t)s[1] << 16);
-	w.y = ((uint32_t)s[2] & 0xFFFFu) | ((uint32_t)s[3] << 16);
-	w.z = ((uint32_t)s[4] & 0xFFFFu) | ((uint32_t)s[5] << 16);
-	w.w = ((uint32_t)s[6] & 0xFFFFu) | ((uint32_t)s[7] << 16);
-	store_line<NT>(reinterpret_cast<u32x4 *>(at), w);
-}
-
-__device__ __forceinline__ float to_out(float *, int s) { return (float)s * 0x1p-15f; }
-__device__ __forceinline__ int16_t to_out(int16_t *, int s) { return (int16_t)s; }
-
-template <bool NT> __device__ __forceinline__ void store_vec(float *at, const int (&s)[DENSE_VEC])
-{
-	f32x4 a, b;
-	a.x = to_out(at, s[0]);
-	a.y = to_out(at, s[1]);
-	a.z = to_out(at, s[2]);
-	a.w = to_out(at, s[3]);
-	b.x = to_out(at, s[4]);
-	b.y = to_out(at, s[5]);
-	b.z = to_out(at, s[6]);
-	b.w = to_out(at, s[7]);
-	store_line<NT>(reinterpret_cast<f32x4 *>(at), a);
-	store_line<NT>(reinterpret_cast<f32x4 *>(at) + 1, b);
-}
 
 /* sub_len: output samples of a sub-row (frames with STRIDE 2, else the whole row); units: workgroups per sub-row */
 template <typename OUT, int STRIDE, bool NT>

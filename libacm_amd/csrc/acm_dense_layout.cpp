@@ -11,7 +11,7 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 {
 	DenseLayout &D = *out;
 	D = DenseLayout();
-	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) || (dense->flags & ~ACM_DENSE_PLANAR))
+	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) || (dense->flags & ~(ACM_DENSE_PLANAR | ACM_DENSE_MIX)))
 		return ACMHIP_ERR_ARG;
 	/* padding has one meaning in the signed little-endian writer only; the staged forms of a prestaged or packed batch are not a window's */
 	if (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE || opts.parse > ACM_BATCH_PARSE_AUTO || opts.prestaged || (opts.flags & ACM_BATCH_STAGE_PACKED))
@@ -22,22 +22,42 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 	D.channels = dense->channels;
 	D.row_words = D.frames * D.channels;
 	D.planar = (dense->flags & ACM_DENSE_PLANAR) != 0;
+	D.mix = (dense->flags & ACM_DENSE_MIX) != 0;
 	D.f32 = (opts.flags & ACM_BATCH_PCM_F32) != 0;
 	if (nwin && D.row_words > ~0ull / nwin)
 		return ACMHIP_ERR_ARG;
 	D.out_words = nwin * D.row_words;
 	if (opts.d_pcm_words < D.out_words)
 		return ACMHIP_ERR_ARG;
-	for (size_t k = 0; k < nwin; k++)
-		if (wins[k].max_words > D.row_words || wins[k].first_word % D.channels || wins[k].max_words % D.channels)
+	/* a converting row's record carries its mode above the count of its samples, of which it has 2 * frames at most */
+	if (D.mix && D.frames > (ACM_DENSE_COUNT_MASK >> 1))
+		return ACMHIP_ERR_ARG;
+	/* an item that is not ACM, or whose index it cannot have, has no channel count: its windows deliver nothing anyway */
+	auto has_chans = [&](const acm_batch_window &w) { return w.item < n && items[w.item].ok; };
+	/* ... and with ACM_DENSE_MIX one that has the other of the two counts is converted */
+	auto converts = [&](const acm_batch_window &w) {
+		if (!D.mix || !has_chans(w))
+			return false;
+		const uint32_t c = items[w.item].info.channels;
+		return c != D.channels && (c == 1 || c == 2);
+	};
+	for (size_t k = 0; k < nwin; k++) {
+		/* whole frames, T of them at most - of the batch's channel count, or of the item's own where the window is converted */
+		const uint32_t c = converts(wins[k]) ? items[wins[k].item].info.channels : D.channels;
+		if (wins[k].max_words > D.frames * c || wins[k].first_word % c || wins[k].max_words % c)
 			return ACMHIP_ERR_ARG;
+	}
 
 	D.wins.assign(wins, wins + nwin);
 	D.rejected.assign(nwin, 0);
+	D.mode.assign(nwin, D.channels == 2 && D.planar ? ACM_DENSE_MODE_SPLIT : ACM_DENSE_MODE_COPY);
 	for (size_t k = 0; k < nwin; k++) {
 		const acm_batch_window &w = wins[k];
-		/* an item that is not ACM, or whose index it cannot have, has no channel count to compare: its windows deliver nothing anyway */
-		if (w.item < n && items[w.item].ok && items[w.item].info.channels != D.channels) {
+		if (!has_chans(w) || items[w.item].info.channels == D.channels)
+			continue;
+		if (converts(w)) {
+			D.mode[k] = D.channels == 1 ? ACM_DENSE_MODE_DOWN : D.planar ? ACM_DENSE_MODE_UP_PLANAR : ACM_DENSE_MODE_UP_INTER;
+		} else {
 			D.rejected[k] = 1;
 			D.wins[k].max_words = 0;
 		}
@@ -57,12 +77,16 @@ void acm_dense_report(const DenseLayout &D, const WindowSlot &s, size_t k, acm_b
 	w->slot_words = D.row_words;
 }
 
-void acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows)
+bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows)
 {
+	bool converts = false;
 	for (size_t k = 0; k < D.wins.size(); k++) {
 		const uint64_t count = slots[k].active ? std::min(final[k].words, slots[k].words) : 0;
-		rows[k] = AcmDenseRow{ count ? slots[k].dev_off : 0, count };
+		const uint64_t mode = count && D.mode[k] >= ACM_DENSE_MODE_DOWN ? D.mode[k] : 0;       /* a row of zeros is one in any mode */
+		rows[k] = AcmDenseRow{ count ? slots[k].dev_off : 0, count | mode << ACM_DENSE_MODE_SHIFT };
+		converts |= mode != 0;
 	}
+	return converts;
 }
 
 } // namespace acmbatch
@@ -105,12 +129,17 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 				wins[k].words = final_words[k];
 		}
 		std::vector<AcmDenseRow> rows(nwin);
-		acm_dense_rows(D, L.slots.data(), wins.data(), rows.data());
+		const bool converts = acm_dense_rows(D, L.slots.data(), wins.data(), rows.data());
 		if (nwin) {
 			visit(ctx, "wins", w.data(), 3 * sizeof(uint64_t), nwin);
 			visit(ctx, "rejected", rej.data(), sizeof(uint64_t), nwin);
 			visit(ctx, "report", rep.data(), 5 * sizeof(uint64_t), nwin);
 			visit(ctx, "rows", rows.data(), sizeof(AcmDenseRow), nwin);
+		}
+		if (D.mix) {
+			std::vector<uint64_t> mix(D.mode.begin(), D.mode.end());
+			mix.push_back(converts);
+			visit(ctx, "mix", mix.data(), sizeof(uint64_t), mix.size());
 		}
 	}
 	const uint64_t totals[] = { D.frames, D.row_words, D.channels, (uint64_t)D.planar, (uint64_t)D.f32, D.out_words, D.pcm_arena_words(L.pcm_total),

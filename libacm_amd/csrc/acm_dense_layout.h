@@ -1,8 +1,9 @@
 /*
  * acm_dense_layout.h - the device-free half of acm_batch_decode_windows_dense (acm_batch_windows.cpp): whether the call is one the
  * dense writer takes, which windows it turns away softly, how large the output is, and - once staging has settled what every
- * window delivers - the row table the gather kernel (acm_dense.hip) reads.  Internal.  Neither this header nor acm_dense_layout.cpp
- * knows a device (tests/test_dense_crops.py); where a window's samples sit in the intermediate arena stays acm_window_layout.cpp's.
+ * window delivers - the row table the gather kernel (acm_dense.hip; acm_dense_mix.hip where a row converts) reads.  Internal.
+ * Neither this header nor acm_dense_layout.cpp knows a device (tests/test_dense_crops.py); where a window's samples sit in the
+ * intermediate arena stays acm_window_layout.cpp's.
  */
 #ifndef ACM_DENSE_LAYOUT_H
 #define ACM_DENSE_LAYOUT_H
@@ -24,7 +25,9 @@ struct DenseLayout {
 	bool planar = false, f32 = false;
 	uint64_t out_words = 0;                 /* nwin * R: what opts->d_pcm must hold, in samples of the output type */
 	std::vector<acm_batch_window> wins;     /* the windows as acm_window_layout gets them: one turned away asks for no samples */
-	std::vector<uint8_t> rejected;          /* [k]: window k's item has another channel count than the batch */
+	std::vector<uint8_t> rejected;          /* [k]: window k's item has another channel count than the batch (no ACM_DENSE_MIX) */
+	bool mix = false;                       /* ACM_DENSE_MIX: such a window is decoded and converted instead */
+	std::vector<uint8_t> mode;              /* [k]: AcmDenseMode - what row k does with its window's samples, if it gets any */
 	acm_batch_opts inner{};                 /* the options of the windowed decode underneath: int16 rows into the handle's own arena */
 	uint64_t pcm_arena_words(uint64_t pcm_total) const { return pcm_total + ACM_DENSE_PCM_SLACK; }
 	/* the row table travels behind the device parser's tables in the H_JOBS / D_JOBS arenas */
@@ -40,8 +43,10 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 /* what the caller's window k receives, from its slot of the layout underneath */
 void acm_dense_report(const DenseLayout &D, const WindowSlot &s, size_t k, acm_batch_window *w);
 
-/* the row table: final[k].words is what window k delivers after staging (0: the host stager turned it away) */
-void acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows);
+/* the row table: final[k].words is what window k delivers after staging (0: the host stager turned it away).  Returns whether a row
+ * converts: then the table is acm_dense_mix.hip's to read, else it is - bit for bit what a call without ACM_DENSE_MIX makes -
+ * acm_dense.hip's */
+bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows);
 
 } // namespace acmbatch
 
@@ -50,8 +55,8 @@ extern "C" {
  * null: what the window layout says) stands for what staging left of every window.  A refused call visits "totals" alone.  Tables,
  * as uint64 words: "wins" (3 per window: item, first_word, max_words as the window layout gets them), "rejected", "report" (5 per
  * window: status (sign-extended), words, dev_off, slot_off, slot_words as the caller receives them), "rows" (2 per window: src,
- * count), "totals": frames, row_words, channels, planar, f32, out_words, pcm_arena_words, blocks_parsed, table_off, table_bytes and
- * the return code */
+ * count), with ACM_DENSE_MIX alone "mix" (nwin + 1 words: AcmDenseMode per window, then 1 if a row converts, else 0), "totals":
+ * frames, row_words, channels, planar, f32, out_words, pcm_arena_words, blocks_parsed, table_off, table_bytes and the return code */
 int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status, const uint64_t *whole,
 			    const acm_block_mark *const *marks, const uint32_t *blocks, size_t n, const uint64_t *win3, size_t nwin,
 			    const acm_batch_opts *opts, const acm_dense_opts *dense, const uint64_t *final_words,

@@ -105,6 +105,18 @@ struct AcmDenseRow {
 	uint64_t src;
 	uint64_t count;        /* 0: the row is all zeros and src is not read */
 };
+/* ACM_DENSE_MIX (acm_dense_mix.hip): what a row does with its source samples.  A converting row carries its mode in the bits of
+ * `count` from ACM_DENSE_MODE_SHIFT on, and `count` is then the SOURCE samples; a row that copies or splits has none of them set, so
+ * the table of a call in which nothing converts is the one acm_dense_rows reads */
+enum AcmDenseMode {
+	ACM_DENSE_MODE_COPY = 0,        /* the item has the batch's channel count, rows interleaved (or mono) */
+	ACM_DENSE_MODE_SPLIT = 1,       /* ... stereo rows as a plane per channel */
+	ACM_DENSE_MODE_DOWN = 2,        /* stereo item, mono batch: (L + R) >> 1 */
+	ACM_DENSE_MODE_UP_INTER = 3,    /* mono item, stereo batch, interleaved: the sample in both channels */
+	ACM_DENSE_MODE_UP_PLANAR = 4,   /* mono item, stereo batch, planar: the sample in both planes */
+};
+#define ACM_DENSE_MODE_SHIFT 56
+#define ACM_DENSE_COUNT_MASK ((1ull << ACM_DENSE_MODE_SHIFT) - 1)
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -162,8 +174,8 @@ void acmhip_set_error_text(const char *text);                    /* what acmhip_
 /* Two kinds of acmk_* functions.  The ones that launch nothing - a build's tile rows, threads, grid, first-pass depth, lead-in, packed
  * slots, the split of a chunk table, what the device parser accepts and where it cuts - live in acm_kernel_geo.cpp: plain C++ over the
  * tables of acm_kernel_geo.h, linkable without a device or a kernel.  The launchers (acmk_launch_*, acmk_warmup) live with their kernels in
- * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip and acm_dense.hip, and take block size and grid from the queries.
- * `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
+ * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip, acm_dense.hip and acm_dense_mix.hip, and take block size and
+ * grid from the queries.  `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
  * d_pcm (and d_sink) then hold floats and the streams' pcm_off / n_emit count them (acmhip_plan_launch_f32) */
 #define ACMK_FMT_F32 0x100u
 /* one number over every table of acm_kernel_geo.h, as the planner's half (acm_kernel_geo.cpp) and the kernels' half (acm_kernels.hip) of
@@ -297,6 +309,12 @@ int acmk_launch_emit_f32(const AcmDevStream *d_streams, const uint32_t *d_list, 
  * at least one of a row's samples.  d_out: aligned to its element.  One launch, nothing allocated, nothing waited for */
 int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
 			   int planar, int f32, void *stream);
+/* acm_dense_mix.hip: the same launch for a row table in which some row carries a converting mode (AcmDenseMode) - the one the
+ * batch's layout allows: DOWN with channels == 1, UP_INTER with channels == 2, UP_PLANAR with channels == 2 and planar.  Rows without
+ * mode bits are written as acmk_launch_dense_rows writes them.  The same demands on d_src and d_out; a converting row's samples lie
+ * inside its slot too */
+int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
+			    int planar, int f32, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,16 @@ runs out of time ends the probe.
   bytes the launch moves (2 per sample read, 2 or 4 written, from the shapes) and the box's copy kernel over the same byte count
   (profiles/ubench/libcopybw.so).  ACM_HIP_LIB=libacm_amd/lib/exp/tuning.so ACM_DENSE_NT=1 runs it with non-temporal stores.
 
-    python profiles/dense_crop_probe.py [--windows 1024,16384] [--out probe_out/dense_crop.json]
+  --mix (profiles/dense_mix_notes.txt): the streams alternate mono and stereo and levels 7, 8, 9 file by file, as workload.corpus_shapes
+  does, each with the default workload's sample count; batches of C = 1 and C = 2, float32 [N, C, T] and int16 [N, T, C].
+    (a) crop_batch(mix=True)                                   - one call, acm_dense_mixed converts the rows of the other channel count
+    (b) two crop_batch calls, one per channel count, the torch conversion of the second one's rows - the integer (L + R) >> 1, or the
+        sample into both channels - and an index_copy of both into the batch: the way to the same tensor without ACM_DENSE_MIX
+  With --step kernel --mix the trace holds acm_dense_mixed (the mixed batch) and acm_dense_rows (a batch of equal bytes over the files
+  of one channel count) side by side.  --parent-lib <the parent commit's libacm_hip.so>: per shape also the batch of one channel count -
+  the call that must cost what it cost - on that library and, without and with the flag alternating, on this tree's.
+
+    python profiles/dense_crop_probe.py [--mix] [--windows 1024,16384] [--out probe_out/dense_crop.json]
 """
 import argparse
 import ctypes as C
@@ -42,6 +51,9 @@ def make_files(args):
     from libacm_amd import synth, workload
 
     def one(i):
+        if args.mix:
+            level = 7 + i % 3
+            return synth.generate(seed=synth.BASE_SEED + i, level=level, rows=args.rows, nblocks=args.blocks << (args.level - level), channels=1 + i % 2)
         return synth.generate(seed=synth.BASE_SEED + i, level=args.level, rows=args.rows, nblocks=args.blocks)
     with ThreadPoolExecutor(max_workers=min(16, workload.usable_cpus())) as ex:
         return list(ex.map(one, range(args.streams)))
@@ -132,6 +144,143 @@ def step_compare(args, n, f32):
     return {"%d_windows_%s" % (n, "float32_planar" if f32 else "int16_interleaved"): res}
 
 
+def mix_windows(args, n, only=None):
+    """(file, first_frame, FRAMES) over the alternating streams (file i has 1 + i % 2 channels); only: files of that channel count"""
+    import numpy as np
+    rng = np.random.default_rng(22051)
+    total = args.blocks * args.rows << args.level
+    wins = []
+    for k in range(n):
+        f = k % args.streams if only is None else (2 * k + only - 1) % args.streams
+        frames = total // (1 + f % 2)
+        wins.append((f, int(rng.integers(0, frames - FRAMES + (FRAMES // 4 if k % 64 == 63 else 0))), FRAMES))
+    return wins
+
+
+def step_mix(args, n, f32, C):
+    import numpy as np
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32 if f32 else torch.int16)
+    index = dec.build_index(files)
+    wins = mix_windows(args, n)
+    planar = f32
+    own = [k for k, w in enumerate(wins) if 1 + w[0] % 2 == C]
+    other = [k for k, w in enumerate(wins) if 1 + w[0] % 2 != C]
+    i_own, i_other = (torch.tensor(v, dtype=torch.int64, device="cuda:0") for v in (own, other))
+    w_own, w_other = [wins[k] for k in own], [wins[k] for k in other]
+    out_a = torch.empty(n * C * FRAMES, dtype=dec.dtype, device="cuda:0")
+    buf_own = torch.empty(len(own) * C * FRAMES, dtype=dec.dtype, device="cuda:0")
+    buf_other = torch.empty(len(other) * (3 - C) * FRAMES, dtype=dec.dtype, device="cuda:0")
+    keep = {}
+
+    def a_mix():
+        keep["a"], keep["frames"], keep["st"] = dec.crop_batch(files, wins, FRAMES, channels=C, planar=planar, index=index, out=out_a, mix=True)
+        keep["a_kernel_ms"] = dec.timing.kernel_s * 1e3
+
+    def b_two_calls():
+        x, _, _ = dec.crop_batch(files, w_own, FRAMES, channels=C, planar=planar, index=index, out=buf_own)
+        y, _, _ = dec.crop_batch(files, w_other, FRAMES, channels=3 - C, planar=False, index=index, out=buf_other)          # [n, T, 3 - C]
+        if C == 1:
+            q = (y * 32768.0).to(torch.int32) if f32 else y.to(torch.int32)
+            q = (q[:, :, 0] + q[:, :, 1]) >> 1
+            y = (q.to(torch.float32) * 2.0 ** -15 if f32 else q.to(torch.int16)).view((len(other), 1, FRAMES) if planar else (len(other), FRAMES, 1))
+        else:
+            y = y.view(len(other), 1, FRAMES).expand(-1, 2, -1) if planar else y.expand(-1, -1, 2)
+        out = torch.empty((n,) + tuple(x.shape[1:]), dtype=dec.dtype, device="cuda:0")
+        out.index_copy_(0, i_own, x)
+        out.index_copy_(0, i_other, y.contiguous())
+        keep["b"] = out
+
+    variants = [("a_crop_batch_mix", a_mix), ("b_two_calls_convert_index_copy", b_two_calls)]
+    times = {name: [] for name, _ in variants}
+    for r in range(args.warmup + args.reps):
+        for name, fn in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if r >= args.warmup:
+                times[name].append(time.perf_counter() - t0)
+    res = {name: stats(t) for name, t in times.items()}
+    a, b = res["a_crop_batch_mix"], res["b_two_calls_convert_index_copy"]
+    res["tensors_equal"] = bool(np.array_equal(keep["a"].cpu().numpy().view(np.uint8), keep["b"].cpu().numpy().view(np.uint8)))
+    pair = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+    res["verdict"] = dict(two_calls_min_ms=b["min_ms"], mix_max_ms=a["max_ms"], margin_ms=round(b["min_ms"] - a["max_ms"], 3),
+                          spread_of_the_two_compared_ms=round(pair, 3), mix_wins=bool(b["min_ms"] - a["max_ms"] > pair))
+    res["inside_the_call"] = dict(mix_kernel_ms=round(keep["a_kernel_ms"], 4), converted_rows=len(other),
+                                  clipped_windows=int(sum(1 for f in keep["frames"] if f < FRAMES)), ok=all(s == 0 for s in keep["st"]))
+    dec.dev.close()
+    return {"%d_windows_c%d_%s" % (n, C, "float32_planar" if f32 else "int16_interleaved"): res}
+
+
+def step_flag(args, n, f32, ch):
+    """a batch over the files of ONE channel count - the call that runs acm_dense_rows whatever the flag says - without ACM_DENSE_MIX and,
+    where the loaded library knows the flag, with it, alternating; ACM_HIP_LIB names the library (the parent commit's knows no flag)"""
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32 if f32 else torch.int16)
+    index = dec.build_index(files)
+    wins = mix_windows(args, n, only=ch)
+    buf = torch.empty(n * ch * FRAMES, dtype=dec.dtype, device="cuda:0")
+    variants = [("plain", False)]
+    try:
+        dec.crop_batch(files, wins[:4], FRAMES, channels=ch, planar=f32, index=index, out=buf, mix=True)
+        variants.append(("flag", True))
+    except Exception:
+        pass
+    times = {name: [] for name, _ in variants}
+    for r in range(args.warmup + args.reps):
+        for name, mix in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dec.crop_batch(files, wins, FRAMES, channels=ch, planar=f32, index=index, out=buf, mix=mix)
+            torch.cuda.synchronize()
+            if r >= args.warmup:
+                times[name].append(time.perf_counter() - t0)
+    dec.dev.close()
+    return {name: stats(t) for name, t in times.items()}
+
+
+def step_kernel_mix(args):
+    """REPS calls per shape of the mixed batch (acm_dense_mixed) and of a batch over the files of one channel count (acm_dense_rows): the
+    launch's own durations are the trace's; the call's wall clock and event time are printed here"""
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    out = {}
+    cb = C.CDLL(os.path.join(ROOT, "profiles", "ubench", "libcopybw.so"))
+    cb.acm_copy_ceiling_gbs.restype = C.c_double
+    cb.acm_copy_ceiling_gbs.argtypes = [C.c_size_t, C.c_char_p, C.c_size_t]
+    for f32 in (True, False):
+        dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32 if f32 else torch.int16)
+        index = dec.build_index(files)
+        for n in args.windows:
+            for ch in (1, 2):
+                buf = torch.empty(n * ch * FRAMES, dtype=dec.dtype, device="cuda:0")
+                for what, wins, mix in (("mixed", mix_windows(args, n), True), ("one_count", mix_windows(args, n, only=ch), False)):
+                    k_ms, wall = [], []
+                    for r in range(args.warmup + args.reps):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        b, frames, st = dec.crop_batch(files, wins, FRAMES, channels=ch, planar=f32, index=index, out=buf, mix=mix)
+                        if r >= args.warmup:
+                            wall.append(time.perf_counter() - t0)
+                            k_ms.append(dec.timing.kernel_s)
+                    read = 2 * sum(fr * (1 + w[0] % 2) for fr, w in zip(frames, wins))
+                    moved = read + (4 if f32 else 2) * n * ch * FRAMES
+                    name = C.create_string_buffer(96)
+                    gbs = cb.acm_copy_ceiling_gbs(moved // 2 // 4096 * 4096, name, 96)
+                    out["%d_windows_c%d_%s_%s" % (n, ch, "float32" if f32 else "int16", what)] = dict(
+                        call_wall=stats(wall), synthesis_plus_gather_events=stats(k_ms), gather_bytes_moved=int(moved),
+                        copy_kernel_gbs_same_bytes=round(gbs, 1), copy_kernel_ms_same_bytes=round(moved / gbs / 1e6, 4) if gbs > 0 else None)
+                del buf
+        dec.dev.close()
+    return out
+
+
 def step_kernel(args):
     import torch
     from libacm_amd import batch, capi
@@ -174,22 +323,41 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--step-seconds", type=int, default=280, help="time limit of each GPU step")
     ap.add_argument("--out", default=os.path.join(ROOT, "probe_out", "dense_crop.json"))
-    ap.add_argument("--step", help="(internal) compare:<windows>:<f32 0|1>, or kernel: run one step in this process and print its JSON")
+    ap.add_argument("--mix", action="store_true", help="mono and stereo streams in one batch: crop_batch(mix=True) against two calls + torch")
+    ap.add_argument("--parent-lib", help="with --mix: the parent commit's libacm_hip.so; adds, per shape, a batch of one channel count on that "
+                    "library and on this tree's without and with the flag (each library a child process of its own)")
+    ap.add_argument("--step", help="(internal) compare:<windows>:<f32 0|1>, mix:<windows>:<f32>:<channels>, or kernel: run one step in this "
+                    "process and print its JSON")
     args = ap.parse_args()
     if args.step:
         if args.step == "kernel":
-            res = step_kernel(args)
+            res = step_kernel_mix(args) if args.mix else step_kernel(args)
+        elif args.step.startswith("flag:"):
+            _, n, f32, ch = args.step.split(":")
+            res = step_flag(args, int(n), f32 == "1", int(ch))
+        elif args.step.startswith("mix:"):
+            _, n, f32, ch = args.step.split(":")
+            res = step_mix(args, int(n), f32 == "1", int(ch))
         else:
             _, n, f32 = args.step.split(":")
             res = step_compare(args, int(n), f32 == "1")
         print("RESULT " + json.dumps(res))
         return 0
     result = dict(workload=dict(streams=args.streams, level=args.level, rows=args.rows, blocks=args.blocks, frames=FRAMES))
-    for step in ["compare:%d:%d" % (n, f32) for n in args.windows for f32 in (1, 0)]:
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--host-index-max", str(args.host_index_max)] + \
+    steps = ["compare:%d:%d" % (n, f32) for n in args.windows for f32 in (1, 0)]
+    if args.mix:
+        steps = ["mix:%d:%d:%d" % (n, f32, ch) for n in args.windows for f32 in (1, 0) for ch in (1, 2)]
+    if args.mix and args.parent_lib:
+        steps += ["flag:%d:%d:%d:%s" % (n, f32, ch, lib) for n in args.windows for f32 in (1, 0) for ch in (1, 2) for lib in ("parent", "tree")]
+    for step in steps:
+        env = dict(os.environ)
+        if step.endswith(":parent"):
+            env["ACM_HIP_LIB"] = os.path.abspath(args.parent_lib)
+        key, step = step, step.rsplit(":", 1)[0] if step.startswith("flag:") else step
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--host-index-max", str(args.host_index_max)] + ["--mix"] * args.mix + \
               [a for k in ("streams", "level", "rows", "blocks", "warmup", "reps") for a in ("--" + k, str(getattr(args, k)))]
         try:
-            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.step_seconds)
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.step_seconds, env=env)
         except subprocess.TimeoutExpired:
             print("step %s ran out of time: nothing more is started" % step)
             return 1
@@ -197,7 +365,8 @@ def main():
         if r.returncode != 0 or not line:
             print("step %s failed (%d): nothing more is started\n%s" % (step, r.returncode, r.stdout[-3000:]))
             return 1
-        result.update(json.loads(line[-1][7:]))
+        got = json.loads(line[-1][7:])
+        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else got)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
