@@ -675,14 +675,73 @@ int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, s
  * Where no row of a call converts - every file has C channels, or the others' windows deliver nothing - the launch is
  * acm_dense_rows as without the flag; else one launch of acm_dense_mixed (csrc/acm_dense_mix.hip) takes its place and writes the
  * plain rows as well.
+ *
+ * ACM_DENSE_RESAMPLE: files of several sample rates in one batch of rate Ro = dense->rate.  Without the flag nothing of the above
+ * changes, and dense->rate and dense->reserved are not read: a caller built against the 16-byte acm_dense_opts stays correct.  With
+ * it, rate == 0 or reserved != 0 is ACMHIP_ERR_ARG before anything is written.  The flag combines with ACM_DENSE_PLANAR,
+ * ACM_DENSE_MIX and ACM_BATCH_PCM_F32.  For window k let Ri be the rate in its item's header, c_k the item's channel count after
+ * force_chans, g = gcd(Ri, Ro), L = Ro / g, M = Ri / g.
+ * As with ACM_DENSE_MIX a window's first_word and max_words count the item's OWN interleaved samples at its OWN rate; `whole`,
+ * `words` (SOURCE samples) and `status` are what acm_batch_decode_windows reports for the same window, which delivers
+ * f = words / c_k source frames.  The channel conversion comes first: x_ch[i], 0 <= i < f, is channel ch of source frame i AFTER the
+ * conversion the row's mode defines above - a copy or a split for a file of C channels, (L + R) >> 1 or duplication with
+ * ACM_DENSE_MIX; without ACM_DENSE_MIX a file of another channel count is turned away as ever.  (The down-mix floors, so the order
+ * matters.)  x_ch[i] = 0 for i < 0 and i >= f: a row is the resampled CROP, the stream's own neighbours of the window are not used,
+ * the windowed decode underneath is what it is without the flag and the kernel loads nothing but the row's own samples rounded out
+ * to 16 bytes.
+ * A row with Ri == Ro is exactly the row the call writes without the flag; it is not filtered.  A row of another rate has
+ * n_out = ceil(f * L / M) = (f * L + M - 1) / M frames; frame j < n_out of channel ch, in the layout [T][C] or, with
+ * ACM_DENSE_PLANAR, [C][T], is
+ *   n = j * M;  base = n / L;  ph = n % L                                   (integer division)
+ *   acc = sum over t in [0, K) of q[ph][t] * x_ch[base - Wd + 1 + t]        (32 bits; it cannot overflow, see the taps)
+ *   y   = clamp((acc + 8192) >> 14, -32768, 32767)                          (arithmetic shift; it saturates, where the decoder wraps)
+ * and the frames j >= n_out are zero.  float32 is y * 2^-15 exactly.  Every element of every row is written and nothing outside
+ * [0, nwin * R), as without the flag.
+ * The taps: Z = 8 zero crossings a side, a Hann-windowed sinc in Q14, computed on the host in double:
+ *   s  = min(1, L / M)                                  the cutoff as a fraction of the source's Nyquist rate
+ *   Wd = Z where L >= M, else (Z * M + L - 1) / L;      K = 2 * Wd
+ *   for ph in [0, L), t in [0, K):   a = (t - Wd + 1) * L - ph;  u = a / L;  v = u * s / Z
+ *       h[ph][t] = s * sinc(s * u) * (0.5 + 0.5 * cos(pi * v) where |v| < 1, else 0)        sinc(x) = sin(pi x) / (pi x), 1 at 0
+ *   h[ph] /= sum over t of h[ph][t]
+ *   q[ph][t] = nearbyint(h[ph][t] * 16384)                                 ties to even
+ *   q[ph][first index of the largest q[ph]] += 16384 - sum over t of q[ph][t]
+ * so every phase sums to 16384 exactly - a constant input comes out as it went in - and Ri == Ro has the single tap 16384, the
+ * identity: why a row of the batch's rate may skip the filter.  Every phase has sum |q[ph][t]| < 65536, so |acc| < 2^31; the library
+ * checks that of every table it designs.
+ * A ratio is supported when Ri > 0, M <= 8 * L and L * K <= 16384, a table of 32 KB at most: 22050 -> 16000 (L 320, K 24),
+ * 8000 -> 22050 (L 441, K 16), 48000 -> 11025 (L 147, K 70), 44100 <-> 48000.  A window whose item's ratio is not supported is
+ * turned away softly, as one of another channel count without ACM_DENSE_MIX is: words = 0, status = ACMHIP_ERR_ARG, a row of
+ * zeros, nothing of it parsed (timing->blocks_parsed shows it).  More than 16 distinct ratios among the resampled windows of one
+ * call: ACMHIP_ERR_ARG for the whole call.
+ * ACMHIP_ERR_ARG before anything is written where a window has first_word % c_k != 0, max_words % c_k != 0, or more frames than a
+ * row takes: ceil((max_words / c_k) * L / M) > T for a resampled window, max_words / c_k > T for any other - so the longest source
+ * window of a row is T * M / L frames.  Windows without a rate (not ACM, no such file, an unusable index), and those turned away
+ * for their ratio or channel count, are checked as rows of the batch's own rate and deliver zeros.  frames of 2^40 and more:
+ * ACMHIP_ERR_ARG.  dev_off = slot_off = k * R and slot_words = R as ever.
+ * Where no row of a call resamples - every file is at Ro, the others' windows deliver nothing, or the flag is unset - the call
+ * launches the kernel it launches without the flag, over the same row table, bit for bit.  Else one launch of acm_dense_resample
+ * (csrc/acm_dense_resample.hip) takes its place and writes the plain and the converting rows as well; its second table (32 bytes a
+ * row) and the ratios' taps travel behind the row table.
  * ---------------------------------------------------------------------- */
-#define ACM_DENSE_PLANAR 1u              /* row k is [channels][frames]; default [frames][channels] */
-#define ACM_DENSE_MIX    4u              /* windows of files with the other channel count are converted, not turned away */
+#define ACM_DENSE_PLANAR   1u            /* row k is [channels][frames]; default [frames][channels] */
+#define ACM_DENSE_MIX      4u            /* windows of files with the other channel count are converted, not turned away */
+#define ACM_DENSE_RESAMPLE 16u           /* windows of files with another sample rate than dense->rate are resampled to it */
 typedef struct acm_dense_opts {
 	uint64_t frames;                 /* T >= 1 */
 	uint32_t channels;               /* C: 1 or 2 (all an ACM header can say) */
 	uint32_t flags;                  /* ACM_DENSE_* */
+	uint32_t rate;                   /* Ro; read with ACM_DENSE_RESAMPLE only, and so is ... */
+	uint32_t reserved;               /* ... this: 0 */
 } acm_dense_opts;
+
+/* frames of a row resampled from source_frames frames: n_out above, source_frames itself for equal rates; UINT64_MAX for a ratio that
+ * is not supported (or 2^50 frames and more).  No device is needed */
+uint64_t acm_dense_resampled_frames(uint64_t source_frames, uint32_t rate_in, uint32_t rate_out);
+/* L, M, K, Wd (each may be NULL) and the Q14 table q[L][K] of a ratio into taps[cap] - what the kernel reads is this function's
+ * output, uploaded.  taps == NULL: the sizes alone.  ACMHIP_ERR_ARG for a ratio that is not supported, or cap < L * K.  No device is
+ * needed */
+int  acm_dense_resample_taps(uint32_t rate_in, uint32_t rate_out, uint32_t *L, uint32_t *M, uint32_t *K, uint32_t *Wd, int16_t *taps,
+			     size_t cap);
 
 int  acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 				    acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts,

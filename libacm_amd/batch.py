@@ -16,6 +16,7 @@ libacm_hip.so, device memory owned by torch); tests on CPU-only machines inject 
 sharding, scatter and gather are exercised with world_size > 1.
 """
 import heapq
+import math
 import os
 
 import numpy as np
@@ -121,6 +122,7 @@ class GpuDecoder:
         self.timing = None
         self.index_timing = None
         self._chans = None              # crop_batch(mix=True): (the index object, channels per file of the files it belongs to)
+        self._rates = None              # crop_batch(rate=...): (the index object, sample rate per file)
         torch.cuda.set_device(ordinal)
         # the library runs on a stream of its own (torch's current stream is usually the null stream, which
         # acmhip_device_open does not adopt); __call__ orders the two around the torch-owned PCM tensor
@@ -191,7 +193,16 @@ class GpuDecoder:
             kept = self._chans = (index, [found[f] if found.get(f) in (1, 2) else 0 for f in range(len(files))])
         return kept[1]
 
-    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False):
+    def _header_rates(self, files, index):
+        """[f]: the sample rate the header of files[f] says, None for a file without one; kept with the index object as the channel
+        counts are"""
+        kept = self._rates
+        if kept is None or kept[0] is not index or len(kept[1]) != len(files):
+            found = capi.header_rates(files)
+            kept = self._rates = (index, [found.get(f) for f in range(len(files))])
+        return kept[1]
+
+    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None):
         """Random-access crops as one batch tensor: windows = (file_no, first_frame, n_frames) triples with n_frames <= frames, index as
         for crop().  -> (batch, frames_delivered, statuses): batch is a tensor of this decoder's dtype shaped [N, channels, frames]
         (planar) or [N, frames, channels], row k the crop's frames with zeros behind them - also where a window is clipped by the end of
@@ -202,7 +213,11 @@ class GpuDecoder:
         mix=True (ACM_DENSE_MIX): mono and stereo files in one batch.  Windows are (file_no, first_frame, n_frames) for any file; a file
         with the other channel count is decoded and converted instead of turned away - stereo becomes (L + R) >> 1, a mono sample goes
         into both channels - and frames_delivered counts its frames.  The channel counts are read from the headers once per `index`
-        object and kept with it: pass the index of the files, and a new one with new files, as crop() needs anyway."""
+        object and kept with it: pass the index of the files, and a new one with new files, as crop() needs anyway.
+        rate (ACM_DENSE_RESAMPLE): the batch's sample rate.  Windows stay (file_no, first_frame, n_frames) in the file's own frames at
+        its own rate - source_frames() says how many fit a row; the row of a file at another rate is its crop resampled, zeros beyond
+        the crop's ends, and frames_delivered[k] counts the row's OUTPUT frames.  A file whose ratio to `rate` the filter does not take
+        is turned away (capi.ERR_ARG).  The rates are kept with the index object, beside the channel counts."""
         torch = self.torch
         files = [_load(f) for f in files]
         if index is None:
@@ -213,6 +228,8 @@ class GpuDecoder:
         if mix:
             own = self._header_channels(files, index)
             per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
+        if rate is not None:
+            rates = self._header_rates(files, index)
         shape = (n, channels, frames) if planar else (n, frames, channels)
         need = n * channels * frames
         if out is not None and out.dtype != self.dtype:
@@ -222,9 +239,19 @@ class GpuDecoder:
         torch.cuda.current_stream().synchronize()
         statuses, words, self.timing = capi.batch_decode_windows_dense(
             self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], d_pcm.data_ptr(), d_pcm.numel(),
-            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix)
+            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix, rate=rate)
         # the call returns with its stream drained: the batch is complete and visible to torch's streams
-        return d_pcm.reshape(-1)[:need].view(shape), [w // c for w, c in zip(words, per)], statuses
+        delivered = [w // c for w, c in zip(words, per)]
+        if rate is not None:        # a row that got frames is of a file with a rate the filter takes
+            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
+        return d_pcm.reshape(-1)[:need].view(shape), delivered, statuses
+
+
+def source_frames(frames, rate_in, rate_out):
+    """the longest window, in frames of a file at rate_in, whose crop fits a row of `frames` frames at rate_out
+    (crop_batch(rate=rate_out)): frames * M // L"""
+    g = math.gcd(rate_in, rate_out)
+    return frames * (rate_in // g) // (rate_out // g)
 
 
 def _trace(trace, *ev):

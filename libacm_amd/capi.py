@@ -136,11 +136,12 @@ class WindowTiming(C.Structure):
 
 
 class DenseOpts(C.Structure):
-    _fields_ = [("frames", C.c_uint64), ("channels", C.c_uint32), ("flags", C.c_uint32)]
+    _fields_ = [("frames", C.c_uint64), ("channels", C.c_uint32), ("flags", C.c_uint32), ("rate", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 DENSE_PLANAR = 1
 DENSE_MIX = 4                   # windows of files with the other channel count are converted (mono <-> stereo), not turned away
+DENSE_RESAMPLE = 16             # windows of files with another sample rate than DenseOpts.rate are resampled to it
 
 
 class BatchIndexOut(C.Structure):
@@ -170,6 +171,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
+    "acm_dense_resampled_frames", "acm_dense_resample_taps",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info",
 ]
@@ -267,6 +269,10 @@ def lib():
                                            C.POINTER(BatchOpts), C.POINTER(WindowTiming)]
     L.acm_batch_decode_windows_dense.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
                                                  C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(WindowTiming)]
+    if hasattr(L, "acm_dense_resampled_frames"):                   # (an older library named by ACM_HIP_LIB for an A/B run has none)
+        L.acm_dense_resampled_frames.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+        L.acm_dense_resampled_frames.restype = C.c_uint64
+        L.acm_dense_resample_taps.argtypes = [C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4 + [vp, sz]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -332,6 +338,15 @@ def probe(data, force_chans=0):
 def header_channels(files, which=None, force_chans=0):
     """{file number: channels the header of files[number] says} for the numbers in `which` (default: all) whose file is ACM - the
     probe of probe(); no file image is copied"""
+    return _header_field(files, which, force_chans, "channels")
+
+
+def header_rates(files, which=None, force_chans=0):
+    """header_channels' sibling: {file number: the sample rate the header of files[number] says}"""
+    return _header_field(files, which, force_chans, "rate")
+
+
+def _header_field(files, which, force_chans, field):
     probe_fn, info, out = lib().acm_stage_probe, StageInfo(), {}
     ref = C.byref(info)
     for f in range(len(files)) if which is None else which:
@@ -342,8 +357,27 @@ def header_channels(files, which=None, force_chans=0):
             a = _as_u8(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
             rc = probe_fn(a.ctypes.data, a.size, force_chans, ref)
         if rc == 0:
-            out[f] = info.channels
+            out[f] = getattr(info, field)
     return out
+
+
+def dense_resampled_frames(source_frames, rate_in, rate_out):
+    """acm_dense_resampled_frames: the frames of a row of ACM_DENSE_RESAMPLE made of source_frames frames, None for a ratio the dense
+    writer does not take"""
+    n = lib().acm_dense_resampled_frames(source_frames, rate_in, rate_out)
+    return None if n == 2 ** 64 - 1 else int(n)
+
+
+def dense_resample_taps(rate_in, rate_out):
+    """acm_dense_resample_taps -> (L, M, K, Wd, the Q14 table as an int16 array [L, K]); ValueError for a ratio that is not supported"""
+    n = [C.c_uint32() for _ in range(4)]
+    refs = [C.byref(v) for v in n]
+    if lib().acm_dense_resample_taps(rate_in, rate_out, *refs, None, 0) != 0:
+        raise ValueError("acm_dense_resample_taps: %d -> %d is not a supported ratio" % (rate_in, rate_out))
+    L, M, K, Wd = (int(v.value) for v in n)
+    taps = np.zeros((L, K), dtype=np.int16)
+    _check(lib().acm_dense_resample_taps(rate_in, rate_out, *refs, taps.ctypes.data, taps.size), "acm_dense_resample_taps")
+    return L, M, K, Wd, taps
 
 
 def stage_file(data, force_chans=0, idx_out=None, hdr_out=None):
@@ -1074,18 +1108,21 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
 
 def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                               check=True, mix=False):
+                               check=True, mix=False, rate=None):
     """acm_batch_decode_windows_dense: the windows as len(windows) rows of frames * channels samples in d_pcm (int16, or float32 with
     f32=True), row k at sample k * frames * channels - interleaved, or a plane per channel with planar=True - zeros behind what a window
     delivers.  mix=True (ACM_DENSE_MIX): a window of a file with the other channel count counts that file's own samples and its row is
-    converted - stereo averaged into mono, mono repeated in both channels.  Returns (statuses, words, WindowTiming).  check=False (tests
+    converted - stereo averaged into mono, mono repeated in both channels.  rate (ACM_DENSE_RESAMPLE): the batch's sample rate; a window
+    of a file at another rate counts that file's own samples and its row is resampled (dense_resampled_frames says to how many frames).
+    Returns (statuses, words, WindowTiming).  check=False (tests
     of the refusals): the return code instead of an exception, as a fourth element; dense_flags: the raw acm_dense_opts.flags instead of planar and mix; frames None: no acm_dense_opts at all; dev None: the call's
     own answer to a missing handle."""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
-    dense = None if frames is None else DenseOpts(frames, channels, ((DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0)) if dense_flags is None
-                                                      else dense_flags)
+    if dense_flags is None:
+        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0)
+    dense = None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
     tm = WindowTiming()
     _fill(dev)
     rc = lib().acm_batch_decode_windows_dense(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),

@@ -18,7 +18,9 @@
  * acm_batch_decode_windows_dense is the same run with another end: the windows are synthesised into the handle's own PCM arena, nothing
  * is read back, and one launch of acm_dense_rows (acm_dense.hip) lays them out as the rows of the caller's tensor.  What that call
  * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's - also whether, with ACM_DENSE_MIX, a row
- * of the table converts between mono and stereo: then the launch is acm_dense_mixed's (acm_dense_mix.hip) instead.
+ * of the table converts between mono and stereo: then the launch is acm_dense_mixed's (acm_dense_mix.hip) instead - and whether, with
+ * ACM_DENSE_RESAMPLE, a row is filtered to the batch's sample rate: then a second table and the ratios' taps travel with the first and
+ * the launch is acm_dense_resample's (acm_dense_resample.hip).
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -292,18 +294,28 @@ int WinRun::synthesise_and_gather()
 	collect(ps);
 	if (!ps.descs.empty())
 		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
-	const size_t at = dense->table_off(L), bytes = dense->table_bytes();
-	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX) */
-	const bool mixed = acm_dense_rows(*dense, L.slots.data(), wins, reinterpret_cast<AcmDenseRow *>(h_jobs + at));
+	const size_t at = dense->table_off(L);
+	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX) or is filtered (ACM_DENSE_RESAMPLE);
+	 * only a call that filters sends the second table and the taps */
+	AcmDenseRow *rows = reinterpret_cast<AcmDenseRow *>(h_jobs + at);
+	const bool mixed = acm_dense_rows(*dense, L.slots.data(), wins, rows);
+	const bool filters = !dense->tables.empty() &&
+			     acm_dense_resample_rows(*dense, rows, reinterpret_cast<AcmResampleRow *>(h_jobs + at + dense->resample_off()),
+						     reinterpret_cast<int16_t *>(h_jobs + at + dense->taps_off()));
+	const size_t bytes = filters ? dense->table_bytes() : dense->row_table_bytes();
 	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
 	tm.h2d_bytes += bytes;
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
-	const int e = (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, reinterpret_cast<const AcmDenseRow *>(d_jobs + at), L.slots.size(),
-										 dense_out, dense->frames, dense->channels, dense->planar, dense->f32, st);
+	const AcmDenseRow *d_rows = reinterpret_cast<const AcmDenseRow *>(d_jobs + at);
+	const int e = filters ? acmk_launch_dense_resample(d_pcm, d_rows, reinterpret_cast<const AcmResampleRow *>(d_jobs + at + dense->resample_off()),
+							   reinterpret_cast<const int16_t *>(d_jobs + at + dense->taps_off()), L.slots.size(), dense_out,
+							   dense->frames, dense->channels, dense->planar, dense->f32, st)
+			      : (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), dense_out, dense->frames,
+											   dense->channels, dense->planar, dense->f32, st);
 	if (e != 0)
-		return acmhip_report_hip(e, mixed ? "acmk_launch_dense_mixed" : "acmk_launch_dense_rows");
+		return acmhip_report_hip(e, filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed" : "acmk_launch_dense_rows");
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
 	ACM_HIP_TRY(hipStreamSynchronize(st));
 	float ms = 0;

@@ -1,6 +1,7 @@
 /*
  * acm_dense_layout.cpp - the device-free half of acm_batch_decode_windows_dense (acm_batch_windows.cpp): the call's validation, its
- * soft rejections, the output size and the gather kernel's row table.  No HIP call here.
+ * soft rejections, the output size and the gather kernel's row table - with ACM_DENSE_RESAMPLE also which windows are filtered by
+ * which ratio's table (acm_resample_layout.cpp) and the second row table that says so.  No HIP call here.
  */
 #include "acm_dense_layout.h"
 
@@ -11,8 +12,14 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 {
 	DenseLayout &D = *out;
 	D = DenseLayout();
-	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) || (dense->flags & ~(ACM_DENSE_PLANAR | ACM_DENSE_MIX)))
+	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) ||
+	    (dense->flags & ~(ACM_DENSE_PLANAR | ACM_DENSE_MIX | ACM_DENSE_RESAMPLE)))
 		return ACMHIP_ERR_ARG;
+	/* the two fields behind `flags` exist for a caller that sets the flag; the products of frames and a ratio stay far inside 64 bits */
+	D.resample = (dense->flags & ACM_DENSE_RESAMPLE) != 0;
+	if (D.resample && (dense->rate == 0 || dense->reserved != 0 || dense->frames >= (1ull << 40)))
+		return ACMHIP_ERR_ARG;
+	D.rate = D.resample ? dense->rate : 0;
 	/* padding has one meaning in the signed little-endian writer only; the staged forms of a prestaged or packed batch are not a window's */
 	if (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE || opts.parse > ACM_BATCH_PARSE_AUTO || opts.prestaged || (opts.flags & ACM_BATCH_STAGE_PACKED))
 		return ACMHIP_ERR_ARG;
@@ -41,11 +48,32 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 		const uint32_t c = items[w.item].info.channels;
 		return c != D.channels && (c == 1 || c == 2);
 	};
+	/* ... and with ACM_DENSE_RESAMPLE one at another rate than the batch's is filtered, or turned away where the ratio is none the
+	 * filter takes.  Only a window that is not turned away for its channel count is asked for its rate */
+	enum { SAME, FILTERED, BAD };
+	auto rate_kind = [&](const acm_batch_window &w, ResampleRatio *r) {
+		if (!D.resample || !has_chans(w) || (items[w.item].info.channels != D.channels && !converts(w)))
+			return (int)SAME;
+		const uint32_t ri = items[w.item].info.rate;
+		if (ri == D.rate)
+			return (int)SAME;
+		return acm_resample_ratio(ri, D.rate, r) ? (int)FILTERED : (int)BAD;
+	};
 	for (size_t k = 0; k < nwin; k++) {
 		/* whole frames, T of them at most - of the batch's channel count, or of the item's own where the window is converted */
 		const uint32_t c = converts(wins[k]) ? items[wins[k].item].info.channels : D.channels;
-		if (wins[k].max_words > D.frames * c || wins[k].first_word % c || wins[k].max_words % c)
-			return ACMHIP_ERR_ARG;
+		if (wins[k].max_words > D.frames * c || wins[k].first_word % c || wins[k].max_words % c) {
+			/* ... T frames of the batch's rate: a filtered window may be M / L times as long (8 times at most) */
+			ResampleRatio r;
+			if (wins[k].first_word % c || wins[k].max_words % c || rate_kind(wins[k], &r) != FILTERED)
+				return ACMHIP_ERR_ARG;
+			if (wins[k].max_words / c > ACM_RESAMPLE_MAX_DOWN * D.frames || acm_resample_frames(wins[k].max_words / c, r) > D.frames)
+				return ACMHIP_ERR_ARG;
+		} else if (D.resample) {
+			ResampleRatio r;
+			if (rate_kind(wins[k], &r) == FILTERED && acm_resample_frames(wins[k].max_words / c, r) > D.frames)
+				return ACMHIP_ERR_ARG;
+		}
 	}
 
 	D.wins.assign(wins, wins + nwin);
@@ -60,6 +88,39 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 		} else {
 			D.rejected[k] = 1;
 			D.wins[k].max_words = 0;
+		}
+	}
+	if (D.resample) {
+		D.bad_ratio.assign(nwin, 0);
+		std::vector<int8_t> ratio(nwin, -1);
+		std::vector<uint8_t> chans(nwin, (uint8_t)D.channels);
+		for (size_t k = 0; k < nwin; k++) {
+			const acm_batch_window &w = wins[k];
+			ResampleRatio r;
+			const int kind = rate_kind(w, &r);
+			if (kind == BAD) {
+				D.bad_ratio[k] = D.rejected[k] = 1;
+				D.wins[k].max_words = 0;
+			}
+			if (kind != FILTERED)
+				continue;
+			const uint32_t ri = items[w.item].info.rate;
+			size_t id = 0;
+			while (id < D.tables.size() && D.tables[id]->rate_in != ri)
+				id++;
+			if (id == D.tables.size()) {
+				if (id == ACM_RESAMPLE_MAX_RATIOS)
+					return ACMHIP_ERR_ARG;
+				D.tables.push_back(acm_resample_table(ri, D.rate));
+				if (!D.tables.back())
+					return ACMHIP_ERR_ARG;
+			}
+			ratio[k] = (int8_t)id;
+			chans[k] = (uint8_t)items[w.item].info.channels;
+		}
+		if (!D.tables.empty()) {
+			D.ratio.swap(ratio);
+			D.chans.swap(chans);
 		}
 	}
 	D.inner = opts;
@@ -87,6 +148,26 @@ bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_bat
 		converts |= mode != 0;
 	}
 	return converts;
+}
+
+bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmResampleRow *rs, int16_t *taps)
+{
+	bool filters = false;
+	for (size_t k = 0; k < D.wins.size(); k++) {
+		const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
+		rs[k] = AcmResampleRow{};
+		if (D.ratio[k] < 0 || !count)
+			continue;
+		const ResampleRatio &r = D.tables[D.ratio[k]]->r;
+		const uint64_t f = count / D.chans[k];
+		rs[k] = AcmResampleRow{ (uint32_t)D.tap_at(D.ratio[k]), r.L, r.M, r.Wd, acm_resample_frames(f, r), f };
+		filters = true;
+	}
+	for (size_t id = 0; id < D.tables.size(); id++) {
+		int16_t *at = taps + D.tap_at(id);
+		std::fill(std::copy(D.tables[id]->q.begin(), D.tables[id]->q.end(), at), at + D.tap_words(id), (int16_t)0);
+	}
+	return filters;
 }
 
 } // namespace acmbatch
@@ -140,6 +221,27 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 			std::vector<uint64_t> mix(D.mode.begin(), D.mode.end());
 			mix.push_back(converts);
 			visit(ctx, "mix", mix.data(), sizeof(uint64_t), mix.size());
+		}
+		if (D.resample) {
+			std::vector<AcmResampleRow> rs(nwin);
+			std::vector<int16_t> taps(D.tables.empty() ? 0 : D.tap_at(D.tables.size()));
+			const bool filters = !D.tables.empty() && acm_dense_resample_rows(D, rows.data(), rs.data(), taps.data());
+			std::vector<uint64_t> res, tabs;
+			for (size_t k = 0; k < nwin; k++) {
+				const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
+				const uint32_t c = (rows[k].count >> ACM_DENSE_MODE_SHIFT) ? 3 - D.channels : D.channels;
+				if (rs[k].L)
+					res.insert(res.end(), { (uint64_t)rs[k].L, (uint64_t)rs[k].M, (uint64_t)D.ratio[k], rs[k].n_out, 0 });
+				else
+					res.insert(res.end(), { (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, count / c, (uint64_t)D.bad_ratio[k] });
+			}
+			res.insert(res.end(), { (uint64_t)filters, 0, 0, 0, 0 });
+			for (size_t id = 0; id < D.tables.size(); id++) {
+				const ResampleTable &t = *D.tables[id];
+				tabs.insert(tabs.end(), { (uint64_t)t.rate_in, (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd, (uint64_t)D.tap_at(id) });
+			}
+			visit(ctx, "resample", res.data(), 5 * sizeof(uint64_t), nwin + 1);
+			visit(ctx, "tables", tabs.data(), 6 * sizeof(uint64_t), D.tables.size());
 		}
 	}
 	const uint64_t totals[] = { D.frames, D.row_words, D.channels, (uint64_t)D.planar, (uint64_t)D.f32, D.out_words, D.pcm_arena_words(L.pcm_total),

@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "acm_resample_layout.h"
 #include "acm_window_layout.h"
 
 namespace acmbatch {
@@ -28,11 +29,29 @@ struct DenseLayout {
 	std::vector<uint8_t> rejected;          /* [k]: window k's item has another channel count than the batch (no ACM_DENSE_MIX) */
 	bool mix = false;                       /* ACM_DENSE_MIX: such a window is decoded and converted instead */
 	std::vector<uint8_t> mode;              /* [k]: AcmDenseMode - what row k does with its window's samples, if it gets any */
+	bool resample = false;                  /* ACM_DENSE_RESAMPLE: a window of a file at another rate than `rate` is resampled */
+	uint32_t rate = 0;
+	std::vector<uint8_t> bad_ratio;         /* [k]: turned away for its item's rate (also counted in `rejected`) */
+	std::vector<int8_t> ratio;              /* [k]: which of `tables` row k is filtered by if it gets samples, or -1; empty without a table */
+	std::vector<uint8_t> chans;             /* [k]: samples per source frame of a row that is filtered */
+	std::vector<std::shared_ptr<const ResampleTable>> tables;      /* the distinct ratios of the call, in the order of their first window */
 	acm_batch_opts inner{};                 /* the options of the windowed decode underneath: int16 rows into the handle's own arena */
 	uint64_t pcm_arena_words(uint64_t pcm_total) const { return pcm_total + ACM_DENSE_PCM_SLACK; }
 	/* the row table travels behind the device parser's tables in the H_JOBS / D_JOBS arenas */
 	size_t table_off(const WindowLayout &L) const { return (size_t)round_up(L.job_arena_bytes(), 64); }
-	size_t table_bytes() const { return wins.size() * sizeof(AcmDenseRow); }
+	/* ... and, where a window may be resampled, the second table and the ratios' taps behind it, each from a multiple of 16 bytes on */
+	size_t row_table_bytes() const { return wins.size() * sizeof(AcmDenseRow); }
+	size_t resample_off() const { return row_table_bytes(); }
+	size_t taps_off() const { return resample_off() + wins.size() * sizeof(AcmResampleRow); }
+	size_t tap_words(size_t id) const { return (size_t)round_up(tables[id]->q.size(), 8); }
+	size_t tap_at(size_t id) const
+	{
+		size_t at = 0;
+		for (size_t i = 0; i < id; i++)
+			at += tap_words(i);
+		return at;
+	}
+	size_t table_bytes() const { return tables.empty() ? row_table_bytes() : taps_off() + tap_at(tables.size()) * sizeof(int16_t); }
 };
 
 /* ACMHIP_OK, or ACMHIP_ERR_ARG for a call the dense writer refuses as a whole (include/acm_hip.h) - then nothing of `out` is to be
@@ -48,6 +67,11 @@ void acm_dense_report(const DenseLayout &D, const WindowSlot &s, size_t k, acm_b
  * acm_dense.hip's */
 bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows);
 
+/* ACM_DENSE_RESAMPLE, for a layout with tables: the second table, from the first one (a row that got no samples is not filtered), and
+ * the taps behind it (tap_at(tables.size()) words).  Returns whether a row is filtered: then the three tables are
+ * acm_dense_resample.hip's to read, else the first alone is the kernel's that acm_dense_rows chose */
+bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmResampleRow *rs, int16_t *taps);
+
 } // namespace acmbatch
 
 extern "C" {
@@ -55,7 +79,10 @@ extern "C" {
  * null: what the window layout says) stands for what staging left of every window.  A refused call visits "totals" alone.  Tables,
  * as uint64 words: "wins" (3 per window: item, first_word, max_words as the window layout gets them), "rejected", "report" (5 per
  * window: status (sign-extended), words, dev_off, slot_off, slot_words as the caller receives them), "rows" (2 per window: src,
- * count), with ACM_DENSE_MIX alone "mix" (nwin + 1 words: AcmDenseMode per window, then 1 if a row converts, else 0), "totals":
+ * count), with ACM_DENSE_MIX alone "mix" (nwin + 1 words: AcmDenseMode per window, then 1 if a row converts, else 0), with
+ * ACM_DENSE_RESAMPLE alone "resample" (5 per window: L, M, the ratio's number in "tables" or all ones, the row's frames, 1 if the window
+ * is turned away for its rate; L = M = 1 for a row that is not filtered, 0 for one turned away; nwin + 1 entries, the last one's first
+ * word 1 if a row is filtered) and "tables" (6 per distinct ratio: rate_in, L, M, K, Wd, where its taps begin behind the tables), "totals":
  * frames, row_words, channels, planar, f32, out_words, pcm_arena_words, blocks_parsed, table_off, table_bytes and the return code */
 int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status, const uint64_t *whole,
 			    const acm_block_mark *const *marks, const uint32_t *blocks, size_t n, const uint64_t *win3, size_t nwin,

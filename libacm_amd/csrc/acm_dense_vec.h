@@ -1,7 +1,7 @@
 /*
- * acm_dense_vec.h - what the dense writers' kernels (acm_dense.hip, acm_dense_mix.hip) share: the geometry of a unit, the aligned
- * 16-byte line loads funnelled by a wavefront-uniform shift, and the whole-line stores of int16 and float32 vectors.  Device code;
- * included by those two files only.
+ * acm_dense_vec.h - what the dense writers' kernels (acm_dense.hip, acm_dense_mix.hip, acm_dense_resample.hip) share: the geometry of
+ * a unit, the aligned 16-byte line loads funnelled by a wavefront-uniform shift, and the whole-line stores of int16 and float32
+ * vectors.  Device code; included by those three files only.
  */
 #ifndef ACM_DENSE_VEC_H
 #define ACM_DENSE_VEC_H

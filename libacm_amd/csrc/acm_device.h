@@ -117,6 +117,14 @@ enum AcmDenseMode {
 };
 #define ACM_DENSE_MODE_SHIFT 56
 #define ACM_DENSE_COUNT_MASK ((1ull << ACM_DENSE_MODE_SHIFT) - 1)
+/* ACM_DENSE_RESAMPLE (acm_dense_resample.hip): a second table beside the first, one record per row.  L == 0: the row is written as
+ * its AcmDenseRow says.  Else that record names the row's SOURCE samples and its channel conversion as ever, and the row is the
+ * `frames_in` frames they make, filtered into n_out frames by the ratio's Q14 table: L phases of 2 * Wd taps from int16 `tab` of the
+ * tap arena on (a multiple of 8) */
+struct AcmResampleRow {
+	uint32_t tab, L, M, Wd;
+	uint64_t n_out, frames_in;
+};
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -174,7 +182,7 @@ void acmhip_set_error_text(const char *text);                    /* what acmhip_
 /* Two kinds of acmk_* functions.  The ones that launch nothing - a build's tile rows, threads, grid, first-pass depth, lead-in, packed
  * slots, the split of a chunk table, what the device parser accepts and where it cuts - live in acm_kernel_geo.cpp: plain C++ over the
  * tables of acm_kernel_geo.h, linkable without a device or a kernel.  The launchers (acmk_launch_*, acmk_warmup) live with their kernels in
- * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip, acm_dense.hip and acm_dense_mix.hip, and take block size and
+ * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip, acm_dense.hip, acm_dense_mix.hip and acm_dense_resample.hip, and take block size and
  * grid from the queries.  `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
  * d_pcm (and d_sink) then hold floats and the streams' pcm_off / n_emit count them (acmhip_plan_launch_f32) */
 #define ACMK_FMT_F32 0x100u
@@ -315,6 +323,11 @@ int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint
  * inside its slot too */
 int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
 			    int planar, int f32, void *stream);
+/* acm_dense_resample.hip: the same launch for a call in which some row is resampled (d_rs[k].L != 0): such a row is filtered from its
+ * source samples after their channel conversion; the others are written as acmk_launch_dense_mixed writes them.  d_taps: the tap
+ * tables of the call's ratios, 16-byte aligned.  The same demands on d_src and d_out */
+int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps, uint64_t nrows,
+			       void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,14 @@ runs out of time ends the probe.
   of one channel count) side by side.  --parent-lib <the parent commit's libacm_hip.so>: per shape also the batch of one channel count -
   the call that must cost what it cost - on that library and, without and with the flag alternating, on this tree's.
 
-    python profiles/dense_crop_probe.py [--mix] [--windows 1024,16384] [--out probe_out/dense_crop.json]
+  --rates (profiles/dense_resample_notes.txt): the default workload's streams, a third each at 11025, 22050 and 44100 Hz; one-second
+  crops of every file (its own rate in frames) as a float32 [N, 1, 22050] batch.
+    rates:<n>:1  crop_batch(rate=22050): acm_dense_resample filters two rows in three
+    rates:<n>:0  the call without the flag over the same windows clipped to 22050 frames - a row cannot hold more - on this tree and,
+                 with --parent-lib, on the parent commit's library in a process of its own
+  With --step kernel --rates the trace holds acm_dense_resample's own durations.
+
+    python profiles/dense_crop_probe.py [--mix | --rates] [--windows 1024,16384] [--out probe_out/dense_crop.json]
 """
 import argparse
 import ctypes as C
@@ -244,6 +251,58 @@ def step_flag(args, n, f32, ch):
     return {name: stats(t) for name, t in times.items()}
 
 
+RATES = (11025, 22050, 44100)
+
+
+def rate_files(args):
+    """the default workload's streams, a third each at 11025, 22050 and 44100 Hz (file i: RATES[i % 3]), mono"""
+    from concurrent.futures import ThreadPoolExecutor
+    from libacm_amd import synth, workload
+    with ThreadPoolExecutor(max_workers=min(16, workload.usable_cpus())) as ex:
+        return list(ex.map(lambda i: synth.generate(seed=synth.BASE_SEED + i, level=args.level, rows=args.rows, nblocks=args.blocks,
+                                                    rate=RATES[i % 3]), range(args.streams)))
+
+
+def rate_windows(args, n, clip):
+    """one-second crops: (file, first_frame, the file's rate in frames) at seeded positions; clip: FRAMES frames at most, what a call
+    without ACM_DENSE_RESAMPLE takes of them"""
+    import numpy as np
+    rng = np.random.default_rng(22052)
+    total = args.blocks * args.rows << args.level
+    wins = []
+    for k in range(n):
+        f = k % args.streams
+        sec = RATES[f % 3]
+        wins.append((f, int(rng.integers(0, total - sec)), min(sec, FRAMES) if clip else sec))
+    return wins
+
+
+def step_rates(args, n, resample):
+    """float32 [N, 1, FRAMES] over rate_files: crop_batch(rate=FRAMES) with resample, else the plain call over the clipped windows (on
+    whichever library ACM_HIP_LIB names: the parent commit's knows no other).  Wall clock of the call plus synchronize, and the call's own
+    event time (synthesis + the gather launch)"""
+    import torch
+    from libacm_amd import batch, capi
+    files = rate_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    wins = rate_windows(args, n, clip=not resample)
+    buf = torch.empty(n * FRAMES, dtype=dec.dtype, device="cuda:0")
+    wall, k_ms = [], []
+    for r in range(args.warmup + args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        b, frames, st = dec.crop_batch(files, wins, FRAMES, channels=1, planar=True, index=index, out=buf, rate=FRAMES if resample else None)
+        torch.cuda.synchronize()
+        if r >= args.warmup:
+            wall.append(time.perf_counter() - t0)
+            k_ms.append(dec.timing.kernel_s)
+    dec.dev.close()
+    return dict(library=os.environ.get("ACM_HIP_LIB", "shipped"), call_wall=stats(wall), synthesis_plus_gather_events=stats(k_ms),
+                source_frames=int(sum(w[2] for w in wins)), frames_delivered=int(sum(frames)), ok=all(s == 0 for s in st),
+                samples_synthesised=int(dec.timing.samples), blocks_parsed=int(dec.timing.blocks_parsed))
+
+
 def step_kernel_mix(args):
     """REPS calls per shape of the mixed batch (acm_dense_mixed) and of a batch over the files of one channel count (acm_dense_rows): the
     launch's own durations are the trace's; the call's wall clock and event time are printed here"""
@@ -324,14 +383,21 @@ def main():
     ap.add_argument("--step-seconds", type=int, default=280, help="time limit of each GPU step")
     ap.add_argument("--out", default=os.path.join(ROOT, "probe_out", "dense_crop.json"))
     ap.add_argument("--mix", action="store_true", help="mono and stereo streams in one batch: crop_batch(mix=True) against two calls + torch")
+    ap.add_argument("--rates", action="store_true", help="files at 11025, 22050 and 44100 Hz in one 22050 Hz batch: crop_batch(rate=22050), and "
+                    "the plain call over the same windows clipped to a row (with --parent-lib also on the parent commit's library)")
     ap.add_argument("--parent-lib", help="with --mix: the parent commit's libacm_hip.so; adds, per shape, a batch of one channel count on that "
                     "library and on this tree's without and with the flag (each library a child process of its own)")
     ap.add_argument("--step", help="(internal) compare:<windows>:<f32 0|1>, mix:<windows>:<f32>:<channels>, or kernel: run one step in this "
                     "process and print its JSON")
     args = ap.parse_args()
     if args.step:
-        if args.step == "kernel":
+        if args.step == "kernel" and args.rates:
+            res = {"%d_windows" % n: step_rates(args, n, True) for n in args.windows}
+        elif args.step == "kernel":
             res = step_kernel_mix(args) if args.mix else step_kernel(args)
+        elif args.step.startswith("rates:"):
+            _, n, resample = args.step.split(":")
+            res = step_rates(args, int(n), resample == "1")
         elif args.step.startswith("flag:"):
             _, n, f32, ch = args.step.split(":")
             res = step_flag(args, int(n), f32 == "1", int(ch))
@@ -347,14 +413,18 @@ def main():
     steps = ["compare:%d:%d" % (n, f32) for n in args.windows for f32 in (1, 0)]
     if args.mix:
         steps = ["mix:%d:%d:%d" % (n, f32, ch) for n in args.windows for f32 in (1, 0) for ch in (1, 2)]
+    if args.rates:
+        steps = ["rates:%d:%d:tree" % (n, r) for n in args.windows for r in (1, 0)]
+        steps += ["rates:%d:0:parent" % n for n in args.windows if args.parent_lib]
     if args.mix and args.parent_lib:
         steps += ["flag:%d:%d:%d:%s" % (n, f32, ch, lib) for n in args.windows for f32 in (1, 0) for ch in (1, 2) for lib in ("parent", "tree")]
     for step in steps:
         env = dict(os.environ)
         if step.endswith(":parent"):
             env["ACM_HIP_LIB"] = os.path.abspath(args.parent_lib)
-        key, step = step, step.rsplit(":", 1)[0] if step.startswith("flag:") else step
+        key, step = step, step.rsplit(":", 1)[0] if step.startswith(("flag:", "rates:")) else step
         cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--host-index-max", str(args.host_index_max)] + ["--mix"] * args.mix + \
+              ["--rates"] * args.rates + \
               [a for k in ("streams", "level", "rows", "blocks", "warmup", "reps") for a in ("--" + k, str(getattr(args, k)))]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.step_seconds, env=env)
@@ -366,7 +436,7 @@ def main():
             print("step %s failed (%d): nothing more is started\n%s" % (step, r.returncode, r.stdout[-3000:]))
             return 1
         got = json.loads(line[-1][7:])
-        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else got)
+        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else {key: got} if key.startswith("rates:") else got)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
