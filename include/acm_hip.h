@@ -593,7 +593,7 @@ typedef struct acm_batch_index {         /* one per item */
 
 typedef struct acm_batch_window {
 	uint32_t item;           /* in:  which items[] entry */
-	uint32_t reserved;
+	uint32_t reserved;       /* in:  read by acm_batch_decode_windows_dense with ACM_DENSE_SPEED alone: the window's speed */
 	uint64_t first_word;     /* in:  first interleaved 16-bit sample wanted */
 	uint64_t max_words;      /* in */
 	int16_t *pcm;            /* in:  host output for min(words, pcm_cap) samples (ignored with opts->d_pcm; may be NULL) */
@@ -722,10 +722,52 @@ int  acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, s
  * launches the kernel it launches without the flag, over the same row table, bit for bit.  Else one launch of acm_dense_resample
  * (csrc/acm_dense_resample.hip) takes its place and writes the plain and the converting rows as well; its second table (32 bytes a
  * row) and the ratios' taps travel behind the row table.
+ *
+ * ACM_DENSE_SPEED: a speed factor per window (speed perturbation), and any rate ratio.  It requires ACM_DENSE_RESAMPLE - alone it is
+ * ACMHIP_ERR_ARG before anything is written - and combines with ACM_DENSE_PLANAR, ACM_DENSE_MIX and ACM_BATCH_PCM_F32.  Without the
+ * flag nothing of the above changes: wins[k].reserved is not read and a ratio beyond the exact table is turned away.  With it, frames
+ * of 2^28 and more are ACMHIP_ERR_ARG, and wins[k].reserved is the window's speed num << 16 | den, meaning num / den: 0 is 1 / 1,
+ * exactly one half 0 is ACMHIP_ERR_ARG for the whole call.  num / den > 1 plays faster and gives fewer frames.  With Ri, Ro and c_k as
+ * above, in 64 bits,
+ *   g = gcd(Ri * num, Ro * den);  L = Ro * den / g;  M = Ri * num / g
+ * take the place of the rates' L and M.  first_word and max_words still count the item's own samples, words and status are still
+ * acm_batch_decode_windows', the channel conversion still comes first, samples outside the crop are zero, n_out = ceil(f * L / M),
+ * and a window with n_out(max_words / c_k) > T - by its own L and M, computed without overflow - is ACMHIP_ERR_ARG for the whole
+ * call.  With Wd and K of (L, M) as above, a row gets
+ *   L == M                                   no filter: the row the call writes without the flags
+ *   M <= 8 L and L * K <= 16384              the EXACT filter above, with the table of that (L, M), bit for bit: a table is a function
+ *                                            of (L, M), so speed 9 / 10 at equal rates (L 10, M 9) is such a row
+ *   M <= 8 L, L and M below 2^31, otherwise  the WIDE filter below
+ *   anything else                            turned away softly: words = 0, ACMHIP_ERR_ARG, a row of zeros, nothing parsed
+ * The wide filter has a table whose size does not depend on L: P + 1 prototype phases of the same windowed sinc, between two of which
+ * the output is interpolated linearly, at a read position stepped in 32.32 fixed point.
+ *   c  = 64 where L >= M, else floor(64 * L / M)       8 .. 63: the cutoff, quantised DOWN to 64ths of the source Nyquist;  s = c / 64
+ *   Wd = Z where c == 64, else ceil(64 * Z / c);  K = 2 * Wd                                                    (16 .. 128)
+ *   P  = the largest power of two with (P + 1) * K <= 16384;  b = log2 P       (K 16, 18: 512;  K 46: 256;  K 128: 64)
+ *   for p in [0, P], t in [0, K):   u = (t - Wd + 1) - p / P;  v = u * s / Z
+ *       h[p][t] = s * sinc(s * u) * (0.5 + 0.5 * cos(pi * v) where |v| < 1, else 0)
+ *   h[p] /= sum over t of h[p][t];  q[p][t] = nearbyint(16384 * h[p][t]);  q[p][first index of the largest] += 16384 - sum over t of q[p][t]
+ * The table depends on c alone - 57 tables at most, one for all upsampling ratios - and every phase has sum |q| < 65536 (33 588 at
+ * most over the 57; the library checks every table it designs).  Output frame j < n_out of a channel is
+ *   step = floor(M * 2^32 / L)                                      (below 2^36)
+ *   X = j * step (64 bits unsigned; j < 2^28);  base = X >> 32;  frac = X & 0xFFFFFFFF
+ *   p = frac >> (32 - b);  w = (frac >> (17 - b)) & 32767
+ *   a0 = sum over t of q[p][t]     * x[base - Wd + 1 + t]
+ *   a1 = sum over t of q[p + 1][t] * x[base - Wd + 1 + t]           (32-bit sums each)
+ *   acc = a0 + (((a1 - a0) * w) >> 15)                              (in 64 bits; the shift arithmetic - the floor)
+ *   y = clamp((acc + 8192) >> 14, -32768, 32767);  float32 = y * 2^-15
+ * and the frames j >= n_out are zero.  step is rounded down, so the read position never runs ahead of the exact one j * M / L; it
+ * falls behind by less than j * 2^-32 source frames: after 2^24 output frames by at most 2^-8 of one.
+ * At most 16 distinct tables a call, exact (L, M) tables and wide c tables counted together; more is ACMHIP_ERR_ARG for the whole
+ * call.  Windows without a rate, or turned away, are checked as rows of the batch's own rate at speed 1 and deliver zeros.
+ * Where no row of a call is wide the call launches exactly what it launches without the flag, over the same tables.  Else one launch
+ * of acm_dense_speed (csrc/acm_dense_speed.hip) takes its place and writes the exact-filtered, the converting and the plain rows as
+ * well; its second table has 48 bytes a row.
  * ---------------------------------------------------------------------- */
 #define ACM_DENSE_PLANAR   1u            /* row k is [channels][frames]; default [frames][channels] */
 #define ACM_DENSE_MIX      4u            /* windows of files with the other channel count are converted, not turned away */
 #define ACM_DENSE_RESAMPLE 16u           /* windows of files with another sample rate than dense->rate are resampled to it */
+#define ACM_DENSE_SPEED    32u           /* wins[k].reserved is window k's speed; ratios beyond the exact table take the wide filter */
 typedef struct acm_dense_opts {
 	uint64_t frames;                 /* T >= 1 */
 	uint32_t channels;               /* C: 1 or 2 (all an ACM header can say) */
@@ -742,6 +784,21 @@ uint64_t acm_dense_resampled_frames(uint64_t source_frames, uint32_t rate_in, ui
  * needed */
 int  acm_dense_resample_taps(uint32_t rate_in, uint32_t rate_out, uint32_t *L, uint32_t *M, uint32_t *K, uint32_t *Wd, int16_t *taps,
 			     size_t cap);
+
+/* ACM_DENSE_SPEED's counterparts: a window of a file at rate_in played at num / den (both 1 .. 65535) into a batch at rate_out.  The
+ * frames of its row - source_frames itself where L == M; UINT64_MAX where the window would be turned away (or 2^50 frames and more) */
+uint64_t acm_dense_speed_frames(uint64_t source_frames, uint32_t rate_in, uint32_t rate_out, uint32_t num, uint32_t den);
+typedef struct acm_dense_speed_info {
+	uint32_t kind;                   /* 0: not filtered (L == M; L = M = 1 and the table is the identity's 16 taps), 1: exact, 2: wide */
+	uint32_t L, M, K, Wd;
+	uint32_t P, c;                   /* wide alone, else 0 */
+	uint32_t phases;                 /* of the table: L, or P + 1 */
+	uint64_t step;                   /* wide alone, else 0 */
+} acm_dense_speed_info;
+/* which filter the row gets (info may be NULL) and the table q[phases][K] the kernel reads into taps[cap]; taps == NULL: info alone.
+ * ACMHIP_ERR_ARG where the window would be turned away, or cap < phases * K.  No device is needed */
+int  acm_dense_speed_taps(uint32_t rate_in, uint32_t rate_out, uint32_t num, uint32_t den, acm_dense_speed_info *info, int16_t *taps,
+			  size_t cap);
 
 int  acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 				    acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts,

@@ -16,7 +16,6 @@ libacm_hip.so, device memory owned by torch); tests on CPU-only machines inject 
 sharding, scatter and gather are exercised with world_size > 1.
 """
 import heapq
-import math
 import os
 
 import numpy as np
@@ -202,7 +201,7 @@ class GpuDecoder:
             kept = self._rates = (index, [found.get(f) for f in range(len(files))])
         return kept[1]
 
-    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None):
+    def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None):
         """Random-access crops as one batch tensor: windows = (file_no, first_frame, n_frames) triples with n_frames <= frames, index as
         for crop().  -> (batch, frames_delivered, statuses): batch is a tensor of this decoder's dtype shaped [N, channels, frames]
         (planar) or [N, frames, channels], row k the crop's frames with zeros behind them - also where a window is clipped by the end of
@@ -217,7 +216,10 @@ class GpuDecoder:
         rate (ACM_DENSE_RESAMPLE): the batch's sample rate.  Windows stay (file_no, first_frame, n_frames) in the file's own frames at
         its own rate - source_frames() says how many fit a row; the row of a file at another rate is its crop resampled, zeros beyond
         the crop's ends, and frames_delivered[k] counts the row's OUTPUT frames.  A file whose ratio to `rate` the filter does not take
-        is turned away (capi.ERR_ARG).  The rates are kept with the index object, beside the channel counts."""
+        is turned away (capi.ERR_ARG).  The rates are kept with the index object, beside the channel counts.
+        speed (ACM_DENSE_SPEED, with rate): a (num, den) pair per window, or None for 1/1 - window k is played at num / den (11/10:
+        faster, fewer frames), which is a resampling of its own; any ratio down to an eighth is taken, the odd ones by a filter that
+        interpolates between prototype phases.  source_frames(..., speed=) says how long a window fits a row."""
         torch = self.torch
         files = [_load(f) for f in files]
         if index is None:
@@ -228,6 +230,8 @@ class GpuDecoder:
         if mix:
             own = self._header_channels(files, index)
             per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
+        if speed is not None and rate is None:
+            raise ValueError("GpuDecoder.crop_batch: speed needs rate")
         if rate is not None:
             rates = self._header_rates(files, index)
         shape = (n, channels, frames) if planar else (n, frames, channels)
@@ -239,19 +243,27 @@ class GpuDecoder:
         torch.cuda.current_stream().synchronize()
         statuses, words, self.timing = capi.batch_decode_windows_dense(
             self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], d_pcm.data_ptr(), d_pcm.numel(),
-            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix, rate=rate)
+            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed)
         # the call returns with its stream drained: the batch is complete and visible to torch's streams
         delivered = [w // c for w, c in zip(words, per)]
-        if rate is not None:        # a row that got frames is of a file with a rate the filter takes
+        if speed is not None:
+            # (a batch has a handful of distinct (frames, rate, speed): each is asked of the library once)
+            known = {}
+            for k, (d, w, sp) in enumerate(zip(delivered, windows, speed)):
+                key = (d, rates[w[0]], sp)
+                if d and key not in known:
+                    known[key] = capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1))
+                delivered[k] = known[key] if d else 0
+        elif rate is not None:      # a row that got frames is of a file with a rate the filter takes
             delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
         return d_pcm.reshape(-1)[:need].view(shape), delivered, statuses
 
 
-def source_frames(frames, rate_in, rate_out):
-    """the longest window, in frames of a file at rate_in, whose crop fits a row of `frames` frames at rate_out
-    (crop_batch(rate=rate_out)): frames * M // L"""
-    g = math.gcd(rate_in, rate_out)
-    return frames * (rate_in // g) // (rate_out // g)
+def source_frames(frames, rate_in, rate_out, speed=(1, 1)):
+    """the longest window, in frames of a file at rate_in played at speed = (num, den), whose crop fits a row of `frames` frames at
+    rate_out (crop_batch(rate=rate_out, speed=...)): frames * M // L"""
+    M, L = rate_in * speed[0], rate_out * speed[1]
+    return frames * M // L
 
 
 def _trace(trace, *ev):

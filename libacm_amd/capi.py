@@ -142,6 +142,15 @@ class DenseOpts(C.Structure):
 DENSE_PLANAR = 1
 DENSE_MIX = 4                   # windows of files with the other channel count are converted (mono <-> stereo), not turned away
 DENSE_RESAMPLE = 16             # windows of files with another sample rate than DenseOpts.rate are resampled to it
+DENSE_SPEED = 32                # BatchWindow.reserved is the window's speed num << 16 | den; ratios beyond the exact table take the wide filter
+
+
+class DenseSpeedInfo(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("L", C.c_uint32), ("M", C.c_uint32), ("K", C.c_uint32), ("Wd", C.c_uint32), ("P", C.c_uint32),
+                ("c", C.c_uint32), ("phases", C.c_uint32), ("step", C.c_uint64)]
+
+
+SPEED_KINDS = ("none", "exact", "wide")
 
 
 class BatchIndexOut(C.Structure):
@@ -171,7 +180,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_mform_tile_rows", "acmhip_mform_group", "acmhip_mform_bytes", "acmhip_mform_pairs", "acmhip_mform_rows", "acmhip_mform_unrows", "acmhip_plan_bind_mform",
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
-    "acm_dense_resampled_frames", "acm_dense_resample_taps",
+    "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info",
 ]
@@ -273,6 +282,10 @@ def lib():
         L.acm_dense_resampled_frames.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.acm_dense_resampled_frames.restype = C.c_uint64
         L.acm_dense_resample_taps.argtypes = [C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4 + [vp, sz]
+    if hasattr(L, "acm_dense_speed_frames"):
+        L.acm_dense_speed_frames.argtypes = [C.c_uint64] + [C.c_uint32] * 4
+        L.acm_dense_speed_frames.restype = C.c_uint64
+        L.acm_dense_speed_taps.argtypes = [C.c_uint32] * 4 + [C.POINTER(DenseSpeedInfo), vp, sz]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -378,6 +391,24 @@ def dense_resample_taps(rate_in, rate_out):
     taps = np.zeros((L, K), dtype=np.int16)
     _check(lib().acm_dense_resample_taps(rate_in, rate_out, *refs, taps.ctypes.data, taps.size), "acm_dense_resample_taps")
     return L, M, K, Wd, taps
+
+
+def dense_speed_frames(source_frames, rate_in, rate_out, speed=(1, 1)):
+    """acm_dense_speed_frames: the frames of a row of ACM_DENSE_SPEED made of source_frames frames of a file at rate_in played at
+    speed = (num, den), None where the window would be turned away"""
+    n = lib().acm_dense_speed_frames(source_frames, rate_in, rate_out, speed[0], speed[1])
+    return None if n == 2 ** 64 - 1 else int(n)
+
+
+def dense_speed_taps(rate_in, rate_out, speed=(1, 1)):
+    """acm_dense_speed_taps -> (DenseSpeedInfo, the Q14 table the kernel reads as an int16 array [phases, K]); info.kind indexes
+    SPEED_KINDS.  ValueError where the window would be turned away"""
+    info = DenseSpeedInfo()
+    if lib().acm_dense_speed_taps(rate_in, rate_out, speed[0], speed[1], C.byref(info), None, 0) != 0:
+        raise ValueError("acm_dense_speed_taps: %d -> %d at %d/%d is turned away" % (rate_in, rate_out, speed[0], speed[1]))
+    taps = np.zeros((info.phases, info.K), dtype=np.int16)
+    _check(lib().acm_dense_speed_taps(rate_in, rate_out, speed[0], speed[1], None, taps.ctypes.data, taps.size), "acm_dense_speed_taps")
+    return info, taps
 
 
 def stage_file(data, force_chans=0, idx_out=None, hdr_out=None):
@@ -1108,12 +1139,14 @@ def batch_decode_windows_device(dev, files, index, windows, d_pcm, d_pcm_words, 
 
 def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                               check=True, mix=False, rate=None):
+                               check=True, mix=False, rate=None, speeds=None):
     """acm_batch_decode_windows_dense: the windows as len(windows) rows of frames * channels samples in d_pcm (int16, or float32 with
     f32=True), row k at sample k * frames * channels - interleaved, or a plane per channel with planar=True - zeros behind what a window
     delivers.  mix=True (ACM_DENSE_MIX): a window of a file with the other channel count counts that file's own samples and its row is
     converted - stereo averaged into mono, mono repeated in both channels.  rate (ACM_DENSE_RESAMPLE): the batch's sample rate; a window
     of a file at another rate counts that file's own samples and its row is resampled (dense_resampled_frames says to how many frames).
+    speeds (ACM_DENSE_SPEED, with rate): (num, den) per window, or None for 1/1 - window k is played at num / den, and a ratio the exact
+    filter does not take gets the wide one (dense_speed_frames).
     Returns (statuses, words, WindowTiming).  check=False (tests
     of the refusals): the return code instead of an exception, as a fourth element; dense_flags: the raw acm_dense_opts.flags instead of planar and mix; frames None: no acm_dense_opts at all; dev None: the call's
     own answer to a missing handle."""
@@ -1121,7 +1154,11 @@ def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, f
     nw = len(windows)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
     if dense_flags is None:
-        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0)
+        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
+            (DENSE_SPEED if speeds is not None else 0)
+    for k, sp in enumerate(speeds or ()):
+        if sp is not None:
+            wins[k].reserved = sp[0] << 16 | sp[1]
     dense = None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
     tm = WindowTiming()
     _fill(dev)

@@ -295,13 +295,16 @@ int WinRun::synthesise_and_gather()
 	if (!ps.descs.empty())
 		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
 	const size_t at = dense->table_off(L);
-	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX) or is filtered (ACM_DENSE_RESAMPLE);
-	 * only a call that filters sends the second table and the taps */
+	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX), is filtered (ACM_DENSE_RESAMPLE) or
+	 * takes the wide filter (ACM_DENSE_SPEED); only a call that filters sends the second table and the taps */
 	AcmDenseRow *rows = reinterpret_cast<AcmDenseRow *>(h_jobs + at);
 	const bool mixed = acm_dense_rows(*dense, L.slots.data(), wins, rows);
-	const bool filters = !dense->tables.empty() &&
-			     acm_dense_resample_rows(*dense, rows, reinterpret_cast<AcmResampleRow *>(h_jobs + at + dense->resample_off()),
-						     reinterpret_cast<int16_t *>(h_jobs + at + dense->taps_off()));
+	void *second = h_jobs + at + dense->resample_off();
+	int16_t *taps = reinterpret_cast<int16_t *>(h_jobs + at + dense->taps_off());
+	const bool wide = !dense->tables.empty() && acm_dense_wide_rows(*dense, rows);
+	if (wide)
+		acm_dense_speed_rows(*dense, rows, static_cast<AcmSpeedRow *>(second), taps);
+	const bool filters = wide || (!dense->tables.empty() && acm_dense_resample_rows(*dense, rows, static_cast<AcmResampleRow *>(second), taps));
 	const size_t bytes = filters ? dense->table_bytes() : dense->row_table_bytes();
 	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
 	tm.h2d_bytes += bytes;
@@ -309,13 +312,17 @@ int WinRun::synthesise_and_gather()
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
 	const AcmDenseRow *d_rows = reinterpret_cast<const AcmDenseRow *>(d_jobs + at);
-	const int e = filters ? acmk_launch_dense_resample(d_pcm, d_rows, reinterpret_cast<const AcmResampleRow *>(d_jobs + at + dense->resample_off()),
-							   reinterpret_cast<const int16_t *>(d_jobs + at + dense->taps_off()), L.slots.size(), dense_out,
-							   dense->frames, dense->channels, dense->planar, dense->f32, st)
-			      : (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), dense_out, dense->frames,
-											   dense->channels, dense->planar, dense->f32, st);
+	const void *d_second = d_jobs + at + dense->resample_off();
+	const int16_t *d_taps = reinterpret_cast<const int16_t *>(d_jobs + at + dense->taps_off());
+	const int e = wide ? acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), dense_out,
+						     dense->frames, dense->channels, dense->planar, dense->f32, st)
+		      : filters ? acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), dense_out,
+							     dense->frames, dense->channels, dense->planar, dense->f32, st)
+				: (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), dense_out, dense->frames,
+											     dense->channels, dense->planar, dense->f32, st);
 	if (e != 0)
-		return acmhip_report_hip(e, filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed" : "acmk_launch_dense_rows");
+		return acmhip_report_hip(e, wide ? "acmk_launch_dense_speed" : filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed"
+													      : "acmk_launch_dense_rows");
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
 	ACM_HIP_TRY(hipStreamSynchronize(st));
 	float ms = 0;

@@ -1,7 +1,8 @@
 /*
  * acm_dense_layout.cpp - the device-free half of acm_batch_decode_windows_dense (acm_batch_windows.cpp): the call's validation, its
  * soft rejections, the output size and the gather kernel's row table - with ACM_DENSE_RESAMPLE also which windows are filtered by
- * which ratio's table (acm_resample_layout.cpp) and the second row table that says so.  No HIP call here.
+ * which ratio's table (acm_resample_layout.cpp) and the second row table that says so, with ACM_DENSE_SPEED the windows' speeds, the
+ * two forms of the filter and the larger records of a call with a wide row.  No HIP call here.
  */
 #include "acm_dense_layout.h"
 
@@ -13,13 +14,20 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 	DenseLayout &D = *out;
 	D = DenseLayout();
 	if (!dense || dense->frames == 0 || (dense->channels != 1 && dense->channels != 2) ||
-	    (dense->flags & ~(ACM_DENSE_PLANAR | ACM_DENSE_MIX | ACM_DENSE_RESAMPLE)))
+	    (dense->flags & ~(ACM_DENSE_PLANAR | ACM_DENSE_MIX | ACM_DENSE_RESAMPLE | ACM_DENSE_SPEED)))
 		return ACMHIP_ERR_ARG;
 	/* the two fields behind `flags` exist for a caller that sets the flag; the products of frames and a ratio stay far inside 64 bits */
 	D.resample = (dense->flags & ACM_DENSE_RESAMPLE) != 0;
 	if (D.resample && (dense->rate == 0 || dense->reserved != 0 || dense->frames >= (1ull << 40)))
 		return ACMHIP_ERR_ARG;
 	D.rate = D.resample ? dense->rate : 0;
+	/* a window's speed is read with its flag alone; an output frame's position is its number times a step below 2^36, in 64 bits */
+	D.speed = (dense->flags & ACM_DENSE_SPEED) != 0;
+	if (D.speed && (!D.resample || dense->frames >= (1ull << 28)))
+		return ACMHIP_ERR_ARG;
+	for (size_t k = 0; D.speed && k < nwin; k++)
+		if (wins[k].reserved && (!(wins[k].reserved >> 16) || !(wins[k].reserved & 0xFFFF)))
+			return ACMHIP_ERR_ARG;
 	/* padding has one meaning in the signed little-endian writer only; the staged forms of a prestaged or packed batch are not a window's */
 	if (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE || opts.parse > ACM_BATCH_PARSE_AUTO || opts.prestaged || (opts.flags & ACM_BATCH_STAGE_PACKED))
 		return ACMHIP_ERR_ARG;
@@ -51,27 +59,38 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 	/* ... and with ACM_DENSE_RESAMPLE one at another rate than the batch's is filtered, or turned away where the ratio is none the
 	 * filter takes.  Only a window that is not turned away for its channel count is asked for its rate */
 	enum { SAME, FILTERED, BAD };
-	auto rate_kind = [&](const acm_batch_window &w, ResampleRatio *r) {
+	auto rate_kind = [&](const acm_batch_window &w, SpeedFilter *f) {
 		if (!D.resample || !has_chans(w) || (items[w.item].info.channels != D.channels && !converts(w)))
 			return (int)SAME;
 		const uint32_t ri = items[w.item].info.rate;
+		if (D.speed) {
+			/* ... by its rate times its speed, in either form of the filter */
+			*f = acm_speed_filter(ri, D.rate, w.reserved ? w.reserved >> 16 : 1, w.reserved ? w.reserved & 0xFFFF : 1);
+			return f->kind == SPEED_NONE ? (int)SAME : f->kind == SPEED_BAD ? (int)BAD : (int)FILTERED;
+		}
 		if (ri == D.rate)
 			return (int)SAME;
-		return acm_resample_ratio(ri, D.rate, r) ? (int)FILTERED : (int)BAD;
+		ResampleRatio r;
+		if (!acm_resample_ratio(ri, D.rate, &r))
+			return (int)BAD;
+		*f = SpeedFilter();
+		f->kind = SPEED_EXACT;
+		f->L = r.L, f->M = r.M, f->K = r.K, f->Wd = r.Wd;
+		return (int)FILTERED;
 	};
 	for (size_t k = 0; k < nwin; k++) {
 		/* whole frames, T of them at most - of the batch's channel count, or of the item's own where the window is converted */
 		const uint32_t c = converts(wins[k]) ? items[wins[k].item].info.channels : D.channels;
 		if (wins[k].max_words > D.frames * c || wins[k].first_word % c || wins[k].max_words % c) {
 			/* ... T frames of the batch's rate: a filtered window may be M / L times as long (8 times at most) */
-			ResampleRatio r;
+			SpeedFilter r;
 			if (wins[k].first_word % c || wins[k].max_words % c || rate_kind(wins[k], &r) != FILTERED)
 				return ACMHIP_ERR_ARG;
-			if (wins[k].max_words / c > ACM_RESAMPLE_MAX_DOWN * D.frames || acm_resample_frames(wins[k].max_words / c, r) > D.frames)
+			if (wins[k].max_words / c > ACM_RESAMPLE_MAX_DOWN * D.frames || acm_resample_frames(wins[k].max_words / c, r.L, r.M) > D.frames)
 				return ACMHIP_ERR_ARG;
 		} else if (D.resample) {
-			ResampleRatio r;
-			if (rate_kind(wins[k], &r) == FILTERED && acm_resample_frames(wins[k].max_words / c, r) > D.frames)
+			SpeedFilter r;
+			if (rate_kind(wins[k], &r) == FILTERED && acm_resample_frames(wins[k].max_words / c, r.L, r.M) > D.frames)
 				return ACMHIP_ERR_ARG;
 		}
 	}
@@ -94,9 +113,10 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 		D.bad_ratio.assign(nwin, 0);
 		std::vector<int8_t> ratio(nwin, -1);
 		std::vector<uint8_t> chans(nwin, (uint8_t)D.channels);
+		std::vector<SpeedFilter> filt(nwin);
 		for (size_t k = 0; k < nwin; k++) {
 			const acm_batch_window &w = wins[k];
-			ResampleRatio r;
+			SpeedFilter r;
 			const int kind = rate_kind(w, &r);
 			if (kind == BAD) {
 				D.bad_ratio[k] = D.rejected[k] = 1;
@@ -104,23 +124,29 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 			}
 			if (kind != FILTERED)
 				continue;
-			const uint32_t ri = items[w.item].info.rate;
+			/* a table is a function of (L, M), or of the cutoff alone where it is wide */
+			auto serves = [&](const ResampleTable &t) {
+				return r.kind == SPEED_WIDE ? t.wide && t.c == r.c : !t.wide && t.r.L == r.L && t.r.M == r.M;
+			};
 			size_t id = 0;
-			while (id < D.tables.size() && D.tables[id]->rate_in != ri)
+			while (id < D.tables.size() && !serves(*D.tables[id]))
 				id++;
 			if (id == D.tables.size()) {
 				if (id == ACM_RESAMPLE_MAX_RATIOS)
 					return ACMHIP_ERR_ARG;
-				D.tables.push_back(acm_resample_table(ri, D.rate));
+				D.tables.push_back(acm_speed_table(r));
+				D.table_rate.push_back(items[w.item].info.rate);
 				if (!D.tables.back())
 					return ACMHIP_ERR_ARG;
 			}
 			ratio[k] = (int8_t)id;
 			chans[k] = (uint8_t)items[w.item].info.channels;
+			filt[k] = r;
 		}
 		if (!D.tables.empty()) {
 			D.ratio.swap(ratio);
 			D.chans.swap(chans);
+			D.filt.swap(filt);
 		}
 	}
 	D.inner = opts;
@@ -150,6 +176,15 @@ bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_bat
 	return converts;
 }
 
+/* every table of the call, each from a multiple of 8 taps on, zeros up to the next */
+static void copy_taps(const DenseLayout &D, int16_t *taps)
+{
+	for (size_t id = 0; id < D.tables.size(); id++) {
+		int16_t *at = taps + D.tap_at(id);
+		std::fill(std::copy(D.tables[id]->q.begin(), D.tables[id]->q.end(), at), at + D.tap_words(id), (int16_t)0);
+	}
+}
+
 bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmResampleRow *rs, int16_t *taps)
 {
 	bool filters = false;
@@ -158,16 +193,36 @@ bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmR
 		rs[k] = AcmResampleRow{};
 		if (D.ratio[k] < 0 || !count)
 			continue;
-		const ResampleRatio &r = D.tables[D.ratio[k]]->r;
+		const SpeedFilter &r = D.filt[k];
 		const uint64_t f = count / D.chans[k];
-		rs[k] = AcmResampleRow{ (uint32_t)D.tap_at(D.ratio[k]), r.L, r.M, r.Wd, acm_resample_frames(f, r), f };
+		rs[k] = AcmResampleRow{ (uint32_t)D.tap_at(D.ratio[k]), r.L, r.M, r.Wd, acm_resample_frames(f, r.L, r.M), f };
 		filters = true;
 	}
-	for (size_t id = 0; id < D.tables.size(); id++) {
-		int16_t *at = taps + D.tap_at(id);
-		std::fill(std::copy(D.tables[id]->q.begin(), D.tables[id]->q.end(), at), at + D.tap_words(id), (int16_t)0);
-	}
+	copy_taps(D, taps);
 	return filters;
+}
+
+bool acm_dense_wide_rows(const DenseLayout &D, const AcmDenseRow *rows)
+{
+	for (size_t k = 0; k < D.filt.size(); k++)
+		if (D.filt[k].kind == SPEED_WIDE && (rows[k].count & ACM_DENSE_COUNT_MASK))
+			return true;
+	return false;
+}
+
+void acm_dense_speed_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmSpeedRow *sp, int16_t *taps)
+{
+	for (size_t k = 0; k < D.wins.size(); k++) {
+		const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
+		sp[k] = AcmSpeedRow{};
+		if (D.ratio[k] < 0 || !count)
+			continue;
+		const SpeedFilter &r = D.filt[k];
+		const uint64_t f = count / D.chans[k];
+		sp[k] = AcmSpeedRow{ (uint32_t)D.tap_at(D.ratio[k]), r.L, r.M, r.Wd, acm_resample_frames(f, r.L, r.M), f,
+				     r.kind == SPEED_WIDE ? r.step : 0, r.b, r.kind == SPEED_WIDE };
+	}
+	copy_taps(D, taps);
 }
 
 } // namespace acmbatch
@@ -176,6 +231,14 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 				       const uint64_t *whole, const acm_block_mark *const *marks, const uint32_t *blocks, size_t n,
 				       const uint64_t *win3, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
 				       const uint64_t *final_words, acmk_window_layout_visit_fn visit, void *ctx)
+{
+	return acmk_dense_speed_layout_visit(info, len, ok, end_status, whole, marks, blocks, n, win3, nullptr, nwin, opts, dense, final_words, visit, ctx);
+}
+
+extern "C" int acmk_dense_speed_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status,
+					     const uint64_t *whole, const acm_block_mark *const *marks, const uint32_t *blocks, size_t n,
+					     const uint64_t *win3, const uint32_t *speeds, size_t nwin, const acm_batch_opts *opts,
+					     const acm_dense_opts *dense, const uint64_t *final_words, acmk_window_layout_visit_fn visit, void *ctx)
 {
 	using namespace acmbatch;
 	std::vector<WindowItem> items(n);
@@ -192,6 +255,7 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 	for (size_t k = 0; k < nwin; k++) {
 		wins[k] = acm_batch_window{};
 		wins[k].item = (uint32_t)win3[3 * k];
+		wins[k].reserved = speeds ? speeds[k] : 0;
 		wins[k].first_word = win3[3 * k + 1];
 		wins[k].max_words = win3[3 * k + 2];
 	}
@@ -222,7 +286,33 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 			mix.push_back(converts);
 			visit(ctx, "mix", mix.data(), sizeof(uint64_t), mix.size());
 		}
-		if (D.resample) {
+		if (D.speed) {
+			const bool any = !D.tables.empty(), wide = any && acm_dense_wide_rows(D, rows.data());
+			std::vector<AcmSpeedRow> sp(nwin);
+			std::vector<int16_t> taps(any ? D.tap_at(D.tables.size()) : 0);
+			bool filters = false;
+			if (any)
+				acm_dense_speed_rows(D, rows.data(), sp.data(), taps.data());
+			std::vector<uint64_t> res, tabs;
+			for (size_t k = 0; k < nwin; k++) {
+				const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
+				const uint32_t c = (rows[k].count >> ACM_DENSE_MODE_SHIFT) ? 3 - D.channels : D.channels;
+				filters |= sp[k].L != 0;
+				if (sp[k].L)
+					res.insert(res.end(), { sp[k].wide ? 2ull : 1ull, (uint64_t)sp[k].L, (uint64_t)sp[k].M, (uint64_t)D.ratio[k], sp[k].n_out,
+								sp[k].step, (uint64_t)sp[k].b, (uint64_t)sp[k].Wd });
+				else
+					res.insert(res.end(), { D.bad_ratio[k] ? ~0ull : 0ull, (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, count / c, 0, 0, 0 });
+			}
+			res.insert(res.end(), { wide ? 2ull : filters ? 1ull : 0ull, 0, 0, 0, 0, 0, 0, 0 });
+			for (size_t id = 0; id < D.tables.size(); id++) {
+				const ResampleTable &t = *D.tables[id];
+				tabs.insert(tabs.end(), { (uint64_t)t.wide, (uint64_t)t.c, (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd,
+							  (uint64_t)t.phases(), (uint64_t)D.tap_at(id) });
+			}
+			visit(ctx, "speed", res.data(), 8 * sizeof(uint64_t), nwin + 1);
+			visit(ctx, "speed_tables", tabs.data(), 8 * sizeof(uint64_t), D.tables.size());
+		} else if (D.resample) {
 			std::vector<AcmResampleRow> rs(nwin);
 			std::vector<int16_t> taps(D.tables.empty() ? 0 : D.tap_at(D.tables.size()));
 			const bool filters = !D.tables.empty() && acm_dense_resample_rows(D, rows.data(), rs.data(), taps.data());
@@ -238,7 +328,7 @@ extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_
 			res.insert(res.end(), { (uint64_t)filters, 0, 0, 0, 0 });
 			for (size_t id = 0; id < D.tables.size(); id++) {
 				const ResampleTable &t = *D.tables[id];
-				tabs.insert(tabs.end(), { (uint64_t)t.rate_in, (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd, (uint64_t)D.tap_at(id) });
+				tabs.insert(tabs.end(), { (uint64_t)D.table_rate[id], (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd, (uint64_t)D.tap_at(id) });
 			}
 			visit(ctx, "resample", res.data(), 5 * sizeof(uint64_t), nwin + 1);
 			visit(ctx, "tables", tabs.data(), 6 * sizeof(uint64_t), D.tables.size());

@@ -34,7 +34,17 @@ struct DenseLayout {
 	std::vector<uint8_t> bad_ratio;         /* [k]: turned away for its item's rate (also counted in `rejected`) */
 	std::vector<int8_t> ratio;              /* [k]: which of `tables` row k is filtered by if it gets samples, or -1; empty without a table */
 	std::vector<uint8_t> chans;             /* [k]: samples per source frame of a row that is filtered */
-	std::vector<std::shared_ptr<const ResampleTable>> tables;      /* the distinct ratios of the call, in the order of their first window */
+	std::vector<std::shared_ptr<const ResampleTable>> tables;      /* the distinct tables of the call, in the order of their first window */
+	std::vector<uint32_t> table_rate;       /* [id]: the rate of the file whose window brought table id in */
+	bool speed = false;                     /* ACM_DENSE_SPEED: a window's `reserved` is its speed, and a ratio beyond the exact table is wide */
+	std::vector<SpeedFilter> filt;          /* [k]: L, M and the filter form of a row that is filtered; empty without a table */
+	bool has_wide() const
+	{
+		for (const auto &t : tables)
+			if (t->wide)
+				return true;
+		return false;
+	}
 	acm_batch_opts inner{};                 /* the options of the windowed decode underneath: int16 rows into the handle's own arena */
 	uint64_t pcm_arena_words(uint64_t pcm_total) const { return pcm_total + ACM_DENSE_PCM_SLACK; }
 	/* the row table travels behind the device parser's tables in the H_JOBS / D_JOBS arenas */
@@ -42,7 +52,9 @@ struct DenseLayout {
 	/* ... and, where a window may be resampled, the second table and the ratios' taps behind it, each from a multiple of 16 bytes on */
 	size_t row_table_bytes() const { return wins.size() * sizeof(AcmDenseRow); }
 	size_t resample_off() const { return row_table_bytes(); }
-	size_t taps_off() const { return resample_off() + wins.size() * sizeof(AcmResampleRow); }
+	/* (a call that may have a wide row keeps room for the larger records of acm_dense_speed.hip) */
+	size_t second_bytes() const { return has_wide() ? sizeof(AcmSpeedRow) : sizeof(AcmResampleRow); }
+	size_t taps_off() const { return resample_off() + wins.size() * second_bytes(); }
 	size_t tap_words(size_t id) const { return (size_t)round_up(tables[id]->q.size(), 8); }
 	size_t tap_at(size_t id) const
 	{
@@ -72,6 +84,11 @@ bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_bat
  * acm_dense_resample.hip's to read, else the first alone is the kernel's that acm_dense_rows chose */
 bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmResampleRow *rs, int16_t *taps);
 
+/* ACM_DENSE_SPEED: whether a row that got samples takes the wide filter.  Then the second table is acm_dense_speed_rows' - the same
+ * for acm_dense_speed.hip, which reads all three - else the call goes on as it does without the flag */
+bool acm_dense_wide_rows(const DenseLayout &D, const AcmDenseRow *rows);
+void acm_dense_speed_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmSpeedRow *sp, int16_t *taps);
+
 } // namespace acmbatch
 
 extern "C" {
@@ -88,6 +105,15 @@ int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_t *len, con
 			    const acm_block_mark *const *marks, const uint32_t *blocks, size_t n, const uint64_t *win3, size_t nwin,
 			    const acm_batch_opts *opts, const acm_dense_opts *dense, const uint64_t *final_words,
 			    acmk_window_layout_visit_fn visit, void *ctx);
+/* The same with speeds[k] (may be null: zeros) as window k's acm_batch_window.reserved.  With ACM_DENSE_SPEED, in place of "resample"
+ * and "tables": "speed" (8 per window: the kind - 0 not filtered, 1 exact, 2 wide, all ones turned away for its ratio -, L, M, the
+ * table's number in "speed_tables" or all ones, the row's frames, step, b, Wd; nwin + 1 entries, the last one's first word what the
+ * launch is: 0 the kernel of a call without the flags, 1 acm_dense_resample, 2 acm_dense_speed) and "speed_tables" (8 per distinct
+ * table: 1 if wide, c, L, M, K, Wd, phases, where its taps begin) */
+int acmk_dense_speed_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status,
+				  const uint64_t *whole, const acm_block_mark *const *marks, const uint32_t *blocks, size_t n, const uint64_t *win3,
+				  const uint32_t *speeds, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+				  const uint64_t *final_words, acmk_window_layout_visit_fn visit, void *ctx);
 }
 
 #endif

@@ -4,303 +4,15 @@
  * laid out - copied, split, down- or up-mixed - as acm_dense_mixed lays them out.  Launched only where the second row table says that
  * a row is filtered (acm_dense_layout.cpp); every other call keeps the kernel it had.
  *
- * No counterpart in the reference.  The filter is the contract's, on integers: for output frame j of a channel,
- *   n = j * M;  base = n / L;  ph = n % L;  acc = sum over t < K of q[ph][t] * x[base - Wd + 1 + t];  y = clamp((acc + 8192) >> 14)
- * with x the row's source frames AFTER their channel conversion, zero outside [0, frames_in), and q the ratio's Q14 table as
- * acm_dense_resample_taps() hands it out.  32-bit sums: a phase's |q| add up to less than 65536.
- *
- * The geometry is acm_dense_mixed's: sub-rows (one, or one per plane), units of 256 lanes and 2048 outputs, a flat grid that strides
- * over (row, sub-row, unit); a workgroup works on one row, so its kind is a workgroup-uniform branch.  A filtered unit
- *
- *   1. copies the ratio's table - 32 KB at most - into LDS: the lanes' phases differ, so the taps are gathered;
- *   2. stages the source span of its outputs, converted, as one plane per output channel of the sub-row in LDS, zeros where the span
- *      reaches in front of the row's first frame or behind its last: lanes load the aligned 16-byte lines that hold a sample of the
- *      span - so every load lies inside the row's own samples rounded out to 16 bytes, which a window's 64-sample slot contains -
- *      and de-interleave, down-mix or duplicate on the way into LDS;
- *   3. has every lane filter its 8 consecutive outputs from LDS - base and phase by one division a lane, then by stepping - and store
- *      them as whole 16-byte lines where the output is aligned; the up to 7 samples in front of a row's first line and behind its
- *      last one are single outputs with narrow stores, as in acm_dense_mix.hip.
- *
- * Table and planes share 63 KB of LDS, so two workgroups fit a CU's 160 KB.  The planes hold SPAN_CAP samples; a unit whose span is
- * longer (M / L above about 7.5: two planes hold half the frames each) is worked off in 2, 4, ... passes of 1024, 512, ... outputs,
- * each staging its own span.  No scratch: every register array is indexed by constants after unrolling.  No float arithmetic before the final
- * times 2^-15.
+ * No counterpart in the reference.  The filter, the staging of a unit and the geometry - acm_dense_mixed's: sub-rows (one, or one
+ * per plane), units of 256 lanes and 2048 outputs, a flat grid that strides over (row, sub-row, unit); a workgroup works on one row, so
+ * its kind is a workgroup-uniform branch - are acm_dense_filter.h's, shared with acm_dense_speed.hip.
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "acm_dense_vec.h"
-#include "acm_device.h"
+#include "acm_dense_filter.h"
 
 namespace {
-
-enum Layout { MONO = 0, INTER = 1, PLANAR = 2 };
-enum Path { COPY, SPLIT, DOWN, UP_INTER };      /* what a sub-row that is not filtered does with its source: acm_dense_mix.hip's */
-
-constexpr uint32_t TAB_CAP = 16384;             /* int16 of a ratio's table: ACM_RESAMPLE_MAX_TAPS */
-constexpr uint32_t SPAN_CAP = 15872;            /* int16 of the staged planes: with the table 63 KB */
-constexpr uint32_t UNIT = DENSE_BLOCK * DENSE_VEC;
-
-/* ------------------------------------------------------------------------------------------------ rows that are not filtered */
-
-/* output sample e of a sub-row whose source starts at sub, e below what the sub-row has */
-template <Path P> __device__ __forceinline__ int sample(const int16_t *sub, uint64_t e)
-{
-	if (P == COPY)
-		return sub[e];
-	if (P == SPLIT)
-		return sub[2 * e];
-	if (P == DOWN)
-		return ((int)sub[2 * e] + (int)sub[2 * e + 1]) >> 1;
-	return sub[e >> 1];
-}
-
-/* one unit of one sub-row: `have` output samples from `sub`, zeros behind them up to sub_len - acm_dense_mix.hip's, line for line */
-template <typename OUT, Path P>
-__device__ __forceinline__ void sub_row(const int16_t *sub, uint64_t have, OUT *o, uint64_t sub_len, uint32_t unit, uint32_t units)
-{
-	constexpr int PER_LANE = P == UP_INTER ? 2 : 1;
-	const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
-	const uint64_t head = to_line < sub_len ? to_line : sub_len;
-	const uint64_t nvec = (sub_len - head) / DENSE_VEC;
-	const uint64_t tail = head + nvec * DENSE_VEC;
-	const int16_t *first = P == COPY ? sub + head : P == UP_INTER ? sub + head / 2 : sub + 2 * head;
-	const uint32_t sh = (uint32_t)reinterpret_cast<uintptr_t>(first) & 15u;
-	const uint32_t odd = P == UP_INTER ? (uint32_t)head & 1u : 0;
-
-	const uint64_t v = ((uint64_t)unit * DENSE_BLOCK + threadIdx.x) * PER_LANE;
-	if (v < nvec) {
-		const uint64_t e = head + v * DENSE_VEC;
-		const bool two = PER_LANE == 2 && v + 1 < nvec;
-		const uint32_t outs = two ? 2 * DENSE_VEC : DENSE_VEC;
-		int s[PER_LANE][DENSE_VEC];
-		if (e + outs <= have) {
-			if (P == COPY) {
-				load_vec<1>(sub + e, sh, s[0]);
-			} else if (P == SPLIT) {
-				load_vec<2>(sub + 2 * e, sh, s[0]);
-			} else if (P == DOWN) {
-				uint32_t d[DENSE_VEC];
-				load_dwords<DENSE_VEC, 3>(sub + 2 * e, sh, 32, d);
-#pragma unroll
-				for (int i = 0; i < DENSE_VEC; i++)
-					s[0][i] = ((int)(int16_t)(d[i] & 0xFFFFu) + (int)(int16_t)(d[i] >> 16)) >> 1;
-			} else {
-				uint32_t d[5];
-				load_dwords<5, 2>(sub + e / 2, sh, outs + 2 * odd, d);
-				int t[10];
-#pragma unroll
-				for (int j = 0; j < 5; j++) {
-					t[2 * j] = (int16_t)(d[j] & 0xFFFFu);
-					t[2 * j + 1] = (int16_t)(d[j] >> 16);
-				}
-#pragma unroll
-				for (int i = 0; i < PER_LANE * DENSE_VEC; i++)
-					s[i / DENSE_VEC][i % DENSE_VEC] = odd ? t[(i + 1) / 2] : t[i / 2];
-			}
-		} else {
-#pragma unroll
-			for (int i = 0; i < PER_LANE * DENSE_VEC; i++)
-				s[i / DENSE_VEC][i % DENSE_VEC] = i < outs && e + i < have ? sample<P>(sub, e + i) : 0;
-		}
-		store_vec<false>(o + e, s[0]);
-		if (two)
-			store_vec<false>(o + e + DENSE_VEC, s[PER_LANE - 1]);
-	}
-	if (unit == 0 && threadIdx.x < head) {
-		const uint64_t e = threadIdx.x;
-		o[e] = to_out(o, e < have ? sample<P>(sub, e) : 0);
-	}
-	if (unit == units - 1 && tail + threadIdx.x < sub_len) {
-		const uint64_t e = tail + threadIdx.x;
-		o[e] = to_out(o, e < have ? sample<P>(sub, e) : 0);
-	}
-}
-
-/* ------------------------------------------------------------------------------------------------ rows that are filtered */
-
-/* K products from the table and a plane, rounded and saturated */
-__device__ __forceinline__ int filter_one(const int16_t *tab, const int16_t *x, uint32_t K)
-{
-	int acc = 0;
-	for (uint32_t t = 0; t < K; t++)
-		acc += (int)tab[t] * (int)x[t];
-	return min(max((acc + 8192) >> 14, -32768), 32767);
-}
-
-/* One unit of one sub-row of a filtered row.  from: the row's source samples, r.frames_in frames of one or two samples - the other
- * count than the batch's where the row converts; plane: which channel a PLANAR sub-row is.  tab, xs: the table and the planes in LDS */
-template <typename OUT, int LAYOUT>
-__device__ __forceinline__ void filtered_sub_row(const int16_t *from, bool converts, uint32_t plane, const AcmResampleRow &r, const int16_t *taps,
-						 OUT *o, uint64_t sub_len, uint32_t unit, uint32_t units, int16_t *tab, int16_t *xs)
-{
-	constexpr uint32_t EPF = LAYOUT == INTER ? 2 : 1;              /* elements of the sub-row per frame = planes staged */
-	const uint32_t src_c = LAYOUT == MONO ? (converts ? 2 : 1) : (converts ? 1 : 2);
-	const uint32_t L = r.L, M = r.M, Wd = r.Wd, K = 2 * Wd, tid = threadIdx.x;
-	const uint32_t qM = M / L, rM = M - qM * L;                     /* a frame's step: base += qM, ph += rM, with a carry */
-	const int64_t f_in = (int64_t)r.frames_in;
-
-	/* 1. the table, dword by dword: K is even and a table begins on a 16-byte line */
-	{
-		const uint32_t *g = reinterpret_cast<const uint32_t *>(taps + r.tab);
-		uint32_t *l = reinterpret_cast<uint32_t *>(tab);
-		for (uint32_t i = tid; i < L * K / 2; i += DENSE_BLOCK)
-			l[i] = g[i];
-	}
-
-	/* the sub-row as acm_dense_mixed cuts it: [0, head) in front of the first aligned output line, nvec vectors, [tail, sub_len) */
-	const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
-	const uint64_t head = to_line < sub_len ? to_line : sub_len;
-	const uint64_t nvec = (sub_len - head) / DENSE_VEC;
-	const uint64_t tail = head + nvec * DENSE_VEC;
-	const uint64_t n_el = min(sub_len, r.n_out * EPF);              /* elements behind these are zero */
-	const uint64_t bs = head + (uint64_t)unit * UNIT, be = min(bs + UNIT, tail);   /* the unit's vectors: elements [bs, be) */
-
-	/* outputs a pass: as many as keep the planes inside SPAN_CAP, the up to 7 + 7 single outputs of a row's ends included */
-	uint32_t P = UNIT;
-	while (EPF * (((uint64_t)(P + 16) / EPF * M + L - 1) / L + K + 2) > SPAN_CAP)
-		P >>= 1;
-	const uint32_t plane_len = SPAN_CAP / EPF;
-
-	/* the aligned line the row's first sample lies in, and how many samples into it */
-	const uint32_t o_src = ((uint32_t)reinterpret_cast<uintptr_t>(from) & 15u) / 2;
-	const u32x4 *lines = reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(from) - 2 * o_src);
-
-	for (uint64_t plo = bs;; plo += P) {
-		const uint64_t phi = min(plo + P, be);
-		const bool last = plo + P >= be;                        /* of the unit's passes */
-		/* elements this pass writes: its vectors, and the ends of the row where it holds them */
-		const uint64_t elo = unit == 0 && plo == bs ? 0 : plo;
-		const uint64_t ehi = last && unit == units - 1 ? sub_len : phi;
-		const uint64_t chi = min(ehi, n_el);                    /* ... of which [elo, chi) are computed */
-		int64_t s0 = 0;
-		if (chi > elo) {
-			/* 2. the span: source frames [s0, s0 + span) serve the output frames [jlo, jhi) */
-			const uint64_t jlo = elo / EPF, jhi = (chi + EPF - 1) / EPF;
-			const uint64_t base_lo = jlo * M / L, base_hi = (jhi - 1) * M / L;
-			s0 = (int64_t)base_lo - (int64_t)Wd + 1;
-			const uint32_t span = (uint32_t)(base_hi - base_lo) + K;
-			const int64_t fa = max(s0, (int64_t)0), fb = min(s0 + (int64_t)span, f_in);
-			for (uint32_t i = tid; i < span; i += DENSE_BLOCK) {
-				const int64_t fr = s0 + i;
-				if (fr < fa || fr >= fb) {
-					xs[i] = 0;
-					if (EPF == 2)
-						xs[plane_len + i] = 0;
-				}
-			}
-			if (fb > fa) {
-				const int64_t sa = fa * src_c, sb = fb * src_c;         /* samples of the row */
-				const uint64_t l0 = (uint64_t)(o_src + sa) / 8, l1 = (uint64_t)(o_src + sb + 7) / 8;
-				for (uint64_t li = l0 + tid; li < l1; li += DENSE_BLOCK) {
-					const u32x4 v = lines[li];
-					const uint32_t d[4] = { v.x, v.y, v.z, v.w };
-					const int64_t s_line = (int64_t)(8 * li) - o_src;       /* the row's sample the line begins with */
-					if (src_c == 1) {
-#pragma unroll
-						for (int p = 0; p < 8; p++) {
-							const int64_t s = s_line + p;
-							if (s >= sa && s < sb) {
-								const int16_t val = (int16_t)(p & 1 ? d[p / 2] >> 16 : d[p / 2] & 0xFFFFu);
-								xs[s - s0] = val;
-								if (EPF == 2)
-									xs[plane_len + (s - s0)] = val;
-							}
-						}
-					} else {
-						/* a stereo row begins on a dword: a dword is a frame */
-#pragma unroll
-						for (int p = 0; p < 4; p++) {
-							const int64_t s = s_line + 2 * p;
-							if (s >= sa && s < sb) {
-								const int lft = (int16_t)(d[p] & 0xFFFFu), rgt = (int16_t)(d[p] >> 16);
-								const int64_t at = s / 2 - s0;
-								if (LAYOUT == MONO) {
-									xs[at] = (int16_t)((lft + rgt) >> 1);
-								} else if (LAYOUT == INTER) {
-									xs[at] = (int16_t)lft;
-									xs[plane_len + at] = (int16_t)rgt;
-								} else {
-									xs[at] = (int16_t)(plane ? rgt : lft);
-								}
-							}
-						}
-					}
-				}
-			}
-		}
-		__syncthreads();
-
-		/* 3. the pass's vectors: lane tid writes elements [e0, e0 + 8) */
-		const uint64_t e0 = plo + (uint64_t)tid * DENSE_VEC;
-		if (e0 < phi) {
-			int y[DENSE_VEC];
-			if (e0 < chi) {
-				/* the frames of the vector: 8, or with two elements a frame the 5 that 8 elements from an odd one on touch */
-				constexpr int NF = EPF == 2 ? 5 : DENSE_VEC;
-				const uint64_t j0 = e0 / EPF, n0 = j0 * M;
-				uint64_t base = n0 / L;
-				uint32_t ph = (uint32_t)(n0 - base * L);
-				/* where a frame's taps and source begin: ph * K into the table, base - Wd + 1 - s0 into a plane */
-				uint32_t ftap[NF], foff[NF];
-#pragma unroll
-				for (int m = 0; m < NF; m++) {
-					ftap[m] = ph * K;
-					foff[m] = (uint32_t)((int64_t)base - (int64_t)Wd + 1 - s0);
-					base += qM;
-					ph += rM;
-					if (ph >= L) {
-						ph -= L;
-						base++;
-					}
-				}
-				const uint32_t par = EPF == 2 ? (uint32_t)e0 & 1u : 0;
-				uint32_t tap[DENSE_VEC], off[DENSE_VEC];
-				int acc[DENSE_VEC];
-#pragma unroll
-				for (int i = 0; i < DENSE_VEC; i++) {
-					const uint32_t f_tap = EPF == 2 ? (par ? ftap[(i + 1) / 2] : ftap[i / 2]) : ftap[i];
-					const uint32_t f_off = EPF == 2 ? (par ? foff[(i + 1) / 2] : foff[i / 2]) : foff[i];
-					const bool live = e0 + i < chi;         /* an element behind the row's last frame reads what is there and is zero */
-					tap[i] = live ? f_tap : 0;
-					off[i] = live ? f_off + (EPF == 2 && ((i + par) & 1) ? plane_len : 0) : 0;
-					acc[i] = 0;
-				}
-				for (uint32_t t = 0; t < K; t++) {
-#pragma unroll
-					for (int i = 0; i < DENSE_VEC; i++)
-						acc[i] += (int)tab[tap[i] + t] * (int)xs[off[i] + t];
-				}
-#pragma unroll
-				for (int i = 0; i < DENSE_VEC; i++)
-					y[i] = e0 + i < chi ? min(max((acc[i] + 8192) >> 14, -32768), 32767) : 0;
-			} else {
-#pragma unroll
-				for (int i = 0; i < DENSE_VEC; i++)
-					y[i] = 0;
-			}
-			store_vec<false>(o + e0, y);
-		}
-		/* ... and the single outputs of the row's ends: [0, head) with the first pass of unit 0, [tail, sub_len) with the last of all */
-		const bool front = unit == 0 && plo == bs && tid < head;
-		const bool back = last && unit == units - 1 && tid >= DENSE_BLOCK - DENSE_VEC && tail + (tid - (DENSE_BLOCK - DENSE_VEC)) < sub_len;
-		if (front || back) {
-			const uint64_t e = front ? tid : tail + (tid - (DENSE_BLOCK - DENSE_VEC));
-			int y = 0;
-			if (e < chi) {
-				const uint64_t j = e / EPF, n = j * M, base = n / L;
-				const uint32_t ph = (uint32_t)(n - base * L);
-				const uint32_t off = (uint32_t)((int64_t)base - (int64_t)Wd + 1 - s0) + (EPF == 2 && (e & 1) ? plane_len : 0);
-				y = filter_one(tab + ph * K, xs + off, K);
-			}
-			o[e] = to_out(o, y);
-		}
-		if (last)
-			break;
-		__syncthreads();                                         /* the next pass stages over these planes */
-	}
-}
 
 /* sub_len: output samples of a sub-row (frames with PLANAR, else the whole row); units: workgroups per sub-row */
 template <typename OUT, int LAYOUT>
@@ -325,32 +37,19 @@ __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_resample(const int16_t 
 		OUT *o = out + k * row_len + (uint64_t)plane * sub_len;
 		if (r.L != 0) {
 			__syncthreads();                                /* the work before this one has read its table and planes */
-			filtered_sub_row<OUT, LAYOUT>(from, converts, plane, r, taps, o, sub_len, unit, units, tab, xs);
-		} else if (LAYOUT == MONO) {
-			if (converts)
-				sub_row<OUT, DOWN>(from, count / 2, o, sub_len, unit, units);
-			else
-				sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
-		} else if (LAYOUT == INTER) {
-			if (converts)
-				sub_row<OUT, UP_INTER>(from, 2 * count, o, sub_len, unit, units);
-			else
-				sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
+			filtered_sub_row<OUT, LAYOUT, false>(from, converts, plane, r, taps, o, sub_len, unit, units, tab, xs);
 		} else {
-			if (converts)
-				sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
-			else
-				sub_row<OUT, SPLIT>(from + plane, (count + 1 - plane) / 2, o, sub_len, unit, units);
+			plain_sub_row<OUT, LAYOUT>(from, converts, count, plane, o, sub_len, unit, units);
 		}
 	}
 }
 
 template <typename OUT, int LAYOUT>
-int launch(uint32_t grid, hipStream_t st, const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps,
-	   uint64_t nwork, uint32_t units, void *d_out, uint64_t row_len, uint64_t sub_len)
+int launch(const FilterGeo &g, hipStream_t st, const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps,
+	   void *d_out)
 {
-	hipLaunchKernelGGL((acm_dense_resample<OUT, LAYOUT>), dim3(grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_rs, d_taps, nwork, units,
-			   static_cast<OUT *>(d_out), row_len, sub_len);
+	hipLaunchKernelGGL((acm_dense_resample<OUT, LAYOUT>), dim3(g.grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_rs, d_taps, g.nwork, g.units,
+			   static_cast<OUT *>(d_out), g.row_len, g.sub_len);
 	return (int)hipGetLastError();
 }
 
@@ -361,18 +60,13 @@ extern "C" int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRo
 {
 	if (nrows == 0)
 		return 0;
-	const int layout = channels == 1 ? MONO : planar ? PLANAR : INTER;
-	const int subs = layout == PLANAR ? 2 : 1;
-	const uint64_t row_len = frames * channels, sub_len = subs == 2 ? frames : row_len;
-	const uint64_t units = std::max<uint64_t>(1, (sub_len / DENSE_VEC + DENSE_BLOCK - 1) / DENSE_BLOCK);
-	if (units > 0x7FFFFFFFull || nrows > ~0ull / (units * subs))
+	const FilterGeo g = filter_geo(nrows, frames, channels, planar);
+	if (!g.ok)
 		return (int)hipErrorInvalidValue;
-	const uint64_t nwork = nrows * units * subs;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
 	hipStream_t st = (hipStream_t)stream;
-#define ACM_RS_LAUNCH(OUT, LAYOUT) launch<OUT, LAYOUT>(grid, st, d_src, d_rows, d_rs, d_taps, nwork, (uint32_t)units, d_out, row_len, sub_len)
+#define ACM_RS_LAUNCH(OUT, LAYOUT) launch<OUT, LAYOUT>(g, st, d_src, d_rows, d_rs, d_taps, d_out)
 	if (f32)
-		return layout == MONO ? ACM_RS_LAUNCH(float, MONO) : layout == INTER ? ACM_RS_LAUNCH(float, INTER) : ACM_RS_LAUNCH(float, PLANAR);
-	return layout == MONO ? ACM_RS_LAUNCH(int16_t, MONO) : layout == INTER ? ACM_RS_LAUNCH(int16_t, INTER) : ACM_RS_LAUNCH(int16_t, PLANAR);
+		return g.layout == MONO ? ACM_RS_LAUNCH(float, MONO) : g.layout == INTER ? ACM_RS_LAUNCH(float, INTER) : ACM_RS_LAUNCH(float, PLANAR);
+	return g.layout == MONO ? ACM_RS_LAUNCH(int16_t, MONO) : g.layout == INTER ? ACM_RS_LAUNCH(int16_t, INTER) : ACM_RS_LAUNCH(int16_t, PLANAR);
 #undef ACM_RS_LAUNCH
 }

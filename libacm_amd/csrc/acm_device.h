@@ -125,6 +125,15 @@ struct AcmResampleRow {
 	uint32_t tab, L, M, Wd;
 	uint64_t n_out, frames_in;
 };
+/* ACM_DENSE_SPEED (acm_dense_speed.hip): that record for a call in which some row takes the wide filter.  wide == 0: the record's
+ * head is the row's AcmResampleRow.  Else the table at `tab` has (1 << b) + 1 phases of 2 * Wd taps, and output frame j reads from
+ * source position j * step in 32.32 fixed point (include/acm_hip.h) */
+struct AcmSpeedRow {
+	uint32_t tab, L, M, Wd;
+	uint64_t n_out, frames_in;
+	uint64_t step;
+	uint32_t b, wide;
+};
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -328,6 +337,11 @@ int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *d_rows, uin
  * tables of the call's ratios, 16-byte aligned.  The same demands on d_src and d_out */
 int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps, uint64_t nrows,
 			       void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
+/* acm_dense_speed.hip: the same launch for a call in which some row takes the wide filter (d_sp[k].wide != 0); rows with L != 0
+ * and wide == 0 are filtered as acmk_launch_dense_resample filters them, the others written as it writes them.  d_taps: the exact
+ * and wide tables of the call, 16-byte aligned.  The same demands on d_src and d_out */
+int acmk_launch_dense_speed(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmSpeedRow *d_sp, const int16_t *d_taps, uint64_t nrows,
+			    void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,17 @@ runs out of time ends the probe.
                  with --parent-lib, on the parent commit's library in a process of its own
   With --step kernel --rates the trace holds acm_dense_resample's own durations.
 
-    python profiles/dense_crop_probe.py [--mix | --rates] [--windows 1024,16384] [--out probe_out/dense_crop.json]
+  --speed (profiles/dense_speed_notes.txt): ACM_DENSE_SPEED.
+    speedflag:<n>   the --rates call with every speed 1/1 (flag 32 on: the same kernels launch) against the same call without the
+                    flag, alternating; with --parent-lib also the call without the flag on the parent commit's library
+    speedmix:<n>    the default workload's streams at 22050 Hz into a float32 [N, 1, 16000] batch, one second of output a row: window k
+                    is played at (9/10, 1/1, 11/10)[k % 3] - wide c = 51, exact 320 : 441, wide c = 42 - in one call; the three groups
+                    as three crop_batch calls plus index_copy; and the rate=-only call of the same shape (every window 22050 frames;
+                    with --parent-lib also on the parent's library)
+  With --step kernel --speed the trace holds, call after call, batches of ONE speed - 1/1 (acm_dense_resample, K = 24), 9/10
+  (acm_dense_speed, K = 22), 11/10 (K = 26) - and the batch of thirds.
+
+    python profiles/dense_crop_probe.py [--mix | --rates | --speed] [--windows 1024,16384] [--out probe_out/dense_crop.json]
 """
 import argparse
 import ctypes as C
@@ -303,6 +313,127 @@ def step_rates(args, n, resample):
                 samples_synthesised=int(dec.timing.samples), blocks_parsed=int(dec.timing.blocks_parsed))
 
 
+SPEEDS = ((9, 10), (1, 1), (11, 10))
+SPEED_RATE = 16000
+
+
+def speed_windows(args, n, speeds):
+    """one second of output a row: (file, first_frame, source frames of that second at the window's speed), and the speeds"""
+    import numpy as np
+    from libacm_amd import batch
+    rng = np.random.default_rng(22053)
+    total = args.blocks * args.rows << args.level
+    sp = [speeds[k % len(speeds)] for k in range(n)]
+    return [(k % args.streams, int(rng.integers(0, total - 2 * FRAMES)), batch.source_frames(SPEED_RATE, FRAMES, SPEED_RATE, sp[k])) for k in range(n)], sp
+
+
+def timed(variants, args):
+    import torch
+    times = {name: [] for name, _ in variants}
+    for r in range(args.warmup + args.reps):
+        for name, fn in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if r >= args.warmup:
+                times[name].append(time.perf_counter() - t0)
+    return {name: stats(t) for name, t in times.items()}
+
+
+def step_speed_flag(args, n):
+    """the --rates call without flag 32 and - where the loaded library knows it - with it and every speed 1/1, alternating"""
+    import torch
+    from libacm_amd import batch, capi
+    files = rate_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    wins = rate_windows(args, n, clip=False)
+    buf = torch.empty(n * FRAMES, dtype=dec.dtype, device="cuda:0")
+    ev = {"rate_only": [], "speed_all_ones": []}
+
+    def call(name, **kw):
+        dec.crop_batch(files, wins, FRAMES, channels=1, planar=True, index=index, out=buf, rate=FRAMES, **kw)
+        ev[name].append(dec.timing.kernel_s)
+    variants = [("rate_only", lambda: call("rate_only"))]
+    if hasattr(capi.lib(), "acm_dense_speed_frames"):
+        variants.append(("speed_all_ones", lambda: call("speed_all_ones", speed=[(1, 1)] * n)))
+    res = timed(variants, args)
+    dec.dev.close()
+    return dict(library=os.environ.get("ACM_HIP_LIB", "shipped"), call_wall=res,
+                synthesis_plus_gather_events={k: stats(v[args.warmup:]) for k, v in ev.items() if v})
+
+
+def step_speed_mix(args, n):
+    import numpy as np
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    T = SPEED_RATE
+    plain = [(f, a, FRAMES) for f, a, _ in speed_windows(args, n, SPEEDS)[0]]
+    buf = torch.empty(n * T, dtype=dec.dtype, device="cuda:0")
+    keep, ev = {}, {"rate_only": [], "one_call_three_speeds": []}
+
+    def rate_only():
+        dec.crop_batch(files, plain, T, channels=1, planar=True, index=index, out=buf, rate=T)
+        ev["rate_only"].append(dec.timing.kernel_s)
+    variants = [("rate_only", rate_only)]
+    if hasattr(capi.lib(), "acm_dense_speed_frames"):
+        wins, sp = speed_windows(args, n, SPEEDS)
+        groups = [[k for k in range(n) if k % 3 == g] for g in range(3)]
+        bufs = [torch.empty(len(g) * T, dtype=dec.dtype, device="cuda:0") for g in groups]
+        idx = [torch.tensor(g, dtype=torch.int64, device="cuda:0") for g in groups]
+
+        def one_call():
+            keep["a"], keep["frames"], keep["st"] = dec.crop_batch(files, wins, T, channels=1, planar=True, index=index, out=buf, rate=T, speed=sp)
+            ev["one_call_three_speeds"].append(dec.timing.kernel_s)
+
+        def three_calls():
+            out = torch.empty(n, 1, T, dtype=dec.dtype, device="cuda:0")
+            for g, b, i in zip(groups, bufs, idx):
+                x, _, _ = dec.crop_batch(files, [wins[k] for k in g], T, channels=1, planar=True, index=index, out=b, rate=T, speed=[sp[k] for k in g])
+                out.index_copy_(0, i, x)
+            keep["b"] = out
+        variants += [("one_call_three_speeds", one_call), ("three_calls_index_copy", three_calls)]
+    res = dict(library=os.environ.get("ACM_HIP_LIB", "shipped"), call_wall=timed(variants, args),
+               synthesis_plus_gather_events={k: stats(v[args.warmup:]) for k, v in ev.items() if v})
+    if "a" in keep:
+        a, b = res["call_wall"]["one_call_three_speeds"], res["call_wall"]["three_calls_index_copy"]
+        pair = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+        res["tensors_equal"] = bool(np.array_equal(keep["a"].cpu().numpy().view(np.uint8), keep["b"].cpu().numpy().view(np.uint8)))
+        res["verdict"] = dict(three_calls_min_ms=b["min_ms"], one_call_max_ms=a["max_ms"], margin_ms=round(b["min_ms"] - a["max_ms"], 3),
+                              spread_of_the_two_compared_ms=round(pair, 3), one_call_wins=bool(b["min_ms"] - a["max_ms"] > pair))
+        res["frames_delivered"] = int(sum(keep["frames"]))
+        res["ok"] = all(s == 0 for s in keep["st"])
+    dec.dev.close()
+    return res
+
+
+def step_kernel_speed(args):
+    """REPS calls per batch of ONE speed and of the thirds: the launches' own durations are the trace's"""
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    out = {}
+    for n in args.windows:
+        buf = torch.empty(n * SPEED_RATE, dtype=dec.dtype, device="cuda:0")
+        for name, speeds in (("1_1", SPEEDS[1:2]), ("9_10", SPEEDS[:1]), ("11_10", SPEEDS[2:]), ("thirds", SPEEDS)):
+            wins, sp = speed_windows(args, n, speeds)
+            k_ms = []
+            for r in range(args.warmup + args.reps):
+                b, frames, st = dec.crop_batch(files, wins, SPEED_RATE, channels=1, planar=True, index=index, out=buf, rate=SPEED_RATE, speed=sp)
+                if r >= args.warmup:
+                    k_ms.append(dec.timing.kernel_s)
+            out["%d_windows_%s" % (n, name)] = dict(synthesis_plus_gather_events=stats(k_ms), frames_delivered=int(sum(frames)),
+                                                    source_frames=int(sum(w[2] for w in wins)), ok=all(s == 0 for s in st))
+    dec.dev.close()
+    return out
+
+
 def step_kernel_mix(args):
     """REPS calls per shape of the mixed batch (acm_dense_mixed) and of a batch over the files of one channel count (acm_dense_rows): the
     launch's own durations are the trace's; the call's wall clock and event time are printed here"""
@@ -385,13 +516,22 @@ def main():
     ap.add_argument("--mix", action="store_true", help="mono and stereo streams in one batch: crop_batch(mix=True) against two calls + torch")
     ap.add_argument("--rates", action="store_true", help="files at 11025, 22050 and 44100 Hz in one 22050 Hz batch: crop_batch(rate=22050), and "
                     "the plain call over the same windows clipped to a row (with --parent-lib also on the parent commit's library)")
+    ap.add_argument("--speed", action="store_true", help="ACM_DENSE_SPEED: the flag with every speed 1/1 against the call without it, and a batch of "
+                    "three speeds in one call against three calls + index_copy and against the rate=-only call (with --parent-lib also on "
+                    "the parent commit's library)")
     ap.add_argument("--parent-lib", help="with --mix: the parent commit's libacm_hip.so; adds, per shape, a batch of one channel count on that "
                     "library and on this tree's without and with the flag (each library a child process of its own)")
     ap.add_argument("--step", help="(internal) compare:<windows>:<f32 0|1>, mix:<windows>:<f32>:<channels>, or kernel: run one step in this "
                     "process and print its JSON")
     args = ap.parse_args()
     if args.step:
-        if args.step == "kernel" and args.rates:
+        if args.step == "kernel" and args.speed:
+            res = step_kernel_speed(args)
+        elif args.step.startswith("speedflag:"):
+            res = step_speed_flag(args, int(args.step.split(":")[1]))
+        elif args.step.startswith("speedmix:"):
+            res = step_speed_mix(args, int(args.step.split(":")[1]))
+        elif args.step == "kernel" and args.rates:
             res = {"%d_windows" % n: step_rates(args, n, True) for n in args.windows}
         elif args.step == "kernel":
             res = step_kernel_mix(args) if args.mix else step_kernel(args)
@@ -416,15 +556,17 @@ def main():
     if args.rates:
         steps = ["rates:%d:%d:tree" % (n, r) for n in args.windows for r in (1, 0)]
         steps += ["rates:%d:0:parent" % n for n in args.windows if args.parent_lib]
+    if args.speed:
+        steps = ["%s:%d:%s" % (what, n, lib) for n in args.windows for what in ("speedflag", "speedmix") for lib in ("tree", "parent")[:2 if args.parent_lib else 1]]
     if args.mix and args.parent_lib:
         steps += ["flag:%d:%d:%d:%s" % (n, f32, ch, lib) for n in args.windows for f32 in (1, 0) for ch in (1, 2) for lib in ("parent", "tree")]
     for step in steps:
         env = dict(os.environ)
         if step.endswith(":parent"):
             env["ACM_HIP_LIB"] = os.path.abspath(args.parent_lib)
-        key, step = step, step.rsplit(":", 1)[0] if step.startswith(("flag:", "rates:")) else step
+        key, step = step, step.rsplit(":", 1)[0] if step.startswith(("flag:", "rates:", "speedflag:", "speedmix:")) else step
         cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--host-index-max", str(args.host_index_max)] + ["--mix"] * args.mix + \
-              ["--rates"] * args.rates + \
+              ["--rates"] * args.rates + ["--speed"] * args.speed + \
               [a for k in ("streams", "level", "rows", "blocks", "warmup", "reps") for a in ("--" + k, str(getattr(args, k)))]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.step_seconds, env=env)
@@ -436,7 +578,7 @@ def main():
             print("step %s failed (%d): nothing more is started\n%s" % (step, r.returncode, r.stdout[-3000:]))
             return 1
         got = json.loads(line[-1][7:])
-        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else {key: got} if key.startswith("rates:") else got)
+        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else {key: got} if key.startswith(("rates:", "speed")) else got)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
