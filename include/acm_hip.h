@@ -805,6 +805,61 @@ int  acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batch_item *it
 				    const acm_dense_opts *dense, acm_window_timing *timing);
 
 /* ------------------------------------------------------------------------
+ * Dense crop batches with an overlay (csrc/acm_batch_windows.cpp over csrc/acm_overlay_layout.cpp, kernels:
+ * csrc/acm_dense_overlay.hip): volume perturbation, and a second crop laid over the first at a chosen signal-to-noise ratio, in the
+ * call that makes the batch.  A call of its own beside acm_batch_decode_windows_dense: that call's flags and what it does with them
+ * are untouched.
+ *
+ * The nwin windows, opts and dense mean what they mean to acm_batch_decode_windows_dense - any of its flags, speeds in
+ * wins[k].reserved included - and define nwin SOURCE ROWS S_k of R = frames * channels int16 elements: exactly the int16 rows that
+ * call would write, a row of zeros for a window that delivers nothing or is turned away.  They go into memory of the handle's own,
+ * not into opts->d_pcm.  opts->d_pcm receives nrows OUTPUT ROWS, row r at element r * R, int16 or (ACM_BATCH_PCM_F32) float32;
+ * d_pcm_words >= nrows * R; every element of every output row is written and nothing outside [0, nrows * R).  The layout
+ * (interleaved, or ACM_DENSE_PLANAR) is the sources': the operation is elementwise over the R elements of a row and knows no channels.
+ *
+ * Output row r, with A = S_a, B = S_b, G_MAX = 32768, on unbounded integers:
+ *   SNR mode (b given, snr != 0)        Ea = sum over e < R of A[e]^2, Eb likewise - exact, both channels and the zeros behind a short
+ *                                       crop included;  D = Eb * snr;  g = 0 if D == 0, else min(G_MAX, isqrt((Ea << 40) / D)):
+ *                                       (g / 4096)^2 = Ea / (Eb * snr / 65536), the power ratio a : b that snr (Q16) asks for
+ *   absolute mode (b given, snr == 0)   g = gain
+ *   b == ACM_OVERLAY_NONE               g = 0
+ *   m[e] = 4096 * A[e] + g * B[e]                                     (fits int32: |m| <= 2^27 + 2^30)
+ *   y[e] = clamp((m[e] * vol + 2^23) >> 24, -32768, 32767)            (the product in 64 bits, the shift arithmetic; it saturates)
+ * with vol == 0 meaning 4096; float32 is y * 2^-15 exactly.  vol == 4096 with b == ACM_OVERLAY_NONE is the identity.  a == b is
+ * allowed, and so is a source used by many rows, a source used by none, and rows in any order.
+ *
+ * rows[r].gain (the g that was used), energy_a and energy_b (0 in absolute mode and without b) come back for every row.  wins[k].words
+ * and .status are acm_batch_decode_windows_dense's; dev_off, slot_off and slot_words are 0: nothing of d_pcm belongs to a window.
+ * nrows == 0 writes nothing to d_pcm and returns ACMHIP_OK.
+ *
+ * ACMHIP_ERR_ARG before anything is written: anything acm_batch_decode_windows_dense refuses for these windows and `dense`, with
+ * d_pcm_words checked against nrows * R instead; rows == NULL with nrows > 0; a >= nwin; b >= nwin unless it is ACM_OVERLAY_NONE;
+ * reserved != 0; vol > 65535; gain > 32768 in absolute mode; R >= 2^24 (so Ea << 40 stays below 2^94 and g^2 * D below 2^116).
+ * dev == NULL: ACMHIP_ERR_NO_DEVICE.
+ *
+ * The dense run goes on unchanged up to its gather launch - whichever of its four kernels the call would have picked - which writes
+ * int16 rows into the handle's source arena.  Behind it on the same stream: the energies zeroed, acm_dense_energy over the source
+ * rows some row in SNR mode names (each summed once, integer atomics: reproducible), acm_dense_gains (g of every output row),
+ * acm_dense_overlay over the output rows, and one read-back of 24 bytes a row.  timing->kernel_s spans synthesis through the combine.
+ * ---------------------------------------------------------------------- */
+#define ACM_OVERLAY_NONE 0xFFFFFFFFu
+typedef struct acm_overlay_row {         /* one per OUTPUT row */
+	uint32_t a;                      /* in:  source window, < nwin */
+	uint32_t b;                      /* in:  source window laid over it, or ACM_OVERLAY_NONE */
+	uint32_t vol;                    /* in:  Q12 gain on the sum, 1 .. 65535; 0 means 4096 */
+	uint32_t snr;                    /* in:  power ratio a : b wanted, Q16, 1 .. 2^32-1; 0: `gain` is given (absolute mode) */
+	uint32_t gain;                   /* in (absolute mode): Q12 gain of b, 0 .. 32768;  out: the g that was used, in either mode */
+	uint32_t reserved;               /* 0 */
+	uint64_t energy_a, energy_b;     /* out: the sums of squares g was made from; 0 in absolute mode and for b == ACM_OVERLAY_NONE */
+} acm_overlay_row;
+
+int  acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+				      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+				      acm_overlay_row *rows, size_t nrows, acm_window_timing *timing);
+/* the g of SNR mode from two energies (the formula above on whatever it is given; snr == 0 gives 0).  No device is needed */
+uint32_t acm_dense_overlay_gain(uint64_t energy_a, uint64_t energy_b, uint32_t snr);
+
+/* ------------------------------------------------------------------------
  * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs
  * before its first crop.  acm_index_file parses a whole file to get it, decoding every filler index and dropping it; the device
  * only WALKS the stream (acm_index_scan_wave, csrc/acm_parse.hip: one stream per wavefront, the walk of acm_batch_decode's device

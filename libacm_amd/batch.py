@@ -259,6 +259,81 @@ class GpuDecoder:
         return d_pcm.reshape(-1)[:need].view(shape), delivered, statuses
 
 
+    def crop_overlay(self, files, windows, rows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None):
+        """crop_batch with volume perturbation and an overlay at a signal-to-noise ratio in the same call
+        (acm_batch_decode_windows_overlay).  windows, frames, channels, planar, index, mix, rate and speed are crop_batch's and define
+        the SOURCE rows - what crop_batch would return, kept in memory of the decoder's own.  rows: one Overlay per row of the batch:
+        source row a, scaled by vol_db, with source row b laid over it at snr_db (a's power over b's, measured over the whole rows) or
+        at gain_db.  Sources may be used by many rows, by none, in any order.
+        -> (batch [len(rows), channels, frames] (planar) or [len(rows), frames, channels], gains, frames_delivered, statuses): gains[r]
+        is (g, energy_a, energy_b), the Q12 gain b got and the sums of squares it was made from; frames_delivered and statuses are
+        the WINDOWS', as crop_batch reports them.  The result is defined on integers (include/acm_hip.h), float32 is the int16 result
+        times 2^-15; out as in crop_batch."""
+        torch = self.torch
+        files = [_load(f) for f in files]
+        if index is None:
+            index = self.build_index(files)
+        n, nr = len(windows), len(rows)
+        per = [channels] * n
+        if mix:
+            own = self._header_channels(files, index)
+            per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
+        if speed is not None and rate is None:
+            raise ValueError("GpuDecoder.crop_overlay: speed needs rate")
+        if rate is not None:
+            rates = self._header_rates(files, index)
+        shape = (nr, channels, frames) if planar else (nr, frames, channels)
+        need = nr * channels * frames
+        if out is not None and out.dtype != self.dtype:
+            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
+        fits = out is not None and out.numel() >= need and out.is_contiguous()
+        d_pcm = out if fits else torch.empty(max(need, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
+        torch.cuda.current_stream().synchronize()
+        # the row table in one piece: an Overlay has made its record when it was built
+        table = np.zeros(nr, dtype=capi.OVERLAY_ROW_DT)
+        if nr:
+            table.view(np.uint32).reshape(nr, -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
+        statuses, words, _, gains, self.timing = capi.batch_decode_windows_overlay(
+            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], table,
+            d_pcm.data_ptr(), d_pcm.numel(), frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse,
+            f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed)
+        delivered = [w // c for w, c in zip(words, per)]
+        if speed is not None:
+            delivered = [capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1)) if d else 0 for d, w, sp in zip(delivered, windows, speed)]
+        elif rate is not None:
+            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
+        return d_pcm.reshape(-1)[:need].view(shape), gains, delivered, statuses
+
+
+def snr_q16(db):
+    """a signal-to-noise ratio in dB as acm_overlay_row.snr: the power ratio in Q16, 1 .. 2^32 - 1"""
+    return min(max(int(round(65536 * 10 ** (db / 10))), 1), 2 ** 32 - 1)
+
+
+def gain_q12(db, lo=0, hi=capi.OVERLAY_G_MAX):
+    """an amplitude gain in dB in Q12, clamped to [lo, hi]: [0, 32768] for the row laid over, [1, 65535] for a row's volume"""
+    return min(max(int(round(4096 * 10 ** (db / 20))), lo), hi)
+
+
+class Overlay:
+    """one row of GpuDecoder.crop_overlay: source row a, with source row b (None: nothing) laid over it - at snr_db, the ratio of a's
+    power to b's in dB, or at gain_db, b's own gain in dB; exactly one of the two with b - and the sum scaled by vol_db"""
+
+    def __init__(self, a, b=None, snr_db=None, gain_db=None, vol_db=0.0):
+        if b is None and (snr_db is not None or gain_db is not None):
+            raise ValueError("Overlay: snr_db and gain_db belong to b")
+        if b is not None and (snr_db is None) == (gain_db is None):
+            raise ValueError("Overlay: exactly one of snr_db and gain_db with b")
+        self.a, self.b, self.snr_db, self.gain_db, self.vol_db = a, b, snr_db, gain_db, vol_db
+        # (a, b, vol, snr, gain) as acm_overlay_row holds them: made once, here, so that a call over many rows converts nothing
+        self.raw = (a, capi.OVERLAY_NONE if b is None else b, gain_q12(vol_db, 1, 65535), snr_q16(snr_db) if snr_db is not None else 0,
+                    gain_q12(gain_db) if gain_db is not None else 0)
+
+    def record(self):
+        """(a, b, vol, snr, gain) of acm_overlay_row, b None where nothing is laid over the row"""
+        return (self.raw[0], self.b) + self.raw[2:]
+
+
 def source_frames(frames, rate_in, rate_out, speed=(1, 1)):
     """the longest window, in frames of a file at rate_in played at speed = (num, den), whose crop fits a row of `frames` frames at
     rate_out (crop_batch(rate=rate_out, speed=...)): frames * M // L"""

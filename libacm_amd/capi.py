@@ -153,6 +153,17 @@ class DenseSpeedInfo(C.Structure):
 SPEED_KINDS = ("none", "exact", "wide")
 
 
+class OverlayRow(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("vol", C.c_uint32), ("snr", C.c_uint32), ("gain", C.c_uint32), ("reserved", C.c_uint32),
+                ("energy_a", C.c_uint64), ("energy_b", C.c_uint64)]
+
+
+OVERLAY_ROW_DT = np.dtype([("a", "<u4"), ("b", "<u4"), ("vol", "<u4"), ("snr", "<u4"), ("gain", "<u4"), ("reserved", "<u4"),
+                           ("energy_a", "<u8"), ("energy_b", "<u8")])          # acm_overlay_row as a numpy record: a table of many rows at once
+OVERLAY_NONE = 0xFFFFFFFF       # OverlayRow.b: nothing is laid over the row
+OVERLAY_G_MAX = 32768           # the largest Q12 gain of b
+
+
 class BatchIndexOut(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("max_blocks", C.c_size_t), ("blocks", C.c_uint32), ("end_status", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_uint32)]
@@ -181,6 +192,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
     "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
+    "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info",
 ]
@@ -286,6 +298,11 @@ def lib():
         L.acm_dense_speed_frames.argtypes = [C.c_uint64] + [C.c_uint32] * 4
         L.acm_dense_speed_frames.restype = C.c_uint64
         L.acm_dense_speed_taps.argtypes = [C.c_uint32] * 4 + [C.POINTER(DenseSpeedInfo), vp, sz]
+    if hasattr(L, "acm_batch_decode_windows_overlay"):
+        L.acm_batch_decode_windows_overlay.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                                       C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(OverlayRow), sz, C.POINTER(WindowTiming)]
+        L.acm_dense_overlay_gain.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.acm_dense_overlay_gain.restype = C.c_uint32
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -1167,6 +1184,53 @@ def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, f
     if check:
         _check(rc, "acm_batch_decode_windows_dense")
     res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)], tm)
+    return res if check else res + (rc,)
+
+
+def dense_overlay_gain(energy_a, energy_b, snr):
+    """acm_dense_overlay_gain: the Q12 gain of b that makes the power ratio a : b what snr (Q16) asks for, from the rows' sums of squares"""
+    return int(lib().acm_dense_overlay_gain(energy_a, energy_b, snr))
+
+
+def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
+                                 fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
+                                 check=True, mix=False, rate=None, speeds=None, nrows=None):
+    """acm_batch_decode_windows_overlay: the windows are the SOURCE rows of batch_decode_windows_dense (every argument it has means the
+    same), and d_pcm receives len(rows) output rows of frames * channels samples, row r at sample r * frames * channels.  rows: tuples
+    (a, b, vol, snr, gain) of acm_overlay_row's inputs - b None for ACM_OVERLAY_NONE - or 6-tuples that end in `reserved`, or an array
+    of OVERLAY_ROW_DT records (a large batch: nothing is done row by row here; it is not written into); None for no row table at all
+    (tests of the refusals: nrows is then what the call is told).  Returns (statuses, words, offsets, gains, WindowTiming): statuses and words are the windows', offsets their
+    (dev_off, slot_off, slot_words), gains (g, energy_a, energy_b) per output row.  check=False: the return code as a sixth element
+    instead of an exception."""
+    bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
+    nw = len(windows)
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
+    if dense_flags is None:
+        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
+            (DENSE_SPEED if speeds is not None else 0)
+    for k, sp in enumerate(speeds or ()):
+        if sp is not None:
+            wins[k].reserved = sp[0] << 16 | sp[1]
+    dense = None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
+    nr = len(rows) if rows is not None else 0
+    if isinstance(rows, np.ndarray):
+        table = np.array(rows, dtype=OVERLAY_ROW_DT, ndmin=1)
+    else:
+        table = np.zeros(max(nr, 1), dtype=OVERLAY_ROW_DT)
+        for r in range(nr):
+            a, b, vol, snr, gain = rows[r][:5]
+            table[r] = (a, OVERLAY_NONE if b is None else b, vol, snr, gain, rows[r][5] if len(rows[r]) > 5 else 0, 0, 0)
+    tm = WindowTiming()
+    _fill(dev)
+    rc = lib().acm_batch_decode_windows_overlay(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
+                                                C.byref(dense) if dense is not None else None,
+                                                C.cast(table.ctypes.data, C.POINTER(OverlayRow)) if rows is not None else None,
+                                                nr if nrows is None else nrows, C.byref(tm))
+    if check:
+        _check(rc, "acm_batch_decode_windows_overlay")
+    res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)],
+           [(int(wins[k].dev_off), int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)],
+           list(zip(table["gain"][:nr].tolist(), table["energy_a"][:nr].tolist(), table["energy_b"][:nr].tolist())), tm)
     return res if check else res + (rc,)
 
 

@@ -21,6 +21,10 @@
  * of the table converts between mono and stereo: then the launch is acm_dense_mixed's (acm_dense_mix.hip) instead - and whether, with
  * ACM_DENSE_RESAMPLE, a row is filtered to the batch's sample rate: then a second table and the ratios' taps travel with the first and
  * the launch is acm_dense_resample's (acm_dense_resample.hip).
+ *
+ * acm_batch_decode_windows_overlay is the dense run with its gather launch aimed at the handle's source arena instead of the caller's
+ * tensor, and two launches of acm_dense_overlay.hip behind it that make the caller's rows from those: which source rows get an
+ * energy and where the tables sit is acm_overlay_layout.cpp's.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -31,6 +35,7 @@
 #include "acm_dense_layout.h"
 #include "acm_device.h"
 #include "acm_hip.h"
+#include "acm_overlay_layout.h"
 #include "acm_stage.h"
 #include "acm_window_layout.h"
 #include "libacm.h"
@@ -45,9 +50,9 @@ class WinRun {
 public:
 	WinRun(acmhip_device *dev_, const acm_batch_item *items_, acm_batch_window *wins_, const acm_batch_opts &opts_,
 	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseLayout *dense_ = nullptr,
-	       void *dense_out_ = nullptr)
+	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr)
 		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), dense(dense_), dense_out(dense_out_),
-		  st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
+		  overlay(overlay_), overlay_rows(overlay_rows_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
 		  pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
 	{
 		for (size_t k : L.act)
@@ -75,8 +80,14 @@ private:
 	void stage_on_host(const std::vector<size_t> &ids);
 	int upload_slices(const std::vector<size_t> &ids);
 	void collect(PlanStreams &ps);
-	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, and behind them a dense call's row table */
-	size_t jobs_bytes() const { return dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes(); }
+	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, behind them a dense call's row table, and behind that an
+	 * overlay call's tables */
+	size_t overlay_off() const { return (size_t)round_up(dense->table_off(L) + dense->table_bytes(), 64); }
+	size_t jobs_bytes() const
+	{
+		return overlay ? overlay_off() + overlay->table_bytes() : dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes();
+	}
+	int combine_rows();
 
 	ArenaLock lock;
 	acmhip_device *const dev;
@@ -89,6 +100,8 @@ private:
 	acm_window_timing &tm;
 	const DenseLayout *const dense;         /* a dense call (then opts are its inner ones: int16 rows, no caller memory), else null */
 	void *const dense_out;                  /* ... and its output tensor */
+	const OverlayLayout *const overlay;     /* an overlay call (a dense call whose rows go to the source arena), else null */
+	acm_overlay_row *const overlay_rows;    /* ... and the caller's row table, for what comes back */
 	const hipStream_t st;
 	const bool out_f32, keep_on_device;
 	const size_t pcm_unit;
@@ -101,6 +114,7 @@ private:
 	acmhip_blkhdr *h_hdr = nullptr, *d_hdr = nullptr;
 	uint8_t *h_files = nullptr, *d_files = nullptr, *h_jobs = nullptr, *d_jobs = nullptr;
 	uint32_t *d_colpos = nullptr;
+	int16_t *d_src = nullptr;               /* the source rows of an overlay call */
 };
 
 /* Arenas (they live in the device handle and are reused by the next call) and events.  Needs nothing but the layout */
@@ -125,6 +139,8 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 	}
 	if (dense)              /* the intermediate PCM; a call without a window to decode still writes every row */
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, dense->pcm_arena_words(L.pcm_total) * sizeof(int16_t), (void **)&d_pcm));
+	if (overlay)
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_SRC, overlay->src_arena_words() * sizeof(int16_t), (void **)&d_src));
 	if (dense || !L.dev_ids.empty()) {
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes(), (void **)&h_jobs));
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes(), (void **)&d_jobs));
@@ -308,29 +324,74 @@ int WinRun::synthesise_and_gather()
 	const size_t bytes = filters ? dense->table_bytes() : dense->row_table_bytes();
 	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
 	tm.h2d_bytes += bytes;
+	if (overlay && overlay->upload_bytes()) {
+		uint8_t *up = h_jobs + overlay_off();
+		memcpy(up, overlay->rows.data(), overlay->rows_bytes());
+		memcpy(up + overlay->marked_off(), overlay->marked.data(), overlay->marked.size() * sizeof(uint32_t));
+		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + overlay_off(), up, overlay->upload_bytes(), hipMemcpyHostToDevice, st));
+		tm.h2d_bytes += overlay->upload_bytes();
+	}
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
 	const AcmDenseRow *d_rows = reinterpret_cast<const AcmDenseRow *>(d_jobs + at);
 	const void *d_second = d_jobs + at + dense->resample_off();
 	const int16_t *d_taps = reinterpret_cast<const int16_t *>(d_jobs + at + dense->taps_off());
-	const int e = wide ? acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), dense_out,
-						     dense->frames, dense->channels, dense->planar, dense->f32, st)
-		      : filters ? acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), dense_out,
-							     dense->frames, dense->channels, dense->planar, dense->f32, st)
-				: (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), dense_out, dense->frames,
-											     dense->channels, dense->planar, dense->f32, st);
+	/* an overlay call: the same launch writes the source rows, int16, and the caller's tensor is combine_rows' */
+	void *const rows_out = overlay ? d_src : dense_out;
+	const bool rows_f32 = overlay ? false : dense->f32;
+	const int e = wide ? acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out,
+						     dense->frames, dense->channels, dense->planar, rows_f32, st)
+		      : filters ? acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out,
+							     dense->frames, dense->channels, dense->planar, rows_f32, st)
+				: (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames,
+											     dense->channels, dense->planar, rows_f32, st);
 	if (e != 0)
 		return acmhip_report_hip(e, wide ? "acmk_launch_dense_speed" : filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed"
 													      : "acmk_launch_dense_rows");
+	if (overlay)
+		ACM_TRY(combine_rows());
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
+	const bool results = overlay && !overlay->rows.empty();
+	const size_t res_at = results ? overlay_off() + overlay->result_off() : 0;
+	if (results) {
+		ACM_HIP_TRY(hipEventRecord(ev[4], st));
+		ACM_HIP_TRY(hipMemcpyAsync(h_jobs + res_at, d_jobs + res_at, overlay->result_bytes(), hipMemcpyDeviceToHost, st));
+		ACM_HIP_TRY(hipEventRecord(ev[5], st));
+	}
 	ACM_HIP_TRY(hipStreamSynchronize(st));
 	float ms = 0;
 	if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
 		tm.h2d_s = ms * 1e-3;
 	if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
 		tm.kernel_s = ms * 1e-3;
+	if (results) {
+		if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
+			tm.d2h_s = ms * 1e-3;
+		const AcmOverlayResult *res = reinterpret_cast<const AcmOverlayResult *>(h_jobs + res_at);
+		for (size_t r = 0; r < overlay->rows.size(); r++)
+			acm_overlay_report(res[r], &overlay_rows[r]);
+	}
 	return ACMHIP_OK;
+}
+
+/* an overlay call, behind the gather launch that wrote the source rows: the row table and the list of rows to sum went up with the
+ * dense tables; the energies are zeroed and summed, and the combine launch writes the caller's tensor and a result per row */
+int WinRun::combine_rows()
+{
+	const size_t at = overlay_off();
+	uint64_t *d_energy = reinterpret_cast<uint64_t *>(d_jobs + at + overlay->energy_off());
+	if (!overlay->marked.empty()) {
+		ACM_HIP_TRY(hipMemsetAsync(d_energy, 0, overlay->energy_bytes(), st));
+		const int e = acmk_launch_dense_energy(d_src, reinterpret_cast<const uint32_t *>(d_jobs + at + overlay->marked_off()), overlay->marked.size(),
+						       overlay->row_words, d_energy, st);
+		if (e != 0)
+			return acmhip_report_hip(e, "acmk_launch_dense_energy");
+	}
+	const int e = acmk_launch_dense_overlay(d_src, reinterpret_cast<const AcmOverlayRow *>(d_jobs + at), d_energy,
+						reinterpret_cast<AcmOverlayResult *>(d_jobs + at + overlay->result_off()), overlay->rows.size(), dense_out,
+						overlay->row_words, dense->f32, st);
+	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_overlay") : ACMHIP_OK;
 }
 
 /* headers, and whether every index is one its file can have - before anything derived from it is used */
@@ -424,9 +485,11 @@ static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_
 	return run.synthesise_and_deliver();
 }
 
-/* the dense call without its wall clock */
+/* the dense call without its wall clock; with_overlay: acm_batch_decode_windows_overlay - the windows are the sources of the nrows rows of
+ * `rows`, which are what opts->d_pcm receives */
 static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
-				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm)
+				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm, bool with_overlay = false,
+				acm_overlay_row *rows = nullptr, size_t nrows = 0)
 {
 	if (!dev)
 		return ACMHIP_ERR_NO_DEVICE;
@@ -440,20 +503,32 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 
 	const std::vector<WindowItem> its = probe_items(pool, items, n, index, opts.force_chans);
 	DenseLayout D;
-	if (acm_dense_prepare(its.data(), n, wins, nwin, opts, dense, &D) != ACMHIP_OK) {
+	/* the room behind d_pcm is measured against the output rows of an overlay call, by its own layout */
+	acm_batch_opts asked = opts;
+	if (with_overlay)
+		asked.d_pcm_words = ~0ull;
+	if (acm_dense_prepare(its.data(), n, wins, nwin, asked, dense, &D) != ACMHIP_OK) {
 		acmhip_set_error_text("acm_batch_decode_windows_dense: a call the dense writer does not take (include/acm_hip.h)");
+		return ACMHIP_ERR_ARG;
+	}
+	OverlayLayout O;
+	if (with_overlay && acm_overlay_prepare(rows, nrows, nwin, D.row_words, opts.d_pcm_words, &O) != ACMHIP_OK) {
+		acmhip_set_error_text("acm_batch_decode_windows_overlay: a row table the call does not take (include/acm_hip.h)");
 		return ACMHIP_ERR_ARG;
 	}
 	WindowLayout layout;
 	ACM_TRY(acm_window_layout(its.data(), n, D.wins.data(), nwin, D.inner, &layout, &pool));
-	for (size_t k = 0; k < nwin; k++)
+	for (size_t k = 0; k < nwin; k++) {
 		acm_dense_report(D, layout.slots[k], k, &wins[k]);
+		if (with_overlay)               /* nothing of d_pcm belongs to a window */
+			wins[k].dev_off = wins[k].slot_off = wins[k].slot_words = 0;
+	}
 	tm.blocks_parsed = layout.blocks_parsed;
 	if (!nwin)
 		return ACMHIP_OK;
 
 	const auto t_hdr = clk::now();
-	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm);
+	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows);
 	ACM_TRY(run.fetch_arenas(t_hdr));
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
@@ -467,6 +542,19 @@ extern "C" int acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batc
 	acm_window_timing tm{};
 	const auto t0 = clk::now();
 	ACM_TRY(decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm));
+	tm.total_s = secs(t0, clk::now());
+	if (timing)
+		*timing = tm;
+	return ACMHIP_OK;
+}
+
+extern "C" int acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+						acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
+						acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
+{
+	acm_window_timing tm{};
+	const auto t0 = clk::now();
+	ACM_TRY(decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows));
 	tm.total_s = secs(t0, clk::now());
 	if (timing)
 		*timing = tm;

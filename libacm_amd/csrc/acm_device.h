@@ -134,6 +134,16 @@ struct AcmSpeedRow {
 	uint64_t step;
 	uint32_t b, wide;
 };
+/* acm_batch_decode_windows_overlay (acm_dense_overlay.hip): output row r is source row a of the source arena, with source row b laid
+ * over it (b == ACM_OVERLAY_NONE: nothing is) and the sum scaled by vol (Q12, never 0 here).  snr != 0: b's gain is made from the
+ * two rows' energies (include/acm_hip.h), else it is `gain` */
+struct AcmOverlayRow {
+	uint32_t a, b, vol, snr, gain, pad;
+};
+/* ... and what the combine launch leaves per output row: the gain used and the energies it was made from (0 where none was) */
+struct AcmOverlayResult {
+	uint64_t gain, energy_a, energy_b;
+};
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -175,6 +185,7 @@ enum {
 	ACM_ARENA_D_PKBLOB, ACM_ARENA_D_PKCHUNK, ACM_ARENA_D_BLKOFF,
 	ACM_ARENA_D_MARKS, ACM_ARENA_H_MARKS,           /* the marks of a batch index build's two groups (acm_batch_index.cpp), or of a decode that hands
 	                                                   the index out (acm_batch_decode_indexed: hdr_total of them), on the device and pinned */
+	ACM_ARENA_D_SRC,                                /* the source rows of acm_batch_decode_windows_overlay: int16 PCM, nwin rows of a dense call */
 	ACM_ARENA_SLOTS
 };
 /* is this slot pinned host memory (else device memory)? */
@@ -342,6 +353,16 @@ int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRow *d_rows, 
  * and wide tables of the call, 16-byte aligned.  The same demands on d_src and d_out */
 int acmk_launch_dense_speed(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmSpeedRow *d_sp, const int16_t *d_taps, uint64_t nrows,
 			    void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
+/* acm_dense_overlay.hip, behind a dense launch that wrote source row k to d_src + k * row_len (int16; d_src 16-byte aligned, 8 samples
+ * of memory behind the last row).  The energy launch adds the sum of squares of every row d_marked names (each once) to
+ * d_energy[that row], which the caller has zeroed: one 64-bit atomic add per workgroup, of integers, so the sums do not depend on the
+ * order of arrival.  The combine call writes d_res[r] - the gain of every row, from the energies, by a small launch of its own - and
+ * then nrows rows of row_len samples to d_out (int16, or float32 = the int16 result times 2^-15 with f32), row r at element
+ * r * row_len, by include/acm_hip.h's formula.  Both calls: nothing allocated, nothing waited for; the same kind of loads as
+ * acmk_launch_dense_rows */
+int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_marked, uint64_t nmarked, uint64_t row_len, uint64_t *d_energy, void *stream);
+int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayRow *d_rows, const uint64_t *d_energy, AcmOverlayResult *d_res, uint64_t nrows,
+			      void *d_out, uint64_t row_len, int f32, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,16 @@ runs out of time ends the probe.
   With --step kernel --speed the trace holds, call after call, batches of ONE speed - 1/1 (acm_dense_resample, K = 24), 9/10
   (acm_dense_speed, K = 22), 11/10 (K = 26) - and the batch of thirds.
 
-    python profiles/dense_crop_probe.py [--mix | --rates | --speed] [--windows 1024,16384] [--out probe_out/dense_crop.json]
+  --overlay (profiles/dense_overlay_notes.txt): acm_batch_decode_windows_overlay.  N speech + N noise one-second crops of the default
+  workload's streams into N float32 rows at 10 dB.
+    overlay:<n>   crop_overlay (one call); crop_overlay of 2N identity rows; crop_batch of the 2N rows; crop_batch + the torch assembly
+                  (energies, gain, add, clamp - the noise rows are a slice of the batch, so the assembly pays no gather), alternating.
+                  With --parent-lib the last two also on the parent commit's library, a process of its own.  The one call and the
+                  torch way are compared within float, not byte for byte.
+  With --step kernel --overlay the trace holds the gather launch into the source arena (acm_dense_rows), acm_dense_energy and
+  acm_dense_overlay; the step prints the bytes each moves and the box's copy kernel over the same byte counts.
+
+    python profiles/dense_crop_probe.py [--mix | --rates | --speed | --overlay] [--windows 1024,16384] [--out probe_out/dense_crop.json]
 """
 import argparse
 import ctypes as C
@@ -434,6 +443,115 @@ def step_kernel_speed(args):
     return out
 
 
+SNR_DB = 10.0
+
+
+def overlay_windows(args, n):
+    """n speech and n noise one-second crops of the default workload's streams: windows [0, n) and [n, 2n)"""
+    import numpy as np
+    rng = np.random.default_rng(22054)
+    total = args.blocks * args.rows << args.level
+    return [(int(rng.integers(0, args.streams)), int(rng.integers(0, total - FRAMES)), FRAMES) for k in range(2 * n)]
+
+
+def step_overlay(args, n):
+    """n speech + n noise crops into n float32 rows at 10 dB.  On this tree's library: crop_overlay (one call), crop_overlay of 2n
+    identity rows, crop_batch of the 2n rows, and crop_batch + the torch assembly (energies, gain, add, clamp; the noise rows are a
+    slice, so no gather is paid), alternating.  On the library ACM_HIP_LIB names where it has no overlay call (the parent commit's):
+    crop_batch of the 2n rows, and crop_batch + the torch assembly"""
+    import numpy as np
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    wins = overlay_windows(args, n)
+    buf2 = torch.empty(2 * n * FRAMES, dtype=dec.dtype, device="cuda:0")
+    buf1 = torch.empty(n * FRAMES, dtype=dec.dtype, device="cuda:0")
+    keep, ev = {}, {}
+    ratio = 10.0 ** (SNR_DB / 10)
+
+    def note(name):
+        ev.setdefault(name, []).append(dec.timing.kernel_s)
+
+    def dense_2n():
+        keep["x"], _, keep["st"] = dec.crop_batch(files, wins, FRAMES, channels=1, planar=True, index=index, out=buf2)
+        note("crop_batch_2n")
+
+    def torch_way():
+        x, _, _ = dec.crop_batch(files, wins, FRAMES, channels=1, planar=True, index=index, out=buf2)
+        note("crop_batch_2n_then_torch")
+        a, b = x[:n], x[n:]
+        ea, eb = a.square().sum(dim=(1, 2)), b.square().sum(dim=(1, 2))
+        g = torch.where(eb > 0, torch.sqrt(ea / (eb * ratio).clamp_(min=1e-30)), torch.zeros_like(ea)).clamp_(max=8.0)
+        keep["t"] = torch.addcmul(a, b, g[:, None, None]).clamp_(-1.0, 32767.0 / 32768.0)
+
+    variants = [("crop_batch_2n", dense_2n), ("crop_batch_2n_then_torch", torch_way)]
+    if hasattr(capi.lib(), "acm_batch_decode_windows_overlay"):
+        rows = [batch.Overlay(k, b=n + k, snr_db=SNR_DB) for k in range(n)]
+        ident = [batch.Overlay(k) for k in range(2 * n)]
+
+        def one_call():
+            keep["o"], keep["gains"], _, keep["st_o"] = dec.crop_overlay(files, wins, rows, FRAMES, channels=1, planar=True, index=index, out=buf1)
+            note("crop_overlay")
+
+        def identity():
+            keep["i"], _, _, _ = dec.crop_overlay(files, wins, ident, FRAMES, channels=1, planar=True, index=index, out=buf2)
+            note("crop_overlay_identity_2n")
+        variants += [("crop_overlay", one_call), ("crop_overlay_identity_2n", identity)]
+    res = dict(library=os.environ.get("ACM_HIP_LIB", "shipped"), call_wall=timed(variants, args),
+               events={k: stats(v[args.warmup:]) for k, v in ev.items()}, ok=all(s == 0 for s in keep["st"]))
+    if "o" in keep:
+        a, b = res["call_wall"]["crop_overlay"], res["call_wall"]["crop_batch_2n_then_torch"]
+        pair = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+        diff = (keep["o"] - keep["t"]).abs()
+        res["one_call_against_torch_same_library"] = dict(
+            margin_ms=round(b["min_ms"] - a["max_ms"], 3), spread_of_the_two_compared_ms=round(pair, 3), one_call_wins=bool(b["min_ms"] - a["max_ms"] > pair),
+            max_abs_difference_lsb=round(float(diff.max()) * 32768, 3), rows_with_a_gain=int(sum(1 for g in keep["gains"] if g[0])),
+            median_gain_q12=int(np.median([g[0] for g in keep["gains"]])))
+        dec.crop_batch(files, wins, FRAMES, channels=1, planar=True, index=index, out=buf2)
+        x = buf2.clone()
+        dec.crop_overlay(files, wins, ident, FRAMES, channels=1, planar=True, index=index, out=buf2)
+        res["identity_equals_crop_batch"] = bool(torch.equal(x, buf2))
+    dec.dev.close()
+    return res
+
+
+def step_kernel_overlay(args):
+    """REPS calls of crop_overlay per shape - n rows at 10 dB over 2n sources - so that the trace holds the launches' own durations:
+    the gather launch into the source arena (acm_dense_rows), acm_dense_energy and acm_dense_overlay; beside them the bytes each moves
+    (from the shapes) and the box's copy kernel over the same byte counts"""
+    import torch
+    from libacm_amd import batch, capi
+    files = make_files(args)
+    cb = C.CDLL(os.path.join(ROOT, "profiles", "ubench", "libcopybw.so"))
+    cb.acm_copy_ceiling_gbs.restype = C.c_double
+    cb.acm_copy_ceiling_gbs.argtypes = [C.c_size_t, C.c_char_p, C.c_size_t]
+    dec = batch.GpuDecoder(0, parse=capi.PARSE_AUTO, dtype=torch.float32)
+    index = dec.build_index(files)
+    out = {}
+    for n in args.windows:
+        wins = overlay_windows(args, n)
+        rows = [batch.Overlay(k, b=n + k, snr_db=SNR_DB) for k in range(n)]
+        buf = torch.empty(n * FRAMES, dtype=dec.dtype, device="cuda:0")
+        k_ms = []
+        for r in range(args.warmup + args.reps):
+            dec.crop_overlay(files, wins, rows, FRAMES, channels=1, planar=True, index=index, out=buf)
+            if r >= args.warmup:
+                k_ms.append(dec.timing.kernel_s)
+        moved = dict(acm_dense_rows=(2 + 2) * 2 * n * FRAMES, acm_dense_energy=2 * 2 * n * FRAMES, acm_dense_overlay=(2 + 2 + 4) * n * FRAMES)
+        res = dict(synthesis_through_combine_events=stats(k_ms), calls=args.reps + args.warmup)
+        for name, nbytes in moved.items():
+            label = C.create_string_buffer(96)
+            gbs = cb.acm_copy_ceiling_gbs(nbytes // 2 // 4096 * 4096, label, 96)
+            res[name] = dict(bytes_moved=int(nbytes), copy_kernel_gbs_same_bytes=round(gbs, 1),
+                             copy_kernel_ms_same_bytes=round(nbytes / gbs / 1e6, 4) if gbs > 0 else None)
+        out["%d_rows" % n] = res
+        del buf
+    dec.dev.close()
+    return out
+
+
 def step_kernel_mix(args):
     """REPS calls per shape of the mixed batch (acm_dense_mixed) and of a batch over the files of one channel count (acm_dense_rows): the
     launch's own durations are the trace's; the call's wall clock and event time are printed here"""
@@ -519,13 +637,20 @@ def main():
     ap.add_argument("--speed", action="store_true", help="ACM_DENSE_SPEED: the flag with every speed 1/1 against the call without it, and a batch of "
                     "three speeds in one call against three calls + index_copy and against the rate=-only call (with --parent-lib also on "
                     "the parent commit's library)")
+    ap.add_argument("--overlay", action="store_true", help="acm_batch_decode_windows_overlay: n speech + n noise crops into n rows at 10 dB in one "
+                    "call against crop_batch + the torch assembly, and an identity-only call against crop_batch (with --parent-lib the torch "
+                    "way and crop_batch also on the parent commit's library)")
     ap.add_argument("--parent-lib", help="with --mix: the parent commit's libacm_hip.so; adds, per shape, a batch of one channel count on that "
                     "library and on this tree's without and with the flag (each library a child process of its own)")
     ap.add_argument("--step", help="(internal) compare:<windows>:<f32 0|1>, mix:<windows>:<f32>:<channels>, or kernel: run one step in this "
                     "process and print its JSON")
     args = ap.parse_args()
     if args.step:
-        if args.step == "kernel" and args.speed:
+        if args.step == "kernel" and args.overlay:
+            res = step_kernel_overlay(args)
+        elif args.step.startswith("overlay:"):
+            res = step_overlay(args, int(args.step.split(":")[1]))
+        elif args.step == "kernel" and args.speed:
             res = step_kernel_speed(args)
         elif args.step.startswith("speedflag:"):
             res = step_speed_flag(args, int(args.step.split(":")[1]))
@@ -558,15 +683,17 @@ def main():
         steps += ["rates:%d:0:parent" % n for n in args.windows if args.parent_lib]
     if args.speed:
         steps = ["%s:%d:%s" % (what, n, lib) for n in args.windows for what in ("speedflag", "speedmix") for lib in ("tree", "parent")[:2 if args.parent_lib else 1]]
+    if args.overlay:
+        steps = ["overlay:%d:%s" % (n, lib) for n in args.windows for lib in ("tree", "parent")[:2 if args.parent_lib else 1]]
     if args.mix and args.parent_lib:
         steps += ["flag:%d:%d:%d:%s" % (n, f32, ch, lib) for n in args.windows for f32 in (1, 0) for ch in (1, 2) for lib in ("parent", "tree")]
     for step in steps:
         env = dict(os.environ)
         if step.endswith(":parent"):
             env["ACM_HIP_LIB"] = os.path.abspath(args.parent_lib)
-        key, step = step, step.rsplit(":", 1)[0] if step.startswith(("flag:", "rates:", "speedflag:", "speedmix:")) else step
+        key, step = step, step.rsplit(":", 1)[0] if step.startswith(("flag:", "rates:", "speedflag:", "speedmix:", "overlay:")) else step
         cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--host-index-max", str(args.host_index_max)] + ["--mix"] * args.mix + \
-              ["--rates"] * args.rates + ["--speed"] * args.speed + \
+              ["--rates"] * args.rates + ["--speed"] * args.speed + ["--overlay"] * args.overlay + \
               [a for k in ("streams", "level", "rows", "blocks", "warmup", "reps") for a in ("--" + k, str(getattr(args, k)))]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.step_seconds, env=env)
@@ -578,7 +705,7 @@ def main():
             print("step %s failed (%d): nothing more is started\n%s" % (step, r.returncode, r.stdout[-3000:]))
             return 1
         got = json.loads(line[-1][7:])
-        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else {key: got} if key.startswith(("rates:", "speed")) else got)
+        result.update({"one_count_" + key[5:]: got} if key.startswith("flag:") else {key: got} if key.startswith(("rates:", "speed", "overlay:")) else got)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
