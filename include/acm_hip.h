@@ -78,7 +78,8 @@ typedef struct acmhip_patch {
  */
 typedef struct acmhip_stream_desc {
 	uint64_t idx_off;        /* int16 units from d_idx to staged row 0; multiple of 8 */
-	uint64_t hdr_off;        /* acmhip_blkhdr units from d_hdr to the header of block 0 */
+	uint64_t hdr_off;        /* acmhip_blkhdr units from d_hdr to the header of block 0.  Header indices are 32 bits wide in the launch
+				  * tables: hdr_off + the stream's blocks (ceil(nrows / rows)) <= 2^32, or plan creation returns ACMHIP_ERR_ARG */
 	uint64_t pcm_off;        /* int16 units from d_pcm to where sample (row_begin, 0) goes; multiple of 8 */
 	uint64_t n_emit;         /* samples to write, starting at row_begin*cols (<= (nrows-row_begin)*cols) */
 	uint32_t level;          /* acm_level 0..15 */
@@ -216,7 +217,11 @@ typedef struct acmhip_packed_chunk {
 typedef struct acmhip_packed_stream {
 	uint64_t chunk_off;      /* ACMHIP_FORM_PACKED: the chunk-table entry the stream's first tile starts at (tile k: chunk_off + k * slots
 				  * of its level);  ACMHIP_FORM_BYTEPLANE: the pair-table entry of the pair of zeros in front of the stream
-				  * (acmhip_mform_rows) */
+				  * (acmhip_mform_rows).  The packed chunk table is indexed in 64 bits (its records' blob_off16: a blob
+				  * below 64 GB).  The byte-plane kernels index the pair table in 32 bits: chunk_off + the stream's entries
+				  * (ntiles * acmhip_mform_tile_rows(level) / 2 + 1) + the table's 32 entries of read slack
+				  * (acmhip_plan_bind_mform) <= 2^32, or plan creation returns ACMHIP_ERR_ARG; an entry reaches 64 GB of
+				  * byte-plane arena (30 bits of 64-byte units) */
 	uint32_t ntiles;         /* 0: this stream has no second staged form */
 	uint32_t form;           /* ACMHIP_FORM_* */
 } acmhip_packed_stream;

@@ -11,6 +11,10 @@
 #include "acm_plan_cut.h"
 
 #define ACM_K1_DEFAULT_VARIANT 0
+/* AcmTile2.hdr_blk is 32 bits wide, and the byte-plane kernels index the pair table in 32 bits (and fetch whole groups of entries: the
+ * table's 32 entries of read slack): header and pair-table indices end below 2^32 (include/acm_hip.h: hdr_off, chunk_off) */
+#define ACM_TABLE_INDEX_END (1ull << 32)
+#define ACM_PAIR_READ_SLACK 32u
 
 namespace {
 
@@ -461,6 +465,24 @@ int Cutter::cut_stream(size_t i)
 			i, s.level, s.rows, s.nrows, s.row_begin, (unsigned long long)s.n_emit,
 			(unsigned long long)s.idx_off, (unsigned long long)s.pcm_off);
 		return ACMHIP_ERR_ARG;
+	}
+	/* the lean records name a block header and (byte-plane form) a pair-table entry in 32 bits: a stream whose last header, or whose
+	 * last pair entry with the table's read slack behind it, does not fit is refused here, whatever kernel family it would go to -
+	 * never wrapped */
+	const uint64_t blocks = ((uint64_t)s.nrows + s.rows - 1) / s.rows;
+	if (s.hdr_off > ACM_TABLE_INDEX_END - blocks) {
+		set_err("stream %zu: hdr_off %llu + %llu blocks is past header %llu, the last a launch can name", i, (unsigned long long)s.hdr_off,
+			(unsigned long long)blocks, (unsigned long long)(ACM_TABLE_INDEX_END - 1));
+		return ACMHIP_ERR_ARG;
+	}
+	if (packed && packed[i].ntiles && packed[i].form == ACMHIP_FORM_BYTEPLANE) {
+		const uint64_t entries = (uint64_t)packed[i].ntiles * (uint64_t)std::max(acmk_tile2m_rows(s.level), 0) / 2 + 1 + ACM_PAIR_READ_SLACK;
+		if (entries > ACM_TABLE_INDEX_END || packed[i].chunk_off > ACM_TABLE_INDEX_END - entries) {
+			set_err("stream %zu: chunk_off %llu + %llu pair-table entries (%u of them read slack) is past entry %llu, the last a launch can name",
+				i, (unsigned long long)packed[i].chunk_off, (unsigned long long)entries, (unsigned)ACM_PAIR_READ_SLACK,
+				(unsigned long long)(ACM_TABLE_INDEX_END - 1));
+			return ACMHIP_ERR_ARG;
+		}
 	}
 	const AcmDevStream d = dev_stream_of(s);        /* by value: cut.streams grows while windows are cut */
 	cut.streams[i] = d;

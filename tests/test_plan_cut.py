@@ -11,6 +11,9 @@ over one list of cases:
   * properties of the records themselves: the emitted PCM is tiled exactly once, form_rows agrees with the second-form records,
     samples are counted, patches land inside the plane.
 
+A second list, limit_cases(), is not held to the recording (the recorded planner wrapped there): header indices and pair-table entries
+at 2^32 - 1, 2^32 and 2^32 + 1 are either exact in every table or refused (test_table_limits_are_refused_not_wrapped).
+
 Two guards inside the cutter's cut_lean() have no case: "a window on the lean kernels starts on a tile boundary of a stream with a
 byte-plane form" and "a window on the lean kernel of level L needs N rows in front".  Its only caller that passes a window (plain fused
 streams, levels 5-12) checks the boundary and the form before it calls, and the one build whose lead-in is longer than a tile is level
@@ -234,6 +237,59 @@ def build_cases(L):
     return cases
 
 
+E32 = 1 << 32
+PAIR_READ_SLACK = 32            # entries the pair table is readable past its last one (include/acm_hip.h: acmhip_plan_bind_mform)
+LIMIT_FLAVOURS = (("lean", capi.PLAN_LEAN_ALWAYS, None), ("byteplane", capi.PLAN_LEAN_ALWAYS, FORM_BYTEPLANE),
+                  ("byteplane_form_only", capi.PLAN_LEAN_ALWAYS | capi.PLAN_FORM_ONLY, FORM_BYTEPLANE), ("packed", capi.PLAN_LEAN_ALWAYS, FORM_PACKED),
+                  ("no_lean", capi.PLAN_NO_LEAN, FORM_BYTEPLANE), ("stagewise", capi.PLAN_STAGEWISE, FORM_PACKED), ("auto", capi.PLAN_AUTO, None))
+
+
+def _limit_batch(L, level, form, rows=3):
+    """a near stream, then the one whose offset a case moves: from row 0 (lean, byte-plane and packed tiles, a ragged rest), and
+    (byte-plane form, levels up to 12) a window of it from a tile boundary"""
+    b, u = Batch(L), _unit(L, level)
+    b.add(level, 2, 2 * u + 1, 0, (2 * u + 1) << level, form)
+    b.add(level, rows, 3 * u + 5, 0, ((3 * u + 4) << level) + 3, form)
+    if form == FORM_BYTEPLANE and level <= 12:
+        b.add(level, rows, 3 * u + 5, u, (2 * u) << level, form)
+        b.descs[2].idx_off, b.descs[2].hdr_off = b.descs[1].idx_off, b.descs[1].hdr_off
+        b.packed[2].chunk_off = b.packed[1].chunk_off
+    return b
+
+
+def form_entries(L, d, p):
+    """table entries a stream's second staged form takes (acmhip_packed_stream)"""
+    if p.form == FORM_PACKED:
+        return p.ntiles * L.acmk_tile2p_slots(d.level)
+    return p.ntiles * max(L.acmk_tile2m_rows(d.level), 0) // 2 + 1
+
+
+def limit_cases(L):
+    """-> [(case, the same case with the moved offsets near, what moved, by how much, whether include/acm_hip.h allows it)]: hdr_off + blocks
+    and chunk_off + a stream's entries at 2^32 - 1, 2^32 and 2^32 + 1 (and chunk_off of a byte-plane stream with the pair table's read
+    slack behind it at 2^32 and one past), for plans that cut lean, byte-plane and packed records and for plans that do not.  Not part of
+    build_cases(): that list is held to a planner recorded before these limits existed, which wrapped."""
+    out = []
+    for level, flavours in ((9, LIMIT_FLAVOURS), (11, LIMIT_FLAVOURS[:3]), (14, LIMIT_FLAVOURS[1:2]), (3, LIMIT_FLAVOURS[-1:])):
+        for fname, flags, form in flavours:
+            near = _limit_batch(L, level, form)
+            blocks = (near.descs[1].nrows + near.descs[1].rows - 1) // near.descs[1].rows
+            points = [("hdr_off", E32 + k - blocks, k <= 0) for k in (-1, 0, 1, blocks, blocks + 8)]       # (the last two: hdr_off itself at and past 2^32)
+            if form is not None:
+                ent = form_entries(L, near.descs[1], near.packed[1])
+                slack = PAIR_READ_SLACK if form == FORM_BYTEPLANE else 0
+                points += [("chunk_off", E32 + k - ent, form == FORM_PACKED or k + slack <= 0) for k in sorted({-1, 0, 1, -slack, 1 - slack})]
+            for what, value, allowed in points:
+                far = _limit_batch(L, level, form)
+                base = getattr(near.descs[1], what) if what == "hdr_off" else near.packed[1].chunk_off
+                for k in range(1, len(far.descs)):
+                    setattr(far.descs[k] if what == "hdr_off" else far.packed[k], what, value)
+                name = "limit_l%d_%s_%s_%d" % (level, fname, what, value)
+                out.append((far.case(name, 2, flags), near.case(name + "_near", 2, flags), what, value - base, allowed))
+    assert len({c[0].name for c in out}) == len(out)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- running a case
 
 def run_case(L, case):
@@ -442,3 +498,50 @@ def test_form_rows_samples_and_patches():
         plane = groups_of(stats)[0]
         if ("patches", 0) in tabs:
             assert (tabs[("patches", 0)]["dst"] < plane).all(), case.name
+
+
+def test_table_limits_are_refused_not_wrapped():
+    """include/acm_hip.h: header indices and the byte-plane form's pair-table entries end below 2^32 (AcmTile2.hdr_blk has 32 bits, the
+    byte-plane kernels read the pair table at a 32-bit index, 32 entries of read slack included); the packed chunk table is indexed in
+    64 bits.  A plan whose stream stays within that equals, table by table, the plan of the same batch with the stream's offset near 0,
+    every header index / table entry moved by exactly the 64-bit difference; one that does not is ACMHIP_ERR_ARG with a message that
+    names the stream - whichever kernel family the plan would have used - and emits no table"""
+    L = _lib()
+    cases = limit_cases(L)
+    moved_fields = {"hdr_off": {"streams": "hdr_off", "tiles2": "hdr_blk", "tiles2p": "hdr_blk", "tiles2p_plain": "hdr_blk", "tiles2m": "hdr_blk",
+                                "tiles2m_plain": "hdr_blk"},
+                    "chunk_off": {"tiles2p": "idx_off", "tiles2m": "idx_off"}}
+    seen = set()
+    for far, near, what, shift, allowed in cases:
+        res = run_case(L, far)
+        if not allowed:
+            assert res["rc"] == capi.ERR_ARG and not res["tables"], far.name
+            assert res["err"].startswith("stream 1: ") and what in res["err"], (far.name, res["err"])
+            seen.add((what, False))
+            continue
+        assert res["rc"] == 0, (far.name, res["err"])
+        ref = run_case(L, near)
+        assert ref["rc"] == 0 and res["tables"].keys() == ref["tables"].keys(), far.name
+        base = near.descs[1].hdr_off if what == "hdr_off" else near.packed[1].chunk_off
+        assert base > 0
+        ft, nt = decode(res), decode(ref)
+        for (name, level), want in nt.items():
+            got = ft[(name, level)]
+            assert got.shape == want.shape, (far.name, name)
+            field = moved_fields[what].get(name)
+            if field is None:
+                assert got.tobytes() == want.tobytes(), (far.name, name)
+                continue
+            for f in want.dtype.names:
+                if f != field:
+                    assert np.array_equal(got[f], want[f]), (far.name, name, f)
+            w64 = want[field].astype(np.uint64)
+            moved = w64 >= np.uint64(base)
+            assert moved.any() and not moved.all(), (far.name, name)
+            w64[moved] += np.uint64(shift)
+            assert np.array_equal(got[field].astype(np.uint64), w64), "%s: %s.%s is not the 64-bit value" % (far.name, name, field)
+            if name == "tiles2m" and what == "chunk_off":       # as the kernels read it: 32 bits, whole groups of entries
+                assert int(w64.max()) + PAIR_READ_SLACK < E32
+            seen.add((what, name))
+    assert {("hdr_off", False), ("chunk_off", False)} <= seen
+    assert {(w, n) for w, names in moved_fields.items() for n in names} <= seen, seen
