@@ -44,6 +44,7 @@
 #include <utility>
 
 #include "acm_device.h"
+#include "acm_late_scale.h"     /* level 9: the power of two that enters in the last LDS pass, and the forms that take it */
 #include "acm_kernel_geo.h"     /* every build's tile, threads and workgroups per CU: the tables the host's queries answer from */
 
 #ifndef ACM_L14_GROUPS
@@ -523,7 +524,8 @@ constexpr int park_piece() { return NJ_LAST == 32 ? 8 : 4; }
  * multiplies by val << SHIFT, the "+1" becomes 1 << SHIFT) that moves the sample onto a byte boundary:
  *   level <= 8 : SHIFT = 8 - level, sample = bytes 1..2 - bits [0,24) still inside the 25 bits that the
  *                one-op v_mad_i32_i24 butterfly keeps exact;
- *   level == 9 : no scaling (bits 9..24 are needed and 25 is all mad24 gives): two shifts per pair instead;
+ *   level == 9 : no scaling here (bits 9..24 are needed and 25 is all mad24 gives): the 2^7 that puts the sample into bytes 2..3
+ *                enters in the last LDS pass instead (LastOut below, acm_late_scale.h);
  *   level >= 10: these levels use exact 32-bit butterflies anyway, SHIFT = 16 - level, sample = bytes 2..3.
  * Two samples are then packed, byte-swapped if asked, by ONE v_perm_b32; unsigned output is one xor per pair.
  */
@@ -531,7 +533,22 @@ template <int L>
 struct OutScale {
 	static constexpr int SHIFT = (L <= 8) ? 8 - L : (L >= 10 ? 16 - L : 0);
 	static constexpr int BYTE = (L <= 8) ? 1 : (L >= 10 ? 2 : 0);     /* first byte of the sample inside the value */
-	static constexpr bool PRESHIFT = (L == 9);
+	static constexpr bool PRESHIFT = (L == 9);                         /* (as the unpack leaves it: see LastOut) */
+};
+
+/*
+ * What the write-out of a LAST pass of G stages sees.  OutScale keeps describing what the unpack multiplies by; at level 9 a last
+ * pass of two or more stages (every shipped build: 3) adds acm_late::LateScale - stage G - 2 of the pass, kind P, injects << 7,
+ * stage G - 1 runs exact mod 2^32 - so the sample starts at byte 2 and no pre-shift is left.  A last pass of ONE stage at level 9
+ * (tuning groupings only) has no P stage in reach and keeps the two shifts per pair.
+ */
+template <int L, int G>
+struct LastOut {
+	using Late = acm_late::LateScale<L, G>;
+	static constexpr bool LATE = Late::ON;
+	static constexpr int BYTE = LATE ? Late::BYTE : OutScale<L>::BYTE;
+	static constexpr bool PRESHIFT = OutScale<L>::PRESHIFT && !LATE;
+	static_assert(!LATE || OutScale<L>::SHIFT == 0, "the late scale stands in for the unpack's, not beside it");
 };
 
 struct PcmFmt {
@@ -539,23 +556,21 @@ struct PcmFmt {
 	uint32_t flip;    /* xor mask for unsigned output */
 };
 
-template <int L>
+/* W: the LastOut of the pass that writes out */
+template <class W>
 __device__ __forceinline__ PcmFmt make_pcm_fmt(unsigned fmt)
 {
 	PcmFmt f;
 	const bool be = fmt & 1u, uns = fmt & 2u;
-	/* v_perm_b32(S0 = second value, S1 = first value): byte k of S1 is index k, of S0 index 4+k */
-	constexpr uint32_t lo = OutScale<L>::BYTE, hi = OutScale<L>::BYTE + 1;
-	f.sel = be ? ((4 + lo) << 24 | (4 + hi) << 16 | lo << 8 | hi)
-		   : ((4 + hi) << 24 | (4 + lo) << 16 | hi << 8 | lo);
-	f.flip = uns ? (be ? 0x00800080u : 0x80008000u) : 0u;
+	f.sel = acm_late::perm_sel((uint32_t)W::BYTE, be);
+	f.flip = acm_late::perm_flip(be, uns);
 	return f;
 }
 
-template <int L, bool FLIP, bool BIGEND = true>
+template <int L, class W, bool FLIP, bool BIGEND = true>
 __device__ __forceinline__ uint32_t pack_pcm(uint32_t a, uint32_t b, const PcmFmt &f)
 {
-	if (OutScale<L>::PRESHIFT) {
+	if (W::PRESHIFT) {
 		if (!BIGEND) {
 			/* two ops per pair: a >> L, then SDWA drops the low half of b >> L into the upper word */
 			uint32_t p = a >> L;
@@ -599,12 +614,17 @@ struct PassGeo {
  * of the body (only the thread owning residue 0 of a stage-0 pass passes 1,
  * and only for rows that exist: history before the stream start is all-zero).
  */
-template <int L, int K0, int G>
+/* LATE (a last pass under acm_late::LateScale): stage G - 2 injects the scale, stage G - 1 runs exact on the scaled values; h[G - 1]
+ * is then in scaled units, here and in the warm-up body that refills it. */
+template <int L, int K0, int G, bool LATE = false>
 __device__ __forceinline__ void pass_body(uint32_t (&v)[2 << G], uint32_t (&h)[G][1 << G],
 					  uint32_t bias_lo, uint32_t bias_hi)
 {
 	constexpr int U = 1 << G, BODY = 2 * U;
 	constexpr bool EXACT32 = (L > 9);
+	using Late = acm_late::LateScale<L, G>;
+	static_assert(!LATE || (Late::ON && K0 + G == L && K0 + Late::INJECT > 0 && !StageKind<L, K0 + (LATE ? Late::INJECT : 0)>::N &&
+				StageKind<L, K0 + (LATE ? Late::EXACT : 0)>::N), "the late scale enters at a P stage behind stage 0 and ends in the last, N, stage");
 #pragma unroll
 	for (int t = 0; t < G; t++) {
 		const int d = 1 << (G - 1 - t);
@@ -624,7 +644,13 @@ __device__ __forceinline__ void pass_body(uint32_t (&v)[2 << G], uint32_t (&h)[G
 			/* the "+1" rides on the first op (an add3 at worst) */
 			const bool biased = (K0 + t == 0) && (u % ((U / 2) > 0 ? (U / 2) : 1)) == 0;
 			const uint32_t b = biased ? ((u < U) ? bias_lo : bias_hi) : 0u;
-			if (!kindN) {
+			if (LATE && t == Late::INJECT) {
+				/* even: y << 7 = (z2+z0 + 2*z1) << 7;  odd: -y << 7 = (z2+z0 - 2*z1) << 7 */
+				y = beta ? acm_late::p_inject_odd(z0, z1, z2) : acm_late::p_inject_even(z0, z1, z2);
+			} else if (LATE && t == Late::EXACT) {
+				const int aneg = (u >> (pb + 1)) & 1;
+				y = (aneg ^ beta) == 0 ? acm_late::n_exact_sub(z0, z1, z2) : acm_late::n_exact_add(z0, z1, z2);
+			} else if (!kindN) {
 				/* even: y = (z2+z0+b) + 2*z1;  odd: -y = (z2+z0-b) - 2*z1 */
 				y = beta ? sub_twice<EXACT32>(biased ? z2 + z0 - b : z2 + z0, z1)
 					 : add_twice(biased ? z2 + z0 + b : z2 + z0, z1);
@@ -858,7 +884,8 @@ __device__ __forceinline__ void lds_pass(uint32_t *tile, const int tid, const un
 	const int seg = tid / SIGMA;
 	const int i = tid % SIGMA;
 	const int m_seg = seg * P::NJ * SIGMA + i;              // first element of this thread's walk
-	const PcmFmt pf = make_pcm_fmt<L>(fmt);
+	using W = LastOut<L, G>;                                /* (looked at by a last pass only) */
+	const PcmFmt pf = make_pcm_fmt<W>(fmt);
 	/* one runtime address per thread; every body of the walk (and the warm-up body in front of it) sits at a
 	 * compile-time offset from it: NJ*SIGMA is a multiple of 64 and bodies never straddle a pad dword */
 	constexpr int PS = C::PS, PG = 1 << PS;
@@ -918,7 +945,7 @@ __device__ __forceinline__ void lds_pass(uint32_t *tile, const int tid, const un
 			nxt[u] = base[P::off(u)];
 	}
 	if (!(ABL & 2))
-		pass_body<L, K0, G>(w, h, K0 == 0 ? bias_warm : 0u, K0 == 0 ? bias_warm : 0u);
+		pass_body<L, K0, G, LAST && W::LATE>(w, h, K0 == 0 ? bias_warm : 0u, K0 == 0 ? bias_warm : 0u);
 
 #pragma unroll
 	for (int it = 0; it < NBODY; it++) {
@@ -934,7 +961,7 @@ __device__ __forceinline__ void lds_pass(uint32_t *tile, const int tid, const un
 				nxt[u] = pn[P::off(u)];
 		}
 		if (!(ABL & 2))
-			pass_body<L, K0, G>(v, h, K0 == 0 ? bias : 0u, K0 == 0 ? bias : 0u);
+			pass_body<L, K0, G, LAST && W::LATE>(v, h, K0 == 0 ? bias : 0u, K0 == 0 ? bias : 0u);
 		if (it + 1 < NBODY && (ABL & MODE_LEAN) != 0) {
 			/* short of registers: the next body is asked for behind this one's butterflies, not beside them */
 			__builtin_amdgcn_sched_barrier(0);
@@ -951,7 +978,7 @@ __device__ __forceinline__ void lds_pass(uint32_t *tile, const int tid, const un
 #pragma unroll
 			for (int u = 0; u < BODY; u += 2) {
 				const int d = it * (BODY / 2) + u / 2;          /* dword of the thread's samples */
-				base[(d / 4) * park_piece<C::NJ_LAST>() + d % 4] = pack_pcm<L, FLIP, BIGEND>(v[u], v[u + 1], pf);
+				base[(d / 4) * park_piece<C::NJ_LAST>() + d % 4] = pack_pcm<L, W, FLIP, BIGEND>(v[u], v[u + 1], pf);
 			}
 		}
 	}
