@@ -24,6 +24,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "acm_launch_caps.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -362,6 +364,18 @@ int  acmhip_device_set_fill(acmhip_device *dev, int on);
  * what the last call that held the handle's arenas asked of it (0: that call did not use it); *fill: the byte the fill mode puts there.
  * Not while a call is using the handle. */
 int  acmhip_device_arena_info(acmhip_device *dev, int slot, const char **name, void **ptr, size_t *bytes, int *is_host, int *fill);
+/*
+ * Launch caps: a debugging aid like the fill mode, for tests only.  Some launchers walk a list longer than one grid in slices, and some
+ * cap their grid and let the kernel stride over the rest (acm_launch_caps.h names the five limits and the kernels behind them).  At
+ * the built-in limits a second slice or a second trip takes 65 536 streams, 32 M samples of one level 0-4 stream or a million dense
+ * rows; with a limit lowered, a test of a few streams walks the same path.  A cap can only be lowered: a field of 0 stands for the
+ * built-in value, a field above it makes the call return ACMHIP_ERR_ARG with nothing changed.  caps == NULL: the built-in values.
+ * *previous (may be NULL): the caps in force before the call, as they were set (0 = built-in).  The handle keeps the caps and hands
+ * them to its launchers as plain arguments: there is no process-wide state, other handles are not affected, and a launch still asks
+ * nothing of the runtime.  No cap changes a result - only how many launches or trips produce it.  Waits for a batch call that is
+ * using the handle; a plan launched while the call runs may see either set.
+ */
+int  acmhip_device_set_launch_caps(acmhip_device *dev, const acmhip_launch_caps *caps, acmhip_launch_caps *previous);
 
 /*
  * Time `reps` back-to-back acmhip_plan_launch calls with HIP events recorded on

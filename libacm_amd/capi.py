@@ -5,6 +5,7 @@ computes: staging is done by the library's host parser, synthesis by its HIP
 kernels.  There is no CPU synthesis fallback - without a usable HIP device
 Device() raises.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -179,6 +180,19 @@ class IndexTiming(C.Structure):
                 ("device_bytes", C.c_uint64), ("groups", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LaunchCaps(C.Structure):
+    """acmhip_launch_caps (include/acm_launch_caps.h): 0 in a field = the built-in value"""
+    _fields_ = [("list_slice", C.c_uint32), ("small_grid_x", C.c_uint32), ("parse_slice", C.c_uint32), ("parse_grid_x", C.c_uint32),
+                ("dense_grid", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+# the built-in values of include/acm_launch_caps.h (tests/test_launch_caps.py holds them against the header and the library)
+LAUNCH_CAPS_BUILTIN = {"list_slice": 65535, "small_grid_x": 4096, "parse_slice": 65535, "parse_grid_x": 2048, "dense_grid": 1 << 20}
+
+
 # every symbol include/acm_hip.h declares (checked by tests/test_abi.py)
 ACMHIP_SYMBOLS = [
     "acmhip_last_error", "acmhip_device_count", "acmhip_device_open", "acmhip_device_close",
@@ -194,7 +208,7 @@ ACMHIP_SYMBOLS = [
     "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
     "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
-    "acmhip_device_set_fill", "acmhip_device_arena_info",
+    "acmhip_device_set_fill", "acmhip_device_arena_info", "acmhip_device_set_launch_caps",
 ]
 # the 19 entry points of include/libacm.h (reference src/libacm.h:120-170)
 LIBACM_SYMBOLS = [
@@ -234,6 +248,9 @@ def lib():
     L.acmhip_device_stream.restype = vp
     L.acmhip_device_set_fill.argtypes = [vp, C.c_int]
     L.acmhip_device_arena_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "acmhip_device_set_launch_caps"):                # (an older library named by ACM_HIP_LIB for an A/B run has none)
+        L.acmhip_device_set_launch_caps.argtypes = [vp, C.POINTER(LaunchCaps), C.POINTER(LaunchCaps)]
+        L.acmk_launch_caps_set.argtypes = [C.POINTER(LaunchCaps)] * 3
     L.acmhip_malloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.acmhip_free.argtypes = [vp, vp]
     L.acmhip_host_alloc.argtypes = [sz, C.POINTER(vp)]
@@ -720,6 +737,26 @@ class Device:
         self.fill = bool(on)
         return bool(was)
 
+    def set_launch_caps(self, caps=None):
+        """acmhip_device_set_launch_caps: caps = a LaunchCaps, a dict of its fields, or None for the built-in values -> the LaunchCaps in
+        force before"""
+        if isinstance(caps, dict):
+            caps = LaunchCaps(**caps)
+        was = LaunchCaps()
+        _check(lib().acmhip_device_set_launch_caps(self.h, C.byref(caps) if caps is not None else None, C.byref(was)),
+               "acmhip_device_set_launch_caps")
+        return was
+
+    @contextlib.contextmanager
+    def launch_caps(self, **fields):
+        """tests only: the handle's launch caps lowered to `fields` (list_slice=3, dense_grid=1, ...; the others built-in) inside the
+        with block, the previous caps back behind it"""
+        was = self.set_launch_caps(LaunchCaps(**fields))
+        try:
+            yield
+        finally:
+            self.set_launch_caps(was)
+
     def arena_info(self):
         """acmhip_device_arena_info over every staging arena of the handle -> {name: (slot, ptr or None, bytes the last call asked of it,
         is_host, fill byte)}"""
@@ -1194,13 +1231,14 @@ def dense_overlay_gain(energy_a, energy_b, snr):
 
 def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                  fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                                 check=True, mix=False, rate=None, speeds=None, nrows=None):
+                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False):
     """acm_batch_decode_windows_overlay: the windows are the SOURCE rows of batch_decode_windows_dense (every argument it has means the
     same), and d_pcm receives len(rows) output rows of frames * channels samples, row r at sample r * frames * channels.  rows: tuples
     (a, b, vol, snr, gain) of acm_overlay_row's inputs - b None for ACM_OVERLAY_NONE - or 6-tuples that end in `reserved`, or an array
     of OVERLAY_ROW_DT records (a large batch: nothing is done row by row here; it is not written into); None for no row table at all
     (tests of the refusals: nrows is then what the call is told).  Returns (statuses, words, offsets, gains, WindowTiming): statuses and words are the windows', offsets their
-    (dev_off, slot_off, slot_words), gains (g, energy_a, energy_b) per output row.  check=False: the return code as a sixth element
+    (dev_off, slot_off, slot_words), gains (g, energy_a, energy_b) per output row - or, with result_table=True (a million rows), the call's own copy of the row table as
+    the library left it, an OVERLAY_ROW_DT array whose gain, energy_a and energy_b fields hold them.  check=False: the return code as a sixth element
     instead of an exception."""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
@@ -1230,7 +1268,8 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
         _check(rc, "acm_batch_decode_windows_overlay")
     res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)],
            [(int(wins[k].dev_off), int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)],
-           list(zip(table["gain"][:nr].tolist(), table["energy_a"][:nr].tolist(), table["energy_b"][:nr].tolist())), tm)
+           table[:nr] if result_table else list(zip(table["gain"][:nr].tolist(), table["energy_a"][:nr].tolist(), table["energy_b"][:nr].tolist())),
+           tm)
     return res if check else res + (rc,)
 
 

@@ -797,10 +797,11 @@ int BatchRun::plan_device_chunks()
 int BatchRun::launch_range(size_t r, size_t stripes_up)
 {
 	AcmParseResult *d_res = reinterpret_cast<AcmParseResult *>(d_jobs + L.jobs_bytes);
+	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	const int e = acmk_launch_parse_range_mf(reinterpret_cast<const AcmParseJob *>(d_jobs), (uint32_t)nd, d_files, d_colpos, d_idx,
 						 d_hdr, d_res, reinterpret_cast<uint32_t *>(d_res + nd), max_columns, (uint32_t)r, (uint32_t)R, (uint32_t)stripes_up,
 						 L.dev_mform ? d_pkblob : nullptr, L.dev_mform ? reinterpret_cast<uint32_t *>(d_pkchunk) : nullptr,
-						 L.dev_mform ? d_blkoff : nullptr, d_marks, st_parse);
+						 L.dev_mform ? d_blkoff : nullptr, d_marks, caps.parse_slice, caps.parse_grid_x, st_parse);
 	if (e != 0)
 		return acmhip_report_hip(e, "acmk_launch_parse_range");
 	BNOTE("range %zu: walk queued", r);

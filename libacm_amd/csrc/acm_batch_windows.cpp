@@ -232,9 +232,10 @@ int WinRun::parse_on_device()
 		timed_h2d = true;
 		tm.h2d_bytes += L.files_total + tables;
 		ACM_HIP_TRY(hipMemsetAsync(d_res, 0, L.res_bytes, st));
+		const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 		const int e = acmk_launch_parse_blocks(reinterpret_cast<const AcmParseJob *>(d_jobs), (uint32_t)nd,
 						       reinterpret_cast<const AcmBlockJob *>(d_jobs + L.bjobs_off()), (uint32_t)L.bjobs.size(), d_files,
-						       d_colpos, d_idx, d_hdr, d_res, d_flags, L.max_columns, st);
+						       d_colpos, d_idx, d_hdr, d_res, d_flags, L.max_columns, caps.parse_slice, caps.parse_grid_x, st);
 		if (e != 0)
 			return acmhip_report_hip(e, "acmk_launch_parse_blocks");
 		ACM_HIP_TRY(hipMemcpyAsync(h_jobs + tables, d_res, L.res_bytes, hipMemcpyDeviceToHost, st));
@@ -340,12 +341,13 @@ int WinRun::synthesise_and_gather()
 	/* an overlay call: the same launch writes the source rows, int16, and the caller's tensor is combine_rows' */
 	void *const rows_out = overlay ? d_src : dense_out;
 	const bool rows_f32 = overlay ? false : dense->f32;
+	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	const int e = wide ? acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out,
-						     dense->frames, dense->channels, dense->planar, rows_f32, st)
+						     dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st)
 		      : filters ? acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out,
-							     dense->frames, dense->channels, dense->planar, rows_f32, st)
+							     dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st)
 				: (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames,
-											     dense->channels, dense->planar, rows_f32, st);
+											     dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
 	if (e != 0)
 		return acmhip_report_hip(e, wide ? "acmk_launch_dense_speed" : filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed"
 													      : "acmk_launch_dense_rows");
@@ -380,17 +382,18 @@ int WinRun::synthesise_and_gather()
 int WinRun::combine_rows()
 {
 	const size_t at = overlay_off();
+	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	uint64_t *d_energy = reinterpret_cast<uint64_t *>(d_jobs + at + overlay->energy_off());
 	if (!overlay->marked.empty()) {
 		ACM_HIP_TRY(hipMemsetAsync(d_energy, 0, overlay->energy_bytes(), st));
 		const int e = acmk_launch_dense_energy(d_src, reinterpret_cast<const uint32_t *>(d_jobs + at + overlay->marked_off()), overlay->marked.size(),
-						       overlay->row_words, d_energy, st);
+						       overlay->row_words, d_energy, caps.dense_grid, st);
 		if (e != 0)
 			return acmhip_report_hip(e, "acmk_launch_dense_energy");
 	}
 	const int e = acmk_launch_dense_overlay(d_src, reinterpret_cast<const AcmOverlayRow *>(d_jobs + at), d_energy,
 						reinterpret_cast<AcmOverlayResult *>(d_jobs + at + overlay->result_off()), overlay->rows.size(), dense_out,
-						overlay->row_words, dense->f32, st);
+						overlay->row_words, dense->f32, caps.dense_grid, st);
 	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_overlay") : ACMHIP_OK;
 }
 

@@ -92,7 +92,7 @@ int launch(bool nt, uint32_t grid, hipStream_t st, const int16_t *d_src, const A
 } // namespace
 
 extern "C" int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
-				      int planar, int f32, void *stream)
+				      int planar, int f32, uint32_t dense_grid, void *stream)
 {
 	if (nrows == 0)
 		return 0;
@@ -102,7 +102,7 @@ extern "C" int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d
 	if (units > 0x7FFFFFFFull || nrows > ~0ull / (units * stride))
 		return (int)hipErrorInvalidValue;
 	const uint64_t nwork = nrows * units * stride;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
 	/* Temporal stores: the batch is read by the next kernel of the caller's step (profiles/dense_crop_notes.txt).  The other variant is
 	 * reachable for measurements only, like every kernel switch (acm_device.h: ACM_TUNING_ENV) */
 	const char *env = ACM_TUNING_ENV("ACM_DENSE_NT");

@@ -399,7 +399,7 @@ struct FilterGeo {
 	uint32_t units, grid;
 	bool ok;                                /* false: more work than the kernels' counters hold */
 };
-inline FilterGeo filter_geo(uint64_t nrows, uint64_t frames, uint32_t channels, int planar)
+inline FilterGeo filter_geo(uint64_t nrows, uint64_t frames, uint32_t channels, int planar, uint32_t dense_grid)
 {
 	FilterGeo g{};
 	g.layout = channels == 1 ? MONO : planar ? PLANAR : INTER;
@@ -410,7 +410,8 @@ inline FilterGeo filter_geo(uint64_t nrows, uint64_t frames, uint32_t channels, 
 	g.ok = units <= 0x7FFFFFFFull && nrows <= ~0ull / ((units ? units : 1) * subs);
 	g.units = (uint32_t)(units ? units : 1);
 	g.nwork = g.ok ? nrows * g.units * subs : 0;
-	g.grid = (uint32_t)(g.nwork < DENSE_MAX_GRID ? g.nwork : DENSE_MAX_GRID);
+	const uint32_t most = acm_cap_value(dense_grid, DENSE_MAX_GRID);         /* the handle's launch cap, 0 = built-in */
+	g.grid = (uint32_t)(g.nwork < most ? g.nwork : most);
 	return g;
 }
 

@@ -175,7 +175,7 @@ int launch(uint32_t grid, hipStream_t st, const int16_t *d_src, const AcmDenseRo
 } // namespace
 
 extern "C" int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
-				       int planar, int f32, void *stream)
+				       int planar, int f32, uint32_t dense_grid, void *stream)
 {
 	if (nrows == 0)
 		return 0;
@@ -186,7 +186,7 @@ extern "C" int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *
 	if (units > 0x7FFFFFFFull || nrows > ~0ull / (units * subs))
 		return (int)hipErrorInvalidValue;
 	const uint64_t nwork = nrows * units * subs;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
 	hipStream_t st = (hipStream_t)stream;
 #define ACM_MIX_LAUNCH(OUT, LAYOUT) launch<OUT, LAYOUT>(grid, st, d_src, d_rows, nwork, (uint32_t)units, d_out, row_len, sub_len)
 	if (f32)

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_overlay(const int16_t *
 } // namespace
 
 extern "C" int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_marked, uint64_t nmarked, uint64_t row_len, uint64_t *d_energy,
-					void *stream)
+					uint32_t dense_grid, void *stream)
 {
 	if (nmarked == 0 || row_len == 0)
 		return 0;
@@ -165,14 +165,14 @@ extern "C" int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_
 	if (units > 0x7FFFFFFFull || nmarked > ~0ull / units)
 		return (int)hipErrorInvalidValue;
 	const uint64_t nwork = nmarked * units;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
 	hipLaunchKernelGGL(acm_dense_energy, dim3(grid), dim3(DENSE_BLOCK), 0, (hipStream_t)stream, d_src, d_marked, nwork, (uint32_t)units, row_len,
 			   reinterpret_cast<unsigned long long *>(d_energy));
 	return (int)hipGetLastError();
 }
 
 extern "C" int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayRow *d_rows, const uint64_t *d_energy, AcmOverlayResult *d_res,
-					 uint64_t nrows, void *d_out, uint64_t row_len, int f32, void *stream)
+					 uint64_t nrows, void *d_out, uint64_t row_len, int f32, uint32_t dense_grid, void *stream)
 {
 	if (nrows == 0 || row_len == 0)
 		return 0;
@@ -180,7 +180,7 @@ extern "C" int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayR
 	if (units > 0x7FFFFFFFull || nrows > ~0ull / units)
 		return (int)hipErrorInvalidValue;
 	const uint64_t nwork = nrows * units;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, DENSE_MAX_GRID);
+	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
 	const unsigned long long *energy = reinterpret_cast<const unsigned long long *>(d_energy);
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t gain_grid = (nrows + DENSE_BLOCK - 1) / DENSE_BLOCK;

@@ -56,11 +56,11 @@ int launch(const FilterGeo &g, hipStream_t st, const int16_t *d_src, const AcmDe
 } // namespace
 
 extern "C" int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps,
-					  uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream)
+					  uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, uint32_t dense_grid, void *stream)
 {
 	if (nrows == 0)
 		return 0;
-	const FilterGeo g = filter_geo(nrows, frames, channels, planar);
+	const FilterGeo g = filter_geo(nrows, frames, channels, planar, dense_grid);
 	if (!g.ok)
 		return (int)hipErrorInvalidValue;
 	hipStream_t st = (hipStream_t)stream;

@@ -10,11 +10,13 @@
 
 #include <stdint.h>
 
+#include "acm_launch_caps.h"
+
 namespace {
 
 constexpr int DENSE_BLOCK = 256;        /* lanes per workgroup = vectors per unit */
 constexpr int DENSE_VEC = 8;            /* output samples per body access */
-constexpr uint32_t DENSE_MAX_GRID = 1u << 20;
+constexpr uint32_t DENSE_MAX_GRID = ACM_CAP_DENSE_GRID;    /* workgroups of a launch at most; the kernels stride over the rest */
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

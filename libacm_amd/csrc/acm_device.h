@@ -197,6 +197,11 @@ int acmhip_copy_stream(acmhip_device *dev, void **out);          /* second strea
 #define ACM_AUX_STREAMS 2
 int acmhip_aux_stream(acmhip_device *dev, int k, void **out);    /* batch pipeline: 0 = device bit parsing, 1 = file uploads */
 int acmhip_report_hip(int hip_error, const char *what);
+/* the handle's launch caps as they were set (0 in a field: the built-in value), for the callers of the launchers below; and the device-free
+ * half of acmhip_device_set_launch_caps (acm_kernel_geo.cpp): checks `caps` (null: all built-in) against acm_launch_caps.h, then *previous = *held,
+ * *held = *caps - or ACMHIP_ERR_ARG and nothing changed */
+acmhip_launch_caps acmhip_device_launch_caps(const acmhip_device *dev);
+int acmk_launch_caps_set(acmhip_launch_caps *held, const acmhip_launch_caps *caps, acmhip_launch_caps *previous);
 void acmhip_set_error_text(const char *text);                    /* what acmhip_last_error() returns on this thread */          /* records the text, returns ACMHIP_ERR_HIP */
 
 /* Two kinds of acmk_* functions.  The ones that launch nothing - a build's tile rows, threads, grid, first-pass depth, lead-in, packed
@@ -257,10 +262,12 @@ int acmk_tile2m_stages(uint32_t level);                         /* stages of the
  * a plan: it launches on its device's one stream - follow each other and share one */
 int acmk_launch_tile2m(uint32_t level, int cus, const AcmTile2 *d_tiles, uint32_t ntiles, const uint8_t *d_mform, const acmhip_mform_pair *d_pairs,
 		       const acmhip_blkhdr *d_hdr, int16_t *d_pcm, int16_t *d_sink, unsigned fmt, uint32_t *d_claim, void *stream);
+/* list_slice (here and in the launchers of stream lists below), small_grid_x, parse_slice / parse_grid_x and dense_grid: the handle's launch caps
+ * (acmhip_device_launch_caps, acm_launch_caps.h) as plain values; 0 = the built-in one */
 int acmk_launch_unpack(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
-		       const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_x, uint32_t shift, void *stream);
+		       const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_x, uint32_t shift, uint32_t list_slice, void *stream);
 int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
-		       uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, void *stream);   /* levels 13-15: unpack + level-12 stages */
+		       uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, uint32_t list_slice, void *stream);   /* levels 13-15: unpack + level-12 stages */
 int acmk_plane_tile_rows(void);                                 /* tile rows (incl. 2 halo rows) of the level-12 plane kernel */
 int acmk_plane_threads(void);
 int acmk_plane_grid(int cus);                                   /* persistent workgroups of that kernel */
@@ -268,7 +275,7 @@ int acmk_launch_fused_plane(int cus, int carry, const AcmDevStream *d_streams, c
 			    const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_patch(const AcmDevPatch *d_patches, uint64_t n, int32_t *d_x, void *stream);
 int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
-		      uint32_t level, uint32_t k, const int32_t *d_in, int32_t *d_out, uint32_t shift, void *stream);
+		      uint32_t level, uint32_t k, const int32_t *d_in, int32_t *d_out, uint32_t shift, uint32_t list_slice, void *stream);
 /* acm_parse.hip's launchers; acmk_parse_supported, acmk_stripe_bound and acmk_range_bound: acm_kernel_geo.cpp (acm_parse_bounds.h is the text
  * the kernels and the host share) */
 int acmk_parse_supported(uint32_t level, uint32_t rows, uint64_t file_len, uint64_t blocks);
@@ -276,27 +283,29 @@ int acmk_parse_supported(uint32_t level, uint32_t rows, uint64_t file_len, uint6
  * of acm_block_mark indexed like d_hdr; every block the walk completes leaves d_marks[hdr_off + b] = { its first bit, val, pwr }.  The entry
  * behind a stream's last block is not written: it is d_res[j].end_bit of a walk that came back clean */
 int acmk_launch_parse(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
-		      acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, void *stream);
+		      acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, uint32_t parse_slice, uint32_t parse_grid_x,
+		      void *stream);
 /* the same for block range r of R: stream j's blocks [blocks * r / R, blocks * (r + 1) / R), resuming at the bit offset range
  * r - 1 left in d_res (ranges are launched in order on one stream; njobs <= ACM_PARSE_RANGE_MAX_STREAMS) */
 #define ACM_PARSE_RANGE_MAX_STREAMS 32768
 int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
 			    acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t r, uint32_t R,
-			    uint32_t stripes_up, acm_block_mark *d_marks, void *stream);
+			    uint32_t stripes_up, acm_block_mark *d_marks, uint32_t parse_slice, uint32_t parse_grid_x, void *stream);
 /* the same with byte-plane staging for the jobs that ask for it (mf_rows != 0): d_mf = the byte-plane arena, d_pairs = its pair table,
  * d_blkoff = one word per block (indexed like d_hdr): where the row pair that holds the block's first row starts in its stream's region, in
  * 64-byte units (blocks of an odd height: every other one begins inside a pair).  Streams are walked
  * by the wave-per-stream kernel only (njobs <= ACM_PARSE_RANGE_MAX_STREAMS) */
 int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx,
 			       acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t r, uint32_t R,
-			       uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, acm_block_mark *d_marks, void *stream);
+			       uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, acm_block_mark *d_marks, uint32_t parse_slice,
+			       uint32_t parse_grid_x, void *stream);
 /* Indexed input: njobs jobs (here: windows into streams; a job's file is the byte span of its blocks, data_start unused) whose blocks are
  * the nblock walks of d_bjobs, one wavefront each; then the column kernel over every job, in one piece, int16 rows only.  d_res and d_flags
  * [njobs] must be zero on entry; afterwards job j is clean iff d_res[j].status == 0 && d_res[j].blocks_done == its blocks && d_flags[j] == 0
  * (a walk that fails - data running out, a bad code, a header or an end that disagrees with the index - raises status) */
 int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock, const uint8_t *d_files,
 			     uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr, AcmParseResult *d_res, uint32_t *d_flags,
-			     uint64_t max_columns, void *stream);
+			     uint64_t max_columns, uint32_t parse_slice, uint32_t parse_grid_x, void *stream);
 /* The block index of njobs streams (<= ACM_PARSE_RANGE_MAX_STREAMS), one wavefront each (acm_index_scan_wave): of a job only file_off, file_len,
  * data_start, level, rows, blocks and hdr_off - here the stream's first entry of d_marks - are read.  Block b of stream j leaves
  * d_marks[hdr_off + b] = { bit, val, pwr }, a walk that covers all its blocks also d_marks[hdr_off + blocks] = { end bit, 0, 0 }; d_res[j] =
@@ -315,9 +324,9 @@ uint32_t acmk_range_bound(uint32_t blocks, uint32_t r, uint32_t R, uint32_t unit
 int acmk_launch_scatter_stripe(const AcmParseJob *d_jobs, uint32_t njobs, const uint64_t *d_stripe_at, const uint8_t *d_stage,
 			       uint8_t *d_files, uint32_t s, uint32_t S, void *stream);
 int acmk_launch_small(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
-		      const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
+		      const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, uint32_t small_grid_x, void *stream);
 int acmk_launch_emit(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
-		     const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream);
+		     const int32_t *d_x, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, void *stream);
 /* the float32 builds (acm_kernels_f32.hip), reached through fmt | ACMK_FMT_F32 of the launchers above */
 int acmk_launch_fused_f32(uint32_t level, int variant, int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles,
 			  uint32_t ntiles, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
@@ -328,31 +337,31 @@ int acmk_launch_tile2m_f32(uint32_t level, int cus, const AcmTile2 *d_tiles, uin
 int acmk_launch_fused_plane_f32(int cus, int carry, const AcmDevStream *d_streams, const AcmTile *d_tiles, uint32_t ntiles,
 				const int32_t *d_plane, int16_t *d_pcm, unsigned fmt, void *stream);
 int acmk_launch_small_f32(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
-			  const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, void *stream);
+			  const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, uint32_t small_grid_x, void *stream);
 int acmk_launch_emit_f32(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
-			 const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream);
+			 const int32_t *d_x, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, void *stream);
 /* acm_dense.hip: nrows rows of frames * channels samples each into d_out (int16, or float32 = the int16 sample times 2^-15 with f32), row k at
  * element k * frames * channels: d_rows[k].count samples from d_src + d_rows[k].src, interleaved as they are or (planar, channels == 2) split
  * into a plane per channel, zeros behind them.  d_src: 16-byte aligned; the kernel loads whole aligned 16-byte lines and only lines that hold
  * at least one of a row's samples.  d_out: aligned to its element.  One launch, nothing allocated, nothing waited for */
 int acmk_launch_dense_rows(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
-			   int planar, int f32, void *stream);
+			   int planar, int f32, uint32_t dense_grid, void *stream);
 /* acm_dense_mix.hip: the same launch for a row table in which some row carries a converting mode (AcmDenseMode) - the one the
  * batch's layout allows: DOWN with channels == 1, UP_INTER with channels == 2, UP_PLANAR with channels == 2 and planar.  Rows without
  * mode bits are written as acmk_launch_dense_rows writes them.  The same demands on d_src and d_out; a converting row's samples lie
  * inside its slot too */
 int acmk_launch_dense_mixed(const int16_t *d_src, const AcmDenseRow *d_rows, uint64_t nrows, void *d_out, uint64_t frames, uint32_t channels,
-			    int planar, int f32, void *stream);
+			    int planar, int f32, uint32_t dense_grid, void *stream);
 /* acm_dense_resample.hip: the same launch for a call in which some row is resampled (d_rs[k].L != 0): such a row is filtered from its
  * source samples after their channel conversion; the others are written as acmk_launch_dense_mixed writes them.  d_taps: the tap
  * tables of the call's ratios, 16-byte aligned.  The same demands on d_src and d_out */
 int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps, uint64_t nrows,
-			       void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
+			       void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, uint32_t dense_grid, void *stream);
 /* acm_dense_speed.hip: the same launch for a call in which some row takes the wide filter (d_sp[k].wide != 0); rows with L != 0
  * and wide == 0 are filtered as acmk_launch_dense_resample filters them, the others written as it writes them.  d_taps: the exact
  * and wide tables of the call, 16-byte aligned.  The same demands on d_src and d_out */
 int acmk_launch_dense_speed(const int16_t *d_src, const AcmDenseRow *d_rows, const AcmSpeedRow *d_sp, const int16_t *d_taps, uint64_t nrows,
-			    void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, void *stream);
+			    void *d_out, uint64_t frames, uint32_t channels, int planar, int f32, uint32_t dense_grid, void *stream);
 /* acm_dense_overlay.hip, behind a dense launch that wrote source row k to d_src + k * row_len (int16; d_src 16-byte aligned, 8 samples
  * of memory behind the last row).  The energy launch adds the sum of squares of every row d_marked names (each once) to
  * d_energy[that row], which the caller has zeroed: one 64-bit atomic add per workgroup, of integers, so the sums do not depend on the
@@ -360,9 +369,10 @@ int acmk_launch_dense_speed(const int16_t *d_src, const AcmDenseRow *d_rows, con
  * then nrows rows of row_len samples to d_out (int16, or float32 = the int16 result times 2^-15 with f32), row r at element
  * r * row_len, by include/acm_hip.h's formula.  Both calls: nothing allocated, nothing waited for; the same kind of loads as
  * acmk_launch_dense_rows */
-int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_marked, uint64_t nmarked, uint64_t row_len, uint64_t *d_energy, void *stream);
+int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_marked, uint64_t nmarked, uint64_t row_len, uint64_t *d_energy, uint32_t dense_grid,
+			     void *stream);
 int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayRow *d_rows, const uint64_t *d_energy, AcmOverlayResult *d_res, uint64_t nrows,
-			      void *d_out, uint64_t row_len, int f32, void *stream);
+			      void *d_out, uint64_t row_len, int f32, uint32_t dense_grid, void *stream);
 #ifdef __cplusplus
 }
 #endif

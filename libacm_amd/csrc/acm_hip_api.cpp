@@ -70,6 +70,7 @@ struct acmhip_device {
 	 * asked of the slot: what acmhip_device_arena_info reports, and with the fill mode on (acmhip_device_set_fill) what has been filled
 	 * for that call */
 	bool fill = false;
+	acmhip_launch_caps caps{};              /* acmhip_device_set_launch_caps: all zero = every built-in value */
 	uint64_t arena_epoch = 0;
 	uint64_t arena_epoch_of[ACM_ARENA_SLOTS] = {};
 	size_t arena_asked[ACM_ARENA_SLOTS] = {};
@@ -314,6 +315,19 @@ extern "C" int acmhip_device_set_fill(acmhip_device *dev, int on)
 	const int was = dev->fill ? 1 : 0;
 	dev->fill = on != 0;
 	return was;
+}
+
+extern "C" int acmhip_device_set_launch_caps(acmhip_device *dev, const acmhip_launch_caps *caps, acmhip_launch_caps *previous)
+{
+	if (!dev)
+		return ACMHIP_ERR_ARG;
+	std::lock_guard<std::mutex> g(dev->arena_mutex);
+	return acmk_launch_caps_set(&dev->caps, caps, previous);
+}
+
+extern "C" acmhip_launch_caps acmhip_device_launch_caps(const acmhip_device *dev)
+{
+	return dev ? dev->caps : acmhip_launch_caps{};
 }
 
 extern "C" int acmhip_device_arena_info(acmhip_device *dev, int slot, const char **name, void **ptr, size_t *bytes, int *is_host, int *fill)
@@ -793,6 +807,7 @@ static int plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhd
 				return ACMHIP_ERR_ARG;
 			}
 
+	const acmhip_launch_caps caps = acmhip_device_launch_caps(pl->dev);    /* plain values from here on: nothing below asks the runtime */
 	const bool spread = pl->ev_fork != nullptr;
 	if (spread) {
 		HIPTRY(hipEventRecord(pl->ev_fork, pl->dev->stream));
@@ -831,34 +846,34 @@ static int plan_launch(acmhip_plan *pl, const int16_t *d_idx, const acmhip_blkhd
 	}
 
 	for (const LevelGroup &g : pl->small)
-		LAUNCHTRY(acmk_launch_small(g.level, pl->d_streams, g.d_list, g.nlist, g.max_emit, d_idx, d_hdr, d_pcm, fmt, st));
+		LAUNCHTRY(acmk_launch_small(g.level, pl->d_streams, g.d_list, g.nlist, g.max_emit, d_idx, d_hdr, d_pcm, fmt, caps.list_slice, caps.small_grid_x, st));
 
 	if (pl->n_sw_all || !pl->prefix.empty()) {
 		if (pl->n_sw_all)
 			LAUNCHTRY(acmk_launch_unpack(pl->d_streams, pl->d_sw_all, pl->n_sw_all, pl->sw_max_elems,
-						     d_idx, d_hdr, pl->d_plane[0], 0, st));
+						     d_idx, d_hdr, pl->d_plane[0], 0, caps.list_slice, st));
 		for (const LevelGroup &g : pl->prefix)
 			if (g.prefix_patched)
-				LAUNCHTRY(acmk_launch_unpack(pl->d_streams, g.d_list, g.nlist, g.max_elems, d_idx, d_hdr, pl->d_plane[0], 16 - g.level, st));
+				LAUNCHTRY(acmk_launch_unpack(pl->d_streams, g.d_list, g.nlist, g.max_elems, d_idx, d_hdr, pl->d_plane[0], 16 - g.level, caps.list_slice, st));
 		LAUNCHTRY(acmk_launch_patch(pl->d_patches, pl->npatches, pl->d_plane[0], st));
 		for (const LevelGroup &g : pl->stagewise) {
 			int cur = 0;
 			for (uint32_t k = 0; k < g.level; k++, cur ^= 1)
 				LAUNCHTRY(acmk_launch_stage(pl->d_streams, g.d_list, g.nlist, g.max_elems, g.level, k,
-							    pl->d_plane[cur], pl->d_plane[cur ^ 1], 0, st));
+							    pl->d_plane[cur], pl->d_plane[cur ^ 1], 0, caps.list_slice, st));
 			LAUNCHTRY(acmk_launch_emit(pl->d_streams, g.d_list, g.nlist, g.max_emit, pl->d_plane[cur],
-						   d_pcm, fmt, st));
+						   d_pcm, fmt, caps.list_slice, st));
 		}
 		for (const LevelGroup &g : pl->prefix) {
 			int cur = 0;
 			if (!g.prefix_patched) {
 				/* unpack and all level - 12 stages in one sweep, straight into the plane the tile kernel reads */
-				LAUNCHTRY(acmk_launch_prefix(pl->d_streams, g.d_list, g.nlist, g.max_elems, g.level, d_idx, d_hdr, pl->d_plane[1], st));
+				LAUNCHTRY(acmk_launch_prefix(pl->d_streams, g.d_list, g.nlist, g.max_elems, g.level, d_idx, d_hdr, pl->d_plane[1], caps.list_slice, st));
 				cur = 1;
 			} else {
 				for (uint32_t k = 0; k < g.prefix_stages; k++, cur ^= 1)
 					LAUNCHTRY(acmk_launch_stage(pl->d_streams, g.d_list, g.nlist, g.max_elems, g.level, k,
-								    pl->d_plane[cur], pl->d_plane[cur ^ 1], 16 - g.level, st));
+								    pl->d_plane[cur], pl->d_plane[cur ^ 1], 16 - g.level, caps.list_slice, st));
 			}
 			LAUNCHTRY(acmk_launch_fused_plane(pl->dev->cus, g.carry, pl->d_streams, g.d_tiles, g.ntiles, pl->d_plane[cur], d_pcm, fmt, st));
 		}

@@ -291,3 +291,22 @@ extern "C" uint32_t acmk_range_bound(uint32_t blocks, uint32_t r, uint32_t R, ui
 {
 	return acm_range_bound(blocks, r, R, unit);
 }
+
+// ---------------------------------------------------------------------------
+// launch caps (acmhip_device_set_launch_caps): the check and the exchange, without a device
+// ---------------------------------------------------------------------------
+extern "C" int acmk_launch_caps_set(acmhip_launch_caps *held, const acmhip_launch_caps *caps, acmhip_launch_caps *previous)
+{
+	if (!held)
+		return ACMHIP_ERR_ARG;
+	const acmhip_launch_caps none{};
+	const acmhip_launch_caps &c = caps ? *caps : none;
+	if (c.list_slice > ACM_CAP_LIST_SLICE || c.small_grid_x > ACM_CAP_SMALL_GRID_X || c.parse_slice > ACM_CAP_PARSE_SLICE ||
+	    c.parse_grid_x > ACM_CAP_PARSE_GRID_X || c.dense_grid > ACM_CAP_DENSE_GRID)
+		return ACMHIP_ERR_ARG;
+	const acmhip_launch_caps was = *held;           /* (previous may be caps itself, or held) */
+	*held = c;
+	if (previous)
+		*previous = was;
+	return ACMHIP_OK;
+}

@@ -3772,8 +3772,9 @@ extern "C" int acmk_warmup(void *stream)
 }
 
 #endif
-/* gridDim.y carries the stream index and is limited to 65535: walk long lists in slices */
-constexpr uint32_t SW_MAX_Y = 65535;
+/* gridDim.y carries the stream index and is limited to 65535: walk long lists in slices (of fewer streams where the handle's launch caps
+ * say so: list_slice of the launchers below, acm_launch_caps.h) */
+constexpr uint32_t SW_MAX_Y = ACM_CAP_LIST_SLICE;
 
 /* a persistent grid (acmk_*_grid: as many workgroups as the chip holds at once), never more than tiles */
 static inline dim3 grid_of(int most, uint32_t ntiles)
@@ -3808,10 +3809,11 @@ extern "C" int ACMK_OUT(acmk_launch_fused)(uint32_t level, int variant, int cus,
  * that finishes them finds a sample in bytes 2..3, as it does for its own levels; 0 everywhere else */
 extern "C" int acmk_launch_unpack(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
 				  uint64_t max_elems, const int16_t *d_idx, const acmhip_blkhdr *d_hdr,
-				  int32_t *d_x, uint32_t shift, void *stream)
+				  int32_t *d_x, uint32_t shift, uint32_t list_slice, void *stream)
 {
-	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
-		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
+	const uint32_t slice = acm_cap_value(list_slice, SW_MAX_Y);
+	for (uint32_t at = 0; at < nlist; at += slice) {
+		const uint32_t n = nlist - at < slice ? nlist - at : slice;
 		hipLaunchKernelGGL(acm_sw_unpack, sw_grid(max_elems, n), dim3(SW_THREADS), 0, (hipStream_t)stream,
 				   d_streams, d_list + at, d_idx, d_hdr, d_x, shift);
 		ACMK_CHECK_LAUNCH();
@@ -3831,10 +3833,11 @@ extern "C" int acmk_launch_patch(const AcmDevPatch *d_patches, uint64_t n, int32
 
 extern "C" int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
 				 uint64_t max_elems, uint32_t level, uint32_t k, const int32_t *d_in,
-				 int32_t *d_out, uint32_t shift, void *stream)
+				 int32_t *d_out, uint32_t shift, uint32_t list_slice, void *stream)
 {
-	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
-		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
+	const uint32_t slice = acm_cap_value(list_slice, SW_MAX_Y);
+	for (uint32_t at = 0; at < nlist; at += slice) {
+		const uint32_t n = nlist - at < slice ? nlist - at : slice;
 		hipLaunchKernelGGL(acm_sw_stage, sw_grid(max_elems, n), dim3(SW_THREADS), 0, (hipStream_t)stream,
 				   d_streams, d_list + at, level, k, d_in, d_out, 1u << shift);
 		ACMK_CHECK_LAUNCH();
@@ -3845,18 +3848,20 @@ extern "C" int acmk_launch_stage(const AcmDevStream *d_streams, const uint32_t *
 #endif
 extern "C" int ACMK_OUT(acmk_launch_small)(uint32_t level, const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
 				 uint64_t max_emit, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm,
-				 unsigned fmt, void *stream)
+				 unsigned fmt, uint32_t list_slice, uint32_t small_grid_x, void *stream)
 {
 #if !ACM_OUT_F32
 	if (fmt & ACMK_FMT_F32)
-		return acmk_launch_small_f32(level, d_streams, d_list, nlist, max_emit, d_idx, d_hdr, d_pcm, fmt & 3u, stream);
+		return acmk_launch_small_f32(level, d_streams, d_list, nlist, max_emit, d_idx, d_hdr, d_pcm, fmt & 3u, list_slice, small_grid_x, stream);
 #endif
 	if (level > ACM_SMALL_MAX_LEVEL)
 		return -1;
 	uint64_t gx = (max_emit + (uint64_t)SL_THREADS * SL_K - 1) / ((uint64_t)SL_THREADS * SL_K);
-	gx = gx < 1 ? 1 : gx > 4096 ? 4096 : gx;
-	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
-		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
+	const uint64_t gx_max = acm_cap_value(small_grid_x, ACM_CAP_SMALL_GRID_X);
+	gx = gx < 1 ? 1 : gx > gx_max ? gx_max : gx;
+	const uint32_t slice = acm_cap_value(list_slice, SW_MAX_Y);
+	for (uint32_t at = 0; at < nlist; at += slice) {
+		const uint32_t n = nlist - at < slice ? nlist - at : slice;
 		const dim3 grid((unsigned)gx, n, 1);
 		switch (level) {
 		case 0: hipLaunchKernelGGL(ACM_K_SMALL<0>, grid, dim3(SL_THREADS), 0, (hipStream_t)stream, d_streams, d_list + at, d_idx, d_hdr, d_pcm, fmt); break;
@@ -3871,14 +3876,15 @@ extern "C" int ACMK_OUT(acmk_launch_small)(uint32_t level, const AcmDevStream *d
 }
 
 extern "C" int ACMK_OUT(acmk_launch_emit)(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist,
-				uint64_t max_emit, const int32_t *d_x, int16_t *d_pcm, unsigned fmt, void *stream)
+				uint64_t max_emit, const int32_t *d_x, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, void *stream)
 {
 #if !ACM_OUT_F32
 	if (fmt & ACMK_FMT_F32)
-		return acmk_launch_emit_f32(d_streams, d_list, nlist, max_emit, d_x, d_pcm, fmt & 3u, stream);
+		return acmk_launch_emit_f32(d_streams, d_list, nlist, max_emit, d_x, d_pcm, fmt & 3u, list_slice, stream);
 #endif
-	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
-		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
+	const uint32_t slice = acm_cap_value(list_slice, SW_MAX_Y);
+	for (uint32_t at = 0; at < nlist; at += slice) {
+		const uint32_t n = nlist - at < slice ? nlist - at : slice;
 		hipLaunchKernelGGL(ACM_K_EMIT, sw_grid(max_emit, n), dim3(SW_THREADS), 0, (hipStream_t)stream,
 				   d_streams, d_list + at, d_x, d_pcm, fmt);
 		ACMK_CHECK_LAUNCH();
@@ -3984,15 +3990,16 @@ extern "C" int ACMK_OUT(acmk_launch_fused_plane)(int cus, int carry, const AcmDe
 
 #if !ACM_OUT_F32
 extern "C" int acmk_launch_prefix(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_elems,
-				 uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, void *stream)
+				 uint32_t level, const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int32_t *d_y, uint32_t list_slice, void *stream)
 {
 	if (level < 13 || level > 15)
 		return (int)hipErrorInvalidValue;
 	const uint64_t rows = max_elems >> level;
 	const uint32_t chunks = (uint32_t)((rows + PREFIX_CHUNK_ROWS - 1) / PREFIX_CHUNK_ROWS);
 	const uint32_t gx = (chunks ? chunks : 1) * (2048 / PREFIX_THREADS);
-	for (uint32_t at = 0; at < nlist; at += SW_MAX_Y) {
-		const uint32_t n = nlist - at < SW_MAX_Y ? nlist - at : SW_MAX_Y;
+	const uint32_t slice = acm_cap_value(list_slice, SW_MAX_Y);
+	for (uint32_t at = 0; at < nlist; at += slice) {
+		const uint32_t n = nlist - at < slice ? nlist - at : slice;
 		auto k = level == 13 ? acm_sw_prefix<1> : level == 14 ? acm_sw_prefix<2> : acm_sw_prefix<3>;
 		hipLaunchKernelGGL(k, dim3(gx, n), dim3(PREFIX_THREADS), 0, (hipStream_t)stream,
 				   d_streams, d_list + at, d_idx, d_hdr, d_y, 16 - level);

@@ -1001,14 +1001,16 @@ extern "C" int acmk_launch_scatter_stripe(const AcmParseJob *d_jobs, uint32_t nj
 }
 
 /* the column kernel behind a walk: `gx` workgroups per stream as the caller sized them, clamped to [1, 2048] (the kernel strides over
- * the grid), the streams along the grid's y in slices of 65535 */
+ * the grid), the streams along the grid's y in slices of 65535 - or to the handle's launch caps where they are lower (acm_launch_caps.h) */
 static int launch_columns(uint64_t gx, const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, const uint32_t *d_colpos, int16_t *d_idx,
 			  const acmhip_blkhdr *d_hdr, const AcmParseResult *d_res, uint32_t *d_flags, uint32_t range, uint32_t nranges, uint8_t *d_mf,
-			  uint32_t *d_pairs, const uint32_t *d_blkoff, hipStream_t st)
+			  uint32_t *d_pairs, const uint32_t *d_blkoff, uint32_t parse_slice, uint32_t parse_grid_x, hipStream_t st)
 {
-	gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
-	for (uint32_t at = 0; at < njobs; at += 65535) {
-		const uint32_t n = njobs - at < 65535 ? njobs - at : 65535;
+	const uint64_t gx_max = acm_cap_value(parse_grid_x, ACM_CAP_PARSE_GRID_X);
+	const uint32_t slice = acm_cap_value(parse_slice, ACM_CAP_PARSE_SLICE);
+	gx = gx < 1 ? 1 : gx > gx_max ? gx_max : gx;
+	for (uint32_t at = 0; at < njobs; at += slice) {
+		const uint32_t n = njobs - at < slice ? njobs - at : slice;
 		hipLaunchKernelGGL(acm_parse_columns, dim3((unsigned)gx, n), dim3(COL_THREADS), 0, st,
 				   d_jobs + at, d_res + at, d_files, d_colpos, d_hdr, d_idx, d_flags + at, range, nranges, d_mf, d_pairs, d_blkoff);
 		ACMP_CHECK();
@@ -1019,17 +1021,17 @@ static int launch_columns(uint64_t gx, const AcmParseJob *d_jobs, uint32_t njobs
 extern "C" int acmk_launch_parse_range(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 				       uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
 				       AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t range, uint32_t nranges,
-				       uint32_t stripes_up, acm_block_mark *d_marks, void *stream)
+				       uint32_t stripes_up, acm_block_mark *d_marks, uint32_t parse_slice, uint32_t parse_grid_x, void *stream)
 {
 	return acmk_launch_parse_range_mf(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, range, nranges, stripes_up,
-					  nullptr, nullptr, nullptr, d_marks, stream);
+					  nullptr, nullptr, nullptr, d_marks, parse_slice, parse_grid_x, stream);
 }
 
 extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 					  uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
 					  AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, uint32_t range, uint32_t nranges,
 					  uint32_t stripes_up, uint8_t *d_mf, uint32_t *d_pairs, uint32_t *d_blkoff, acm_block_mark *d_marks,
-					  void *stream)
+					  uint32_t parse_slice, uint32_t parse_grid_x, void *stream)
 {
 	if (njobs == 0)
 		return 0;
@@ -1074,12 +1076,12 @@ extern "C" int acmk_launch_parse_range_mf(const AcmParseJob *d_jobs, uint32_t nj
 	const uint64_t range_columns = max_columns / nranges + 32768;           /* (the kernel strides over the grid: a bound, not a contract) */
 	const uint64_t gx = ((range_columns < max_columns ? range_columns : max_columns) + COL_THREADS - 1) / COL_THREADS;
 	return launch_columns(gx, d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, range, nranges, mf ? d_mf : nullptr,
-			      mf ? d_pairs : nullptr, mf ? d_blkoff : nullptr, st);
+			      mf ? d_pairs : nullptr, mf ? d_blkoff : nullptr, parse_slice, parse_grid_x, st);
 }
 
 extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njobs, const AcmBlockJob *d_bjobs, uint32_t nblock,
 					const uint8_t *d_files, uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr, AcmParseResult *d_res,
-					uint32_t *d_flags, uint64_t max_columns, void *stream)
+					uint32_t *d_flags, uint64_t max_columns, uint32_t parse_slice, uint32_t parse_grid_x, void *stream)
 {
 	if (njobs == 0 || nblock == 0)
 		return 0;
@@ -1088,7 +1090,7 @@ extern "C" int acmk_launch_parse_blocks(const AcmParseJob *d_jobs, uint32_t njob
 			   d_jobs, d_bjobs, nblock, d_files, d_colpos, d_hdr, d_res);
 	ACMP_CHECK();
 	const uint64_t gx = (max_columns + COL_THREADS - 1) / COL_THREADS;
-	return launch_columns(gx, d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, 0u, 1u, nullptr, nullptr, nullptr, st);
+	return launch_columns(gx, d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, 0u, 1u, nullptr, nullptr, nullptr, parse_slice, parse_grid_x, st);
 }
 
 extern "C" int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files, acm_block_mark *d_marks, AcmParseResult *d_res,
@@ -1106,7 +1108,9 @@ extern "C" int acmk_launch_index(const AcmParseJob *d_jobs, uint32_t njobs, cons
 
 extern "C" int acmk_launch_parse(const AcmParseJob *d_jobs, uint32_t njobs, const uint8_t *d_files,
 				 uint32_t *d_colpos, int16_t *d_idx, acmhip_blkhdr *d_hdr,
-				 AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, void *stream)
+				 AcmParseResult *d_res, uint32_t *d_flags, uint64_t max_columns, acm_block_mark *d_marks, uint32_t parse_slice, uint32_t parse_grid_x,
+				 void *stream)
 {
-	return acmk_launch_parse_range(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, 0, 1, 0, d_marks, stream);
+	return acmk_launch_parse_range(d_jobs, njobs, d_files, d_colpos, d_idx, d_hdr, d_res, d_flags, max_columns, 0, 1, 0, d_marks, parse_slice, parse_grid_x,
+				       stream);
 }
