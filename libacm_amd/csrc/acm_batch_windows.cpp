@@ -17,10 +17,10 @@
  *
  * acm_batch_decode_windows_dense is the same run with another end: the windows are synthesised into the handle's own PCM arena, nothing
  * is read back, and one launch of acm_dense_rows (acm_dense.hip) lays them out as the rows of the caller's tensor.  What that call
- * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's - also whether, with ACM_DENSE_MIX, a row
- * of the table converts between mono and stereo: then the launch is acm_dense_mixed's (acm_dense_mix.hip) instead - and whether, with
- * ACM_DENSE_RESAMPLE, a row is filtered to the batch's sample rate: then a second table and the ratios' taps travel with the first and
- * the launch is acm_dense_resample's (acm_dense_resample.hip).
+ * accepts, which windows it turns away and the kernel's row table are acm_dense_layout.cpp's - also, in one function
+ * (acm_dense_tables), which kernel takes the launch: acm_dense_mixed's (acm_dense_mix.hip) where, with ACM_DENSE_MIX, a row of the
+ * table converts between mono and stereo; acm_dense_resample's or acm_dense_speed's where, with ACM_DENSE_RESAMPLE and
+ * ACM_DENSE_SPEED, a row is filtered to the batch's sample rate: then a second table and the ratios' taps travel with the first.
  *
  * acm_batch_decode_windows_overlay is the dense run with its gather launch aimed at the handle's source arena instead of the caller's
  * tensor, and two launches of acm_dense_overlay.hip behind it that make the caller's rows from those: which source rows get an
@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <optional>
 #include <vector>
 
 #include "acm_batch_common.h"
@@ -312,19 +313,10 @@ int WinRun::synthesise_and_gather()
 	if (!ps.descs.empty())
 		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
 	const size_t at = dense->table_off(L);
-	/* what staging left decides the kernel: acm_dense_rows unless a row converts (ACM_DENSE_MIX), is filtered (ACM_DENSE_RESAMPLE) or
-	 * takes the wide filter (ACM_DENSE_SPEED); only a call that filters sends the second table and the taps */
-	AcmDenseRow *rows = reinterpret_cast<AcmDenseRow *>(h_jobs + at);
-	const bool mixed = acm_dense_rows(*dense, L.slots.data(), wins, rows);
-	void *second = h_jobs + at + dense->resample_off();
-	int16_t *taps = reinterpret_cast<int16_t *>(h_jobs + at + dense->taps_off());
-	const bool wide = !dense->tables.empty() && acm_dense_wide_rows(*dense, rows);
-	if (wide)
-		acm_dense_speed_rows(*dense, rows, static_cast<AcmSpeedRow *>(second), taps);
-	const bool filters = wide || (!dense->tables.empty() && acm_dense_resample_rows(*dense, rows, static_cast<AcmResampleRow *>(second), taps));
-	const size_t bytes = filters ? dense->table_bytes() : dense->row_table_bytes();
-	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, bytes, hipMemcpyHostToDevice, st));
-	tm.h2d_bytes += bytes;
+	/* what staging left decides the kernel and how much of the tables it reads (acm_dense_layout.cpp) */
+	const DenseLaunch gather = acm_dense_tables(*dense, L.slots.data(), wins, h_jobs + at);
+	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, gather.bytes, hipMemcpyHostToDevice, st));
+	tm.h2d_bytes += gather.bytes;
 	if (overlay && overlay->upload_bytes()) {
 		uint8_t *up = h_jobs + overlay_off();
 		memcpy(up, overlay->rows.data(), overlay->rows_bytes());
@@ -342,15 +334,30 @@ int WinRun::synthesise_and_gather()
 	void *const rows_out = overlay ? d_src : dense_out;
 	const bool rows_f32 = overlay ? false : dense->f32;
 	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
-	const int e = wide ? acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out,
-						     dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st)
-		      : filters ? acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out,
-							     dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st)
-				: (mixed ? acmk_launch_dense_mixed : acmk_launch_dense_rows)(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames,
-											     dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+	int e = 0;
+	const char *name = nullptr;
+	switch (gather.kernel) {
+	case DENSE_SPEED:
+		name = "acmk_launch_dense_speed";
+		e = acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out, dense->frames,
+					    dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		break;
+	case DENSE_RESAMPLE:
+		name = "acmk_launch_dense_resample";
+		e = acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out, dense->frames,
+					       dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		break;
+	case DENSE_MIXED:
+		name = "acmk_launch_dense_mixed";
+		e = acmk_launch_dense_mixed(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		break;
+	case DENSE_PLAIN:
+		name = "acmk_launch_dense_rows";
+		e = acmk_launch_dense_rows(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		break;
+	}
 	if (e != 0)
-		return acmhip_report_hip(e, wide ? "acmk_launch_dense_speed" : filters ? "acmk_launch_dense_resample" : mixed ? "acmk_launch_dense_mixed"
-													      : "acmk_launch_dense_rows");
+		return acmhip_report_hip(e, name);
 	if (overlay)
 		ACM_TRY(combine_rows());
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
@@ -446,27 +453,56 @@ extern "C" uint64_t acm_batch_window_pcm_words(const acm_batch_item *items, size
 	return total;
 }
 
-/* the call without its wall clock: the caller reads that once everything held here is released */
+/* what every windowed call begins with: the arguments that must be there, the options with their defaults filled in, a pool sized for
+ * the call's items and windows, and the items' headers */
+struct Prelude {
+	acm_batch_opts opts{};
+	std::optional<Pool> pool;
+	std::vector<WindowItem> its;
+	int begin(const acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, const acm_batch_window *wins, size_t nwin,
+		  const acm_batch_opts *opts_in)
+	{
+		if (!dev)
+			return ACMHIP_ERR_NO_DEVICE;
+		if ((n && (!items || !index)) || (nwin && !wins))
+			return ACMHIP_ERR_ARG;
+		if (opts_in)
+			opts = *opts_in;
+		const int threads_wanted = opts.threads > 0 ? opts.threads : default_threads();
+		pool.emplace((int)std::min<size_t>((size_t)threads_wanted, std::max<size_t>(1, std::max(n, nwin))));
+		its = probe_items(*pool, items, n, index, opts.force_chans);
+		return ACMHIP_OK;
+	}
+};
+
+/* an entry point's wall clock around `call`, which fills in the rest: read once everything the call held is released.  A call that
+ * fails leaves *timing alone */
+template <typename F> int timed(acm_window_timing *timing, F &&call)
+{
+	acm_window_timing tm{};
+	const auto t0 = clk::now();
+	ACM_TRY(call(tm));
+	tm.total_s = secs(t0, clk::now());
+	if (timing)
+		*timing = tm;
+	return ACMHIP_OK;
+}
+
+/* the call without its wall clock */
 static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
 			  size_t nwin, const acm_batch_opts *opts_in, acm_window_timing &tm)
 {
-	if (!dev)
-		return ACMHIP_ERR_NO_DEVICE;
-	if ((n && (!items || !index)) || (nwin && !wins))
-		return ACMHIP_ERR_ARG;
-	acm_batch_opts opts{};
-	if (opts_in)
-		opts = *opts_in;
+	Prelude pre;
+	ACM_TRY(pre.begin(dev, items, n, index, wins, nwin, opts_in));
+	const acm_batch_opts &opts = pre.opts;
+	const std::vector<WindowItem> &its = pre.its;
+	Pool &pool = *pre.pool;
 	if (opts.fmt > 3 || opts.parse > ACM_BATCH_PARSE_AUTO || opts.prestaged || (opts.flags & ACM_BATCH_STAGE_PACKED))
 		return ACMHIP_ERR_ARG;
 	if ((opts.flags & ACM_BATCH_PCM_F32) && (!opts.d_pcm || opts.fmt != ACMHIP_FMT_S16LE)) {
 		acmhip_set_error_text("ACM_BATCH_PCM_F32: device-resident output (opts->d_pcm) and ACMHIP_FMT_S16LE");
 		return ACMHIP_ERR_ARG;
 	}
-	const int threads_wanted = opts.threads > 0 ? opts.threads : default_threads();
-	Pool pool((int)std::min<size_t>((size_t)threads_wanted, std::max<size_t>(1, std::max(n, nwin))));
-
-	const std::vector<WindowItem> its = probe_items(pool, items, n, index, opts.force_chans);
 	WindowLayout layout;
 	const int laid = acm_window_layout(its.data(), n, wins, nwin, opts, &layout, &pool);
 	for (size_t k = 0; k < nwin; k++) {             /* a refused call has told its windows their status and slots too */
@@ -494,17 +530,11 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm, bool with_overlay = false,
 				acm_overlay_row *rows = nullptr, size_t nrows = 0)
 {
-	if (!dev)
-		return ACMHIP_ERR_NO_DEVICE;
-	if ((n && (!items || !index)) || (nwin && !wins))
-		return ACMHIP_ERR_ARG;
-	acm_batch_opts opts{};
-	if (opts_in)
-		opts = *opts_in;
-	const int threads_wanted = opts.threads > 0 ? opts.threads : default_threads();
-	Pool pool((int)std::min<size_t>((size_t)threads_wanted, std::max<size_t>(1, std::max(n, nwin))));
-
-	const std::vector<WindowItem> its = probe_items(pool, items, n, index, opts.force_chans);
+	Prelude pre;
+	ACM_TRY(pre.begin(dev, items, n, index, wins, nwin, opts_in));
+	const acm_batch_opts &opts = pre.opts;
+	const std::vector<WindowItem> &its = pre.its;
+	Pool &pool = *pre.pool;
 	DenseLayout D;
 	/* the room behind d_pcm is measured against the output rows of an overlay call, by its own layout */
 	acm_batch_opts asked = opts;
@@ -542,36 +572,18 @@ extern "C" int acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batc
 					      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 					      acm_window_timing *timing)
 {
-	acm_window_timing tm{};
-	const auto t0 = clk::now();
-	ACM_TRY(decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm));
-	tm.total_s = secs(t0, clk::now());
-	if (timing)
-		*timing = tm;
-	return ACMHIP_OK;
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm); });
 }
 
 extern "C" int acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 						acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 						acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
 {
-	acm_window_timing tm{};
-	const auto t0 = clk::now();
-	ACM_TRY(decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows));
-	tm.total_s = secs(t0, clk::now());
-	if (timing)
-		*timing = tm;
-	return ACMHIP_OK;
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows); });
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 					acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, acm_window_timing *timing)
 {
-	acm_window_timing tm{};
-	const auto t0 = clk::now();
-	ACM_TRY(decode_windows(dev, items, n, index, wins, nwin, opts_in, tm));
-	tm.total_s = secs(t0, clk::now());
-	if (timing)
-		*timing = tm;
-	return ACMHIP_OK;
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows(dev, items, n, index, wins, nwin, opts_in, tm); });
 }

@@ -1,7 +1,7 @@
 /*
- * acm_dense_filter.h - what acm_dense_resample.hip and acm_dense_speed.hip share: one unit of one sub-row of a dense crop batch, for
- * a row that is not filtered (acm_dense_mix.hip's gather) and for a row that is - by the exact polyphase table of ACM_DENSE_RESAMPLE
- * or, WIDE, by the interpolated table of ACM_DENSE_SPEED (include/acm_hip.h).  Device code, in an unnamed namespace of the
+ * acm_dense_filter.h - what acm_dense_resample.hip and acm_dense_speed.hip share: one unit of one sub-row of a dense crop batch for
+ * a row that is filtered - by the exact polyphase table of ACM_DENSE_RESAMPLE or, WIDE, by the interpolated table of ACM_DENSE_SPEED
+ * (include/acm_hip.h); a row that is not filtered takes acm_dense_gather.h's gather.  Device code, in an unnamed namespace of the
  * including file.
  *
  * The exact filter, on integers: for output frame j of a channel,
@@ -18,7 +18,7 @@
  *      and de-interleave, down-mix or duplicate on the way into LDS;
  *   3. has every lane filter its 8 consecutive outputs from LDS - base and phase by one division (WIDE: one 64-bit multiply) a lane,
  *      then by stepping - and store them as whole 16-byte lines where the output is aligned; the up to 7 samples in front of a row's
- *      first line and behind its last one are single outputs with narrow stores, as in acm_dense_mix.hip.
+ *      first line and behind its last one are single outputs with narrow stores, as in acm_dense_gather.h.
  *
  * Table and planes share 63 KB of LDS, so two workgroups fit a CU's 160 KB.  The planes hold SPAN_CAP samples; a unit whose span is
  * longer (M / L above about 7.5: two planes hold half the frames each) is worked off in 2, 4, ... passes of 1024, 512, ... outputs,
@@ -28,95 +28,12 @@
 #ifndef ACM_DENSE_FILTER_H
 #define ACM_DENSE_FILTER_H
 
-#include "acm_dense_vec.h"
-#include "acm_device.h"
+#include "acm_dense_gather.h"
 
 namespace {
 
-enum Layout { MONO = 0, INTER = 1, PLANAR = 2 };
-enum Path { COPY, SPLIT, DOWN, UP_INTER };      /* what a sub-row that is not filtered does with its source: acm_dense_mix.hip's */
-
 constexpr uint32_t TAB_CAP = 16384;             /* int16 of a ratio's table: ACM_RESAMPLE_MAX_TAPS */
 constexpr uint32_t SPAN_CAP = 15872;            /* int16 of the staged planes: with the table 63 KB */
-constexpr uint32_t UNIT = DENSE_BLOCK * DENSE_VEC;
-
-/* ------------------------------------------------------------------------------------------------ rows that are not filtered */
-
-/* output sample e of a sub-row whose source starts at sub, e below what the sub-row has */
-template <Path P> __device__ __forceinline__ int sample(const int16_t *sub, uint64_t e)
-{
-	if (P == COPY)
-		return sub[e];
-	if (P == SPLIT)
-		return sub[2 * e];
-	if (P == DOWN)
-		return ((int)sub[2 * e] + (int)sub[2 * e + 1]) >> 1;
-	return sub[e >> 1];
-}
-
-/* one unit of one sub-row: `have` output samples from `sub`, zeros behind them up to sub_len - acm_dense_mix.hip's, line for line */
-template <typename OUT, Path P>
-__device__ __forceinline__ void sub_row(const int16_t *sub, uint64_t have, OUT *o, uint64_t sub_len, uint32_t unit, uint32_t units)
-{
-	constexpr int PER_LANE = P == UP_INTER ? 2 : 1;
-	const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
-	const uint64_t head = to_line < sub_len ? to_line : sub_len;
-	const uint64_t nvec = (sub_len - head) / DENSE_VEC;
-	const uint64_t tail = head + nvec * DENSE_VEC;
-	const int16_t *first = P == COPY ? sub + head : P == UP_INTER ? sub + head / 2 : sub + 2 * head;
-	const uint32_t sh = (uint32_t)reinterpret_cast<uintptr_t>(first) & 15u;
-	const uint32_t odd = P == UP_INTER ? (uint32_t)head & 1u : 0;
-
-	const uint64_t v = ((uint64_t)unit * DENSE_BLOCK + threadIdx.x) * PER_LANE;
-	if (v < nvec) {
-		const uint64_t e = head + v * DENSE_VEC;
-		const bool two = PER_LANE == 2 && v + 1 < nvec;
-		const uint32_t outs = two ? 2 * DENSE_VEC : DENSE_VEC;
-		int s[PER_LANE][DENSE_VEC];
-		if (e + outs <= have) {
-			if (P == COPY) {
-				load_vec<1>(sub + e, sh, s[0]);
-			} else if (P == SPLIT) {
-				load_vec<2>(sub + 2 * e, sh, s[0]);
-			} else if (P == DOWN) {
-				uint32_t d[DENSE_VEC];
-				load_dwords<DENSE_VEC, 3>(sub + 2 * e, sh, 32, d);
-#pragma unroll
-				for (int i = 0; i < DENSE_VEC; i++)
-					s[0][i] = ((int)(int16_t)(d[i] & 0xFFFFu) + (int)(int16_t)(d[i] >> 16)) >> 1;
-			} else {
-				uint32_t d[5];
-				load_dwords<5, 2>(sub + e / 2, sh, outs + 2 * odd, d);
-				int t[10];
-#pragma unroll
-				for (int j = 0; j < 5; j++) {
-					t[2 * j] = (int16_t)(d[j] & 0xFFFFu);
-					t[2 * j + 1] = (int16_t)(d[j] >> 16);
-				}
-#pragma unroll
-				for (int i = 0; i < PER_LANE * DENSE_VEC; i++)
-					s[i / DENSE_VEC][i % DENSE_VEC] = odd ? t[(i + 1) / 2] : t[i / 2];
-			}
-		} else {
-#pragma unroll
-			for (int i = 0; i < PER_LANE * DENSE_VEC; i++)
-				s[i / DENSE_VEC][i % DENSE_VEC] = i < outs && e + i < have ? sample<P>(sub, e + i) : 0;
-		}
-		store_vec<false>(o + e, s[0]);
-		if (two)
-			store_vec<false>(o + e + DENSE_VEC, s[PER_LANE - 1]);
-	}
-	if (unit == 0 && threadIdx.x < head) {
-		const uint64_t e = threadIdx.x;
-		o[e] = to_out(o, e < have ? sample<P>(sub, e) : 0);
-	}
-	if (unit == units - 1 && tail + threadIdx.x < sub_len) {
-		const uint64_t e = tail + threadIdx.x;
-		o[e] = to_out(o, e < have ? sample<P>(sub, e) : 0);
-	}
-}
-
-/* ------------------------------------------------------------------------------------------------ rows that are filtered */
 
 /* K products from the table and a plane, rounded and saturated */
 __device__ __forceinline__ int filter_one(const int16_t *tab, const int16_t *x, uint32_t K)
@@ -176,17 +93,15 @@ __device__ __forceinline__ void filtered_sub_row(const int16_t *from, bool conve
 			l[i] = g[i];
 	}
 
-	/* the sub-row as acm_dense_mixed cuts it: [0, head) in front of the first aligned output line, nvec vectors, [tail, sub_len) */
-	const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
-	const uint64_t head = to_line < sub_len ? to_line : sub_len;
-	const uint64_t nvec = (sub_len - head) / DENSE_VEC;
-	const uint64_t tail = head + nvec * DENSE_VEC;
+	/* the sub-row as every gather cuts it: [0, head) in front of the first aligned output line, whole vectors, [tail, sub_len) */
+	const SubCut c = cut_sub_row(o, sub_len);
+	const uint64_t head = c.head, tail = c.tail;
 	const uint64_t n_el = min(sub_len, r.n_out * EPF);              /* elements behind these are zero */
-	const uint64_t bs = head + (uint64_t)unit * UNIT, be = min(bs + UNIT, tail);   /* the unit's vectors: elements [bs, be) */
+	const uint64_t bs = head + (uint64_t)unit * DENSE_UNIT, be = min(bs + DENSE_UNIT, tail);       /* the unit's vectors: elements [bs, be) */
 
 	/* outputs a pass: as many as keep the planes inside SPAN_CAP, the up to 7 + 7 single outputs of a row's ends included.  n frames
 	 * are centred on at most ceil(n * M / L) source frames - by the fixed-point bases, floor(n * step / 2^32) + 1 */
-	uint32_t P = UNIT;
+	uint32_t P = DENSE_UNIT;
 	auto reach = [&](uint64_t n) { return WIDE ? ((n * step) >> 32) + 1 : (n * M + L - 1) / L; };
 	while (EPF * (reach((uint64_t)(P + 16) / EPF) + K + 2) > SPAN_CAP)
 		P >>= 1;
@@ -366,53 +281,6 @@ __device__ __forceinline__ void filtered_sub_row(const int16_t *from, bool conve
 			break;
 		__syncthreads();                                         /* the next pass stages over these planes */
 	}
-}
-
-/* one unit of one sub-row of a row that is not filtered: copied, split, down- or up-mixed as acm_dense_mixed does it.  count: the
- * row's source samples */
-template <typename OUT, int LAYOUT>
-__device__ __forceinline__ void plain_sub_row(const int16_t *from, bool converts, uint64_t count, uint32_t plane, OUT *o, uint64_t sub_len,
-					      uint32_t unit, uint32_t units)
-{
-	if (LAYOUT == MONO) {
-		if (converts)
-			sub_row<OUT, DOWN>(from, count / 2, o, sub_len, unit, units);
-		else
-			sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
-	} else if (LAYOUT == INTER) {
-		if (converts)
-			sub_row<OUT, UP_INTER>(from, 2 * count, o, sub_len, unit, units);
-		else
-			sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
-	} else {
-		if (converts)
-			sub_row<OUT, COPY>(from, count, o, sub_len, unit, units);
-		else
-			sub_row<OUT, SPLIT>(from + plane, (count + 1 - plane) / 2, o, sub_len, unit, units);
-	}
-}
-
-/* the launch of either kernel: one workgroup per (row, sub-row, unit), a flat grid that strides over them */
-struct FilterGeo {
-	int layout;
-	uint64_t row_len, sub_len, nwork;
-	uint32_t units, grid;
-	bool ok;                                /* false: more work than the kernels' counters hold */
-};
-inline FilterGeo filter_geo(uint64_t nrows, uint64_t frames, uint32_t channels, int planar, uint32_t dense_grid)
-{
-	FilterGeo g{};
-	g.layout = channels == 1 ? MONO : planar ? PLANAR : INTER;
-	const int subs = g.layout == PLANAR ? 2 : 1;
-	g.row_len = frames * channels;
-	g.sub_len = subs == 2 ? frames : g.row_len;
-	const uint64_t units = (g.sub_len / DENSE_VEC + DENSE_BLOCK - 1) / DENSE_BLOCK;
-	g.ok = units <= 0x7FFFFFFFull && nrows <= ~0ull / ((units ? units : 1) * subs);
-	g.units = (uint32_t)(units ? units : 1);
-	g.nwork = g.ok ? nrows * g.units * subs : 0;
-	const uint32_t most = acm_cap_value(dense_grid, DENSE_MAX_GRID);         /* the handle's launch cap, 0 = built-in */
-	g.grid = (uint32_t)(g.nwork < most ? g.nwork : most);
-	return g;
 }
 
 } // namespace

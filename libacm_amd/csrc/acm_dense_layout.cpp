@@ -6,6 +6,8 @@
  */
 #include "acm_dense_layout.h"
 
+#include <string.h>
+
 namespace acmbatch {
 
 int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window *wins, size_t nwin, const acm_batch_opts &opts,
@@ -225,6 +227,23 @@ void acm_dense_speed_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmSpee
 	copy_taps(D, taps);
 }
 
+DenseLaunch acm_dense_tables(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, uint8_t *table)
+{
+	AcmDenseRow *rows = reinterpret_cast<AcmDenseRow *>(table);
+	const bool mixed = acm_dense_rows(D, slots, final, rows);
+	if (!D.tables.empty()) {
+		void *second = table + D.resample_off();
+		int16_t *taps = reinterpret_cast<int16_t *>(table + D.taps_off());
+		if (acm_dense_wide_rows(D, rows)) {
+			acm_dense_speed_rows(D, rows, static_cast<AcmSpeedRow *>(second), taps);
+			return DenseLaunch{ DENSE_SPEED, D.table_bytes() };
+		}
+		if (acm_dense_resample_rows(D, rows, static_cast<AcmResampleRow *>(second), taps))
+			return DenseLaunch{ DENSE_RESAMPLE, D.table_bytes() };
+	}
+	return DenseLaunch{ mixed ? DENSE_MIXED : DENSE_PLAIN, D.row_table_bytes() };
+}
+
 } // namespace acmbatch
 
 extern "C" int acmk_dense_layout_visit(const acm_stage_info *info, const uint64_t *len, const uint8_t *ok, const int32_t *end_status,
@@ -273,38 +292,50 @@ extern "C" int acmk_dense_speed_layout_visit(const acm_stage_info *info, const u
 			if (final_words)
 				wins[k].words = final_words[k];
 		}
-		std::vector<AcmDenseRow> rows(nwin);
-		const bool converts = acm_dense_rows(D, L.slots.data(), wins.data(), rows.data());
+		/* the tables as the driver fills them, and the kernel it launches */
+		std::vector<uint8_t> table(D.table_bytes());
+		const DenseLaunch launch = acm_dense_tables(D, L.slots.data(), wins.data(), table.data());
+		const AcmDenseRow *rows = reinterpret_cast<const AcmDenseRow *>(table.data());
+		/* row k's record of the second table, where the launch reads one: an AcmResampleRow is the head of an AcmSpeedRow that is not wide */
+		auto second = [&](size_t k) {
+			AcmSpeedRow r{};
+			const uint8_t *at = table.data() + D.resample_off();
+			if (launch.kernel == DENSE_SPEED)
+				memcpy(&r, at + k * sizeof(AcmSpeedRow), sizeof(AcmSpeedRow));
+			else if (launch.kernel == DENSE_RESAMPLE)
+				memcpy(&r, at + k * sizeof(AcmResampleRow), sizeof(AcmResampleRow));
+			return r;
+		};
+		/* ... and its frames where it is not filtered */
+		auto frames_of = [&](size_t k) {
+			const uint32_t c = (rows[k].count >> ACM_DENSE_MODE_SHIFT) ? 3 - D.channels : D.channels;
+			return (rows[k].count & ACM_DENSE_COUNT_MASK) / c;
+		};
 		if (nwin) {
 			visit(ctx, "wins", w.data(), 3 * sizeof(uint64_t), nwin);
 			visit(ctx, "rejected", rej.data(), sizeof(uint64_t), nwin);
 			visit(ctx, "report", rep.data(), 5 * sizeof(uint64_t), nwin);
-			visit(ctx, "rows", rows.data(), sizeof(AcmDenseRow), nwin);
+			visit(ctx, "rows", rows, sizeof(AcmDenseRow), nwin);
 		}
 		if (D.mix) {
 			std::vector<uint64_t> mix(D.mode.begin(), D.mode.end());
+			bool converts = false;
+			for (size_t k = 0; k < nwin; k++)
+				converts |= (rows[k].count >> ACM_DENSE_MODE_SHIFT) != 0;
 			mix.push_back(converts);
 			visit(ctx, "mix", mix.data(), sizeof(uint64_t), mix.size());
 		}
 		if (D.speed) {
-			const bool any = !D.tables.empty(), wide = any && acm_dense_wide_rows(D, rows.data());
-			std::vector<AcmSpeedRow> sp(nwin);
-			std::vector<int16_t> taps(any ? D.tap_at(D.tables.size()) : 0);
-			bool filters = false;
-			if (any)
-				acm_dense_speed_rows(D, rows.data(), sp.data(), taps.data());
 			std::vector<uint64_t> res, tabs;
 			for (size_t k = 0; k < nwin; k++) {
-				const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
-				const uint32_t c = (rows[k].count >> ACM_DENSE_MODE_SHIFT) ? 3 - D.channels : D.channels;
-				filters |= sp[k].L != 0;
-				if (sp[k].L)
-					res.insert(res.end(), { sp[k].wide ? 2ull : 1ull, (uint64_t)sp[k].L, (uint64_t)sp[k].M, (uint64_t)D.ratio[k], sp[k].n_out,
-								sp[k].step, (uint64_t)sp[k].b, (uint64_t)sp[k].Wd });
+				const AcmSpeedRow r = second(k);
+				if (r.L)
+					res.insert(res.end(), { r.wide ? 2ull : 1ull, (uint64_t)r.L, (uint64_t)r.M, (uint64_t)D.ratio[k], r.n_out, r.step, (uint64_t)r.b,
+								(uint64_t)r.Wd });
 				else
-					res.insert(res.end(), { D.bad_ratio[k] ? ~0ull : 0ull, (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, count / c, 0, 0, 0 });
+					res.insert(res.end(), { D.bad_ratio[k] ? ~0ull : 0ull, (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, frames_of(k), 0, 0, 0 });
 			}
-			res.insert(res.end(), { wide ? 2ull : filters ? 1ull : 0ull, 0, 0, 0, 0, 0, 0, 0 });
+			res.insert(res.end(), { launch.kernel == DENSE_SPEED ? 2ull : launch.kernel == DENSE_RESAMPLE ? 1ull : 0ull, 0, 0, 0, 0, 0, 0, 0 });
 			for (size_t id = 0; id < D.tables.size(); id++) {
 				const ResampleTable &t = *D.tables[id];
 				tabs.insert(tabs.end(), { (uint64_t)t.wide, (uint64_t)t.c, (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd,
@@ -313,19 +344,15 @@ extern "C" int acmk_dense_speed_layout_visit(const acm_stage_info *info, const u
 			visit(ctx, "speed", res.data(), 8 * sizeof(uint64_t), nwin + 1);
 			visit(ctx, "speed_tables", tabs.data(), 8 * sizeof(uint64_t), D.tables.size());
 		} else if (D.resample) {
-			std::vector<AcmResampleRow> rs(nwin);
-			std::vector<int16_t> taps(D.tables.empty() ? 0 : D.tap_at(D.tables.size()));
-			const bool filters = !D.tables.empty() && acm_dense_resample_rows(D, rows.data(), rs.data(), taps.data());
 			std::vector<uint64_t> res, tabs;
 			for (size_t k = 0; k < nwin; k++) {
-				const uint64_t count = rows[k].count & ACM_DENSE_COUNT_MASK;
-				const uint32_t c = (rows[k].count >> ACM_DENSE_MODE_SHIFT) ? 3 - D.channels : D.channels;
-				if (rs[k].L)
-					res.insert(res.end(), { (uint64_t)rs[k].L, (uint64_t)rs[k].M, (uint64_t)D.ratio[k], rs[k].n_out, 0 });
+				const AcmSpeedRow r = second(k);
+				if (r.L)
+					res.insert(res.end(), { (uint64_t)r.L, (uint64_t)r.M, (uint64_t)D.ratio[k], r.n_out, 0 });
 				else
-					res.insert(res.end(), { (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, count / c, (uint64_t)D.bad_ratio[k] });
+					res.insert(res.end(), { (uint64_t)!D.bad_ratio[k], (uint64_t)!D.bad_ratio[k], ~0ull, frames_of(k), (uint64_t)D.bad_ratio[k] });
 			}
-			res.insert(res.end(), { (uint64_t)filters, 0, 0, 0, 0 });
+			res.insert(res.end(), { (uint64_t)(launch.kernel == DENSE_RESAMPLE), 0, 0, 0, 0 });
 			for (size_t id = 0; id < D.tables.size(); id++) {
 				const ResampleTable &t = *D.tables[id];
 				tabs.insert(tabs.end(), { (uint64_t)D.table_rate[id], (uint64_t)t.r.L, (uint64_t)t.r.M, (uint64_t)t.r.K, (uint64_t)t.r.Wd, (uint64_t)D.tap_at(id) });

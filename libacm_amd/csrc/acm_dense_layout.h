@@ -1,7 +1,7 @@
 /*
  * acm_dense_layout.h - the device-free half of acm_batch_decode_windows_dense (acm_batch_windows.cpp): whether the call is one the
  * dense writer takes, which windows it turns away softly, how large the output is, and - once staging has settled what every
- * window delivers - the row table the gather kernel (acm_dense.hip; acm_dense_mix.hip where a row converts) reads.  Internal.
+ * window delivers - the tables the gather kernel reads and which of the four kernels that is (acm_dense_tables).  Internal.
  * Neither this header nor acm_dense_layout.cpp knows a device (tests/test_dense_crops.py); where a window's samples sit in the
  * intermediate arena stays acm_window_layout.cpp's.
  */
@@ -74,18 +74,28 @@ int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window 
 /* what the caller's window k receives, from its slot of the layout underneath */
 void acm_dense_report(const DenseLayout &D, const WindowSlot &s, size_t k, acm_batch_window *w);
 
-/* the row table: final[k].words is what window k delivers after staging (0: the host stager turned it away).  Returns whether a row
- * converts: then the table is acm_dense_mix.hip's to read, else it is - bit for bit what a call without ACM_DENSE_MIX makes -
- * acm_dense.hip's */
+/* Which kernel takes the gather launch, and how much of the table region goes up with it - decided here, once, by what staging left of
+ * every window: final[k].words is what window k delivers (0: the host stager turned it away).  `table`: table_bytes() of the jobs
+ * arena, 16-byte aligned.  The row table is always filled and goes up; the second table (at resample_off()) and the taps (at taps_off())
+ * go up with it for DENSE_RESAMPLE - AcmResampleRow records - and DENSE_SPEED - AcmSpeedRow records -, the kernels that read them */
+enum DenseKernel {
+	DENSE_PLAIN = 0,        /* acm_dense_rows: no row converts, none is filtered */
+	DENSE_MIXED = 1,        /* acm_dense_mixed: a row converts between mono and stereo (ACM_DENSE_MIX) */
+	DENSE_RESAMPLE = 2,     /* acm_dense_resample: a row that got samples is filtered (ACM_DENSE_RESAMPLE), by the exact filter */
+	DENSE_SPEED = 3,        /* acm_dense_speed: ... by the wide one (ACM_DENSE_SPEED) */
+};
+struct DenseLaunch {
+	DenseKernel kernel;
+	size_t bytes;           /* of `table`, from its start */
+};
+DenseLaunch acm_dense_tables(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, uint8_t *table);
+
+/* Its steps.  The row table; returns whether a row converts - else the table is, bit for bit, what a call without ACM_DENSE_MIX makes */
 bool acm_dense_rows(const DenseLayout &D, const WindowSlot *slots, const acm_batch_window *final, AcmDenseRow *rows);
-
 /* ACM_DENSE_RESAMPLE, for a layout with tables: the second table, from the first one (a row that got no samples is not filtered), and
- * the taps behind it (tap_at(tables.size()) words).  Returns whether a row is filtered: then the three tables are
- * acm_dense_resample.hip's to read, else the first alone is the kernel's that acm_dense_rows chose */
+ * the taps behind it (tap_at(tables.size()) words).  Returns whether a row is filtered */
 bool acm_dense_resample_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmResampleRow *rs, int16_t *taps);
-
-/* ACM_DENSE_SPEED: whether a row that got samples takes the wide filter.  Then the second table is acm_dense_speed_rows' - the same
- * for acm_dense_speed.hip, which reads all three - else the call goes on as it does without the flag */
+/* ACM_DENSE_SPEED: whether a row that got samples takes the wide filter, and the second table and the taps of a call in which one does */
 bool acm_dense_wide_rows(const DenseLayout &D, const AcmDenseRow *rows);
 void acm_dense_speed_rows(const DenseLayout &D, const AcmDenseRow *rows, AcmSpeedRow *sp, int16_t *taps);
 

@@ -4,18 +4,18 @@
  * and a second crop laid over the first at a signal-to-noise ratio).
  *
  * No counterpart in the reference.  The source rows lie in an arena of the handle's own, row k at sample k * R - any 2-byte alignment
- * - as int16, written by the gather launch in front of these on the same stream.  The two large kernels stand on acm_dense_vec.h's unit
- * geometry: 256 lanes, 8 samples a lane, 2048 samples a unit, aligned 16-byte line loads funnelled by a shift that is the same for
- * every vector of a row.
+ * - as int16, written by the gather launch in front of these on the same stream.  The two large kernels stand on the dense kernels'
+ * unit (acm_dense_geo.h: 256 lanes, 8 samples a lane, 2048 samples a unit) and on acm_dense_vec.h's aligned 16-byte line loads,
+ * funnelled by a shift that is the same for every vector of a row.
  *
  * acm_dense_energy: a flat grid over (marked source row, unit).  A lane squares its 8 samples (the last vector of a row sample by
  * sample) into a 64-bit sum, a wavefront adds its lanes by shuffles, the workgroup its four wavefronts through 32 bytes of LDS, and
  * one 64-bit integer atomic add per workgroup goes to the row's energy.  Integer sums do not depend on the order of arrival: the
  * energies, and everything made from them, are the same in every run.
  *
- * acm_dense_overlay: a flat grid over (output row, unit).  As in acm_dense.hip the body of a row starts where the OUTPUT is 16-byte
- * aligned and stores whole lines (one of int16, two of float32), with single elements in front and behind; A and B have a shift each.
- * A row without b loads no B - the branch is the workgroup's.  No LDS, no scratch.
+ * acm_dense_overlay: a flat grid over (output row, unit).  As in every gather (cut_sub_row, acm_dense_vec.h) the body of a row starts
+ * where the OUTPUT is 16-byte aligned and stores whole lines (one of int16, two of float32), with single elements in front and
+ * behind; A and B have a shift each.  A row without b loads no B - the branch is the workgroup's.  No LDS, no scratch.
  *
  * acm_dense_gains, between the two: a lane per output row derives the row's g from the two energies (16 products of 128 bits,
  * acm_overlay_layout.h - the text acm_dense_overlay_gain compiles too) and stores the row's result, once; the combine kernel reads g
@@ -24,15 +24,12 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "acm_dense_vec.h"
 #include "acm_device.h"
 #include "acm_overlay_layout.h"
 
 namespace {
 
-constexpr uint32_t OVERLAY_UNIT = DENSE_BLOCK * DENSE_VEC;
 constexpr int WAVE = 64;
 
 __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_energy(const int16_t *__restrict__ src, const uint32_t *__restrict__ marked, uint64_t nwork,
@@ -45,7 +42,7 @@ __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_energy(const int16_t *_
 		const uint32_t k = marked[i];
 		const int16_t *row = src + (uint64_t)k * row_len;
 		const uint32_t sh = (uint32_t)reinterpret_cast<uintptr_t>(row) & 15u;
-		const uint64_t e = (uint64_t)unit * OVERLAY_UNIT + threadIdx.x * DENSE_VEC;
+		const uint64_t e = (uint64_t)unit * DENSE_UNIT +threadIdx.x * DENSE_VEC;
 		unsigned long long sum = 0;
 		if (e + DENSE_VEC <= row_len) {
 			int s[DENSE_VEC];
@@ -118,13 +115,9 @@ __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_overlay(const int16_t *
 		const int16_t *A = src + (uint64_t)row.a * row_len;
 		const int16_t *B = src + (uint64_t)(over ? row.b : row.a) * row_len;
 		OUT *o = out + r * row_len;
-		/* [0, head) in front of the first aligned output line, nvec whole vectors, [tail, row_len) behind them */
-		const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
-		const uint64_t head = to_line < row_len ? to_line : row_len;
-		const uint64_t nvec = (row_len - head) / DENSE_VEC;
-		const uint64_t tail = head + nvec * DENSE_VEC;
-		const uint32_t sha = (uint32_t)reinterpret_cast<uintptr_t>(A + head) & 15u;
-		const uint32_t shb = (uint32_t)reinterpret_cast<uintptr_t>(B + head) & 15u;
+		const SubCut c = cut_sub_row(o, row_len);
+		const uint64_t head = c.head, nvec = c.nvec, tail = c.tail;
+		const uint32_t sha = line_shift(A + head), shb = line_shift(B + head);
 
 		const uint64_t v = (uint64_t)unit * DENSE_BLOCK + threadIdx.x;
 		if (v < nvec) {
@@ -161,12 +154,11 @@ extern "C" int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_
 {
 	if (nmarked == 0 || row_len == 0)
 		return 0;
-	const uint64_t units = (row_len + OVERLAY_UNIT - 1) / OVERLAY_UNIT;
-	if (units > 0x7FFFFFFFull || nmarked > ~0ull / units)
+	/* rows of one sub-row; every sample is in a vector here, so the units are whole */
+	const DenseGeo g = dense_geo(nmarked, row_len, 1, 0, dense_grid, DENSE_MAX_GRID, true);
+	if (!g.ok)
 		return (int)hipErrorInvalidValue;
-	const uint64_t nwork = nmarked * units;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
-	hipLaunchKernelGGL(acm_dense_energy, dim3(grid), dim3(DENSE_BLOCK), 0, (hipStream_t)stream, d_src, d_marked, nwork, (uint32_t)units, row_len,
+	hipLaunchKernelGGL(acm_dense_energy, dim3(g.grid), dim3(DENSE_BLOCK), 0, (hipStream_t)stream, d_src, d_marked, g.nwork, g.units, row_len,
 			   reinterpret_cast<unsigned long long *>(d_energy));
 	return (int)hipGetLastError();
 }
@@ -176,11 +168,9 @@ extern "C" int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayR
 {
 	if (nrows == 0 || row_len == 0)
 		return 0;
-	const uint64_t units = std::max<uint64_t>(1, (row_len / DENSE_VEC + DENSE_BLOCK - 1) / DENSE_BLOCK);
-	if (units > 0x7FFFFFFFull || nrows > ~0ull / units)
+	const DenseGeo g = dense_geo(nrows, row_len, 1, 0, dense_grid, DENSE_MAX_GRID);
+	if (!g.ok)
 		return (int)hipErrorInvalidValue;
-	const uint64_t nwork = nrows * units;
-	const uint32_t grid = (uint32_t)std::min<uint64_t>(nwork, acm_cap_value(dense_grid, DENSE_MAX_GRID));
 	const unsigned long long *energy = reinterpret_cast<const unsigned long long *>(d_energy);
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t gain_grid = (nrows + DENSE_BLOCK - 1) / DENSE_BLOCK;
@@ -191,10 +181,10 @@ extern "C" int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayR
 	if (e != 0)
 		return e;
 	if (f32)
-		hipLaunchKernelGGL(acm_dense_overlay<float>, dim3(grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_res, nwork, (uint32_t)units,
+		hipLaunchKernelGGL(acm_dense_overlay<float>, dim3(g.grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_res, g.nwork, g.units,
 				   static_cast<float *>(d_out), row_len);
 	else
-		hipLaunchKernelGGL(acm_dense_overlay<int16_t>, dim3(grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_res, nwork, (uint32_t)units,
+		hipLaunchKernelGGL(acm_dense_overlay<int16_t>, dim3(g.grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_res, g.nwork, g.units,
 				   static_cast<int16_t *>(d_out), row_len);
 	return (int)hipGetLastError();
 }

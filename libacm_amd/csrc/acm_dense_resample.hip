@@ -4,9 +4,8 @@
  * laid out - copied, split, down- or up-mixed - as acm_dense_mixed lays them out.  Launched only where the second row table says that
  * a row is filtered (acm_dense_layout.cpp); every other call keeps the kernel it had.
  *
- * No counterpart in the reference.  The filter, the staging of a unit and the geometry - acm_dense_mixed's: sub-rows (one, or one
- * per plane), units of 256 lanes and 2048 outputs, a flat grid that strides over (row, sub-row, unit); a workgroup works on one row, so
- * its kind is a workgroup-uniform branch - are acm_dense_filter.h's, shared with acm_dense_speed.hip.
+ * No counterpart in the reference.  The filter, the staging of a unit and the kernel's loop are acm_dense_filter.h's, shared with
+ * acm_dense_speed.hip; the geometry is every dense kernel's (acm_dense_geo.h), with 63 KB of LDS a workgroup.
  */
 #include <hip/hip_runtime.h>
 
@@ -14,7 +13,8 @@
 
 namespace {
 
-/* sub_len: output samples of a sub-row (frames with PLANAR, else the whole row); units: workgroups per sub-row */
+/* sub_len: output samples of a sub-row (frames with PLANAR, else the whole row); units: workgroups per sub-row.  A workgroup works
+ * on one row, so whether the row is filtered is a workgroup-uniform branch */
 template <typename OUT, int LAYOUT>
 __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_resample(const int16_t *__restrict__ src, const AcmDenseRow *__restrict__ rows,
 								   const AcmResampleRow *__restrict__ rs, const int16_t *__restrict__ taps, uint64_t nwork,
@@ -22,35 +22,21 @@ __global__ __launch_bounds__(DENSE_BLOCK) void acm_dense_resample(const int16_t 
 {
 	__shared__ __attribute__((aligned(16))) int16_t tab[TAB_CAP];
 	__shared__ __attribute__((aligned(16))) int16_t xs[SPAN_CAP];
-	constexpr uint32_t SUBS = LAYOUT == PLANAR ? 2 : 1;
-	const uint32_t per_row = units * SUBS;
 	for (uint64_t work = blockIdx.x; work < nwork; work += gridDim.x) {
-		const uint64_t k = work / per_row;
-		const uint32_t rem = (uint32_t)(work - k * per_row);
-		const uint32_t plane = SUBS == 2 ? rem / units : 0;
-		const uint32_t unit = rem - plane * units;
-		const AcmDenseRow row = rows[k];
-		const AcmResampleRow r = rs[k];
+		const WorkItem w = work_item<LAYOUT == PLANAR ? 2 : 1>(work, units);
+		const AcmDenseRow row = rows[w.row];
+		const AcmResampleRow r = rs[w.row];
 		const bool converts = (row.count >> ACM_DENSE_MODE_SHIFT) != 0;
 		const uint64_t count = row.count & ACM_DENSE_COUNT_MASK;
 		const int16_t *from = src + row.src;
-		OUT *o = out + k * row_len + (uint64_t)plane * sub_len;
+		OUT *o = out + w.row * row_len + (uint64_t)w.plane * sub_len;
 		if (r.L != 0) {
 			__syncthreads();                                /* the work before this one has read its table and planes */
-			filtered_sub_row<OUT, LAYOUT, false>(from, converts, plane, r, taps, o, sub_len, unit, units, tab, xs);
+			filtered_sub_row<OUT, LAYOUT, false>(from, converts, w.plane, r, taps, o, sub_len, w.unit, units, tab, xs);
 		} else {
-			plain_sub_row<OUT, LAYOUT>(from, converts, count, plane, o, sub_len, unit, units);
+			plain_sub_row<OUT, LAYOUT>(from, converts, count, w.plane, o, sub_len, w.unit, units);
 		}
 	}
-}
-
-template <typename OUT, int LAYOUT>
-int launch(const FilterGeo &g, hipStream_t st, const int16_t *d_src, const AcmDenseRow *d_rows, const AcmResampleRow *d_rs, const int16_t *d_taps,
-	   void *d_out)
-{
-	hipLaunchKernelGGL((acm_dense_resample<OUT, LAYOUT>), dim3(g.grid), dim3(DENSE_BLOCK), 0, st, d_src, d_rows, d_rs, d_taps, g.nwork, g.units,
-			   static_cast<OUT *>(d_out), g.row_len, g.sub_len);
-	return (int)hipGetLastError();
 }
 
 } // namespace
@@ -60,13 +46,13 @@ extern "C" int acmk_launch_dense_resample(const int16_t *d_src, const AcmDenseRo
 {
 	if (nrows == 0)
 		return 0;
-	const FilterGeo g = filter_geo(nrows, frames, channels, planar, dense_grid);
+	const DenseGeo g = dense_geo(nrows, frames, channels, planar, dense_grid, DENSE_MAX_GRID);
 	if (!g.ok)
 		return (int)hipErrorInvalidValue;
-	hipStream_t st = (hipStream_t)stream;
-#define ACM_RS_LAUNCH(OUT, LAYOUT) launch<OUT, LAYOUT>(g, st, d_src, d_rows, d_rs, d_taps, d_out)
-	if (f32)
-		return g.layout == MONO ? ACM_RS_LAUNCH(float, MONO) : g.layout == INTER ? ACM_RS_LAUNCH(float, INTER) : ACM_RS_LAUNCH(float, PLANAR);
-	return g.layout == MONO ? ACM_RS_LAUNCH(int16_t, MONO) : g.layout == INTER ? ACM_RS_LAUNCH(int16_t, INTER) : ACM_RS_LAUNCH(int16_t, PLANAR);
-#undef ACM_RS_LAUNCH
+	return dense_dispatch(f32, g.layout, [&](auto o, auto layout) {
+		using OUT = decltype(o);
+		hipLaunchKernelGGL((acm_dense_resample<OUT, decltype(layout)::value>), dim3(g.grid), dim3(DENSE_BLOCK), 0, (hipStream_t)stream, d_src,
+				   d_rows, d_rs, d_taps, g.nwork, g.units, static_cast<OUT *>(d_out), g.row_len, g.sub_len);
+		return (int)hipGetLastError();
+	});
 }

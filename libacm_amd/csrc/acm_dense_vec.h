@@ -1,7 +1,8 @@
 /*
- * acm_dense_vec.h - what the dense writers' kernels (acm_dense.hip, acm_dense_mix.hip, acm_dense_resample.hip) share: the geometry of
- * a unit, the aligned 16-byte line loads funnelled by a wavefront-uniform shift, and the whole-line stores of int16 and float32
- * vectors.  Device code; included by those three files only.
+ * acm_dense_vec.h - what every dense kernel shares (acm_dense_gather.h's gather and acm_dense_overlay.hip stand on it): the cut of a
+ * sub-row into the samples in front of its first aligned output line, whole vectors and the samples behind them, the aligned 16-byte
+ * line loads funnelled by a wavefront-uniform shift, and the whole-line stores of int16 and float32 vectors.  Device code, in an
+ * unnamed namespace of the including file.  The units and the grid are acm_dense_geo.h's.
  */
 #ifndef ACM_DENSE_VEC_H
 #define ACM_DENSE_VEC_H
@@ -10,16 +11,39 @@
 
 #include <stdint.h>
 
-#include "acm_launch_caps.h"
+#include "acm_dense_geo.h"
 
 namespace {
 
-constexpr int DENSE_BLOCK = 256;        /* lanes per workgroup = vectors per unit */
-constexpr int DENSE_VEC = 8;            /* output samples per body access */
-constexpr uint32_t DENSE_MAX_GRID = ACM_CAP_DENSE_GRID;    /* workgroups of a launch at most; the kernels stride over the rest */
+using namespace acm_dense;
+
+constexpr uint32_t DENSE_MAX_GRID = ACM_CAP_DENSE_GRID;    /* workgroups of a launch at most (dense_geo's `most`); the kernels stride over the rest */
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+/* A sub-row of sub_len output samples at o: [0, head) in front of the first aligned 16-byte output line, nvec whole vectors - the
+ * body, whose lanes store whole lines (one of int16, two of float32) -, [tail, sub_len) behind them.  Lane t of unit u has vector
+ * u * DENSE_BLOCK + t; the up to 7 samples in front are unit 0's and the up to 7 behind the last unit's, with narrow accesses */
+struct SubCut {
+	uint64_t head, nvec, tail;
+};
+template <typename OUT> __device__ __forceinline__ SubCut cut_sub_row(const OUT *o, uint64_t sub_len)
+{
+	const uint64_t to_line = ((0u - (uint32_t)reinterpret_cast<uintptr_t>(o)) & 15u) / sizeof(OUT);
+	SubCut c;
+	c.head = to_line < sub_len ? to_line : sub_len;
+	c.nvec = (sub_len - c.head) / DENSE_VEC;
+	c.tail = c.head + c.nvec * DENSE_VEC;
+	return c;
+}
+
+/* how far into its aligned 16-byte line the source of the body's first vector lies: the same for every vector of the sub-row, since
+ * consecutive vectors' sources are a whole number of lines apart */
+__device__ __forceinline__ uint32_t line_shift(const int16_t *first)
+{
+	return (uint32_t)reinterpret_cast<uintptr_t>(first) & 15u;
+}
 
 template <bool NT, typename V> __device__ __forceinline__ void store_line(V *at, V v)
 {

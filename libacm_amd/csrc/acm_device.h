@@ -207,8 +207,8 @@ void acmhip_set_error_text(const char *text);                    /* what acmhip_
 /* Two kinds of acmk_* functions.  The ones that launch nothing - a build's tile rows, threads, grid, first-pass depth, lead-in, packed
  * slots, the split of a chunk table, what the device parser accepts and where it cuts - live in acm_kernel_geo.cpp: plain C++ over the
  * tables of acm_kernel_geo.h, linkable without a device or a kernel.  The launchers (acmk_launch_*, acmk_warmup) live with their kernels in
- * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip, acm_dense.hip, acm_dense_mix.hip and acm_dense_resample.hip, and take block size and
- * grid from the queries.  `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
+ * acm_kernels.hip (acm_kernels_f32.hip: the _f32 ones), acm_parse.hip and the five acm_dense*.hip, and take block size and
+ * grid from the queries - the dense ones from dense_geo() of acm_dense_geo.h, which is as device-free as the queries are.  `stream` is a hipStream_t.  fmt | ACMK_FMT_F32 (with the format bits 0): the float32 builds,
  * d_pcm (and d_sink) then hold floats and the streams' pcm_off / n_emit count them (acmhip_plan_launch_f32) */
 #define ACMK_FMT_F32 0x100u
 /* one number over every table of acm_kernel_geo.h, as the planner's half (acm_kernel_geo.cpp) and the kernels' half (acm_kernels.hip) of
@@ -340,7 +340,10 @@ int acmk_launch_small_f32(uint32_t level, const AcmDevStream *d_streams, const u
 			  const int16_t *d_idx, const acmhip_blkhdr *d_hdr, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, uint32_t small_grid_x, void *stream);
 int acmk_launch_emit_f32(const AcmDevStream *d_streams, const uint32_t *d_list, uint32_t nlist, uint64_t max_emit,
 			 const int32_t *d_x, int16_t *d_pcm, unsigned fmt, uint32_t list_slice, void *stream);
-/* acm_dense.hip: nrows rows of frames * channels samples each into d_out (int16, or float32 = the int16 sample times 2^-15 with f32), row k at
+/* The dense launchers.  All of them: units, work items, the capped grid and the two refusals (hipErrorInvalidValue for a sub-row of
+ * more than 2^31 - 1 units or work past 2^64; nothing to do returns 0) are acm_dense_geo.h's; the four gather kernels share one body
+ * (acm_dense_gather.h), and which of them a call launches is acm_dense_tables' answer (acm_dense_layout.h).
+ * acm_dense.hip: nrows rows of frames * channels samples each into d_out (int16, or float32 = the int16 sample times 2^-15 with f32), row k at
  * element k * frames * channels: d_rows[k].count samples from d_src + d_rows[k].src, interleaved as they are or (planar, channels == 2) split
  * into a plane per channel, zeros behind them.  d_src: 16-byte aligned; the kernel loads whole aligned 16-byte lines and only lines that hold
  * at least one of a row's samples.  d_out: aligned to its element.  One launch, nothing allocated, nothing waited for */

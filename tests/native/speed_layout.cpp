@@ -118,6 +118,12 @@ int main()
 	CHECK(sp[0].L == 10 && sp[0].M == 9 && !sp[0].wide && sp[0].n_out == 45);
 	CHECK(sp[1].wide && sp[1].b == 9 && sp[1].Wd == 8 && sp[1].n_out == 51 && sp[1].step == ((29999ull << 32) / 30000));
 	CHECK(sp[2].L == 0 && sp[3].wide && sp[4].L == 1 && sp[4].M == 2 && sp[5].wide && sp[5].tab != sp[1].tab && sp[6].L == 0 && sp[7].L == 0);
+	// the one decision the driver and the visitors take: the same three tables into a region of exactly table_bytes(), all of it goes up
+	std::vector<uint8_t> table(D.table_bytes());
+	DenseLaunch launch = acm_dense_tables(D, slots.data(), wins.data(), table.data());
+	CHECK(launch.kernel == DENSE_SPEED && launch.bytes == D.table_bytes());
+	CHECK(!memcmp(table.data(), rows.data(), D.row_table_bytes()) && !memcmp(table.data() + D.resample_off(), sp.data(), sp.size() * sizeof(AcmSpeedRow)) &&
+	      !memcmp(table.data() + D.taps_off(), taps.data(), taps.size() * sizeof(int16_t)));
 	// ... where staging left nothing of the wide rows the call goes on as without the flag
 	for (size_t k : { 1, 3, 5 })
 		wins[k].words = 0;
@@ -125,6 +131,14 @@ int main()
 	CHECK(!acm_dense_wide_rows(D, rows.data()));
 	std::vector<AcmResampleRow> rs(wins.size());
 	CHECK(acm_dense_resample_rows(D, rows.data(), rs.data(), taps.data()) && rs[0].L == 10 && rs[1].L == 0 && rs[4].M == 2);
+	launch = acm_dense_tables(D, slots.data(), wins.data(), table.data());
+	CHECK(launch.kernel == DENSE_RESAMPLE && launch.bytes == D.table_bytes());
+	CHECK(!memcmp(table.data() + D.resample_off(), rs.data(), rs.size() * sizeof(AcmResampleRow)));
+	// ... and where it left nothing of any filtered row, the row table alone goes up, for the kernel of a call without the flags
+	for (size_t k : { 0, 4 })
+		wins[k].words = 0;
+	launch = acm_dense_tables(D, slots.data(), wins.data(), table.data());
+	CHECK(launch.kernel == DENSE_PLAIN && launch.bytes == D.row_table_bytes());
 
 	// 14 exact tables and two wide ones are 16; one more of either kind is refused
 	wins.clear();

@@ -297,8 +297,8 @@ def test_window_matrix_with_the_column_kernel_in_slices(dev, parse_slice):
 # ================================================================================================ the dense kernels
 
 def dense_units(frames, channels, planar):
-    """(units per sub-row, sub-rows per row) of a dense launch: acm_dense.hip, acm_dense_mix.hip and filter_geo of acm_dense_filter.h -
-    a unit is 256 lanes of 8 samples, and the samples behind the last whole vector go with the last unit"""
+    """(units per sub-row, sub-rows per row) of a dense launch, a model of its own of dense_geo() in libacm_amd/csrc/acm_dense_geo.h, which
+    every dense launcher asks - a unit is 256 lanes of 8 samples, and the samples behind the last whole vector go with the last unit"""
     subs = 2 if planar and channels == 2 else 1
     sub_len = frames if subs == 2 else frames * channels
     return max(1, (sub_len // 8 + 255) // 256), subs
