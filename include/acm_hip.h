@@ -879,6 +879,56 @@ int  acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_batch_item *
 uint32_t acm_dense_overlay_gain(uint64_t energy_a, uint64_t energy_b, uint32_t snr);
 
 /* ------------------------------------------------------------------------
+ * Dense crop batches with an overlay and an impulse response (csrc/acm_batch_windows.cpp over csrc/acm_fir_layout.cpp, kernel:
+ * csrc/acm_dense_fir.hip): reverberation - a source row convolved with a room impulse response before anything is laid over it.  A
+ * call of its own beside acm_batch_decode_windows_overlay, which is untouched.
+ *
+ * Windows, opts, dense, rows and everything reported for them mean what they mean to acm_batch_decode_windows_overlay and define
+ * source rows S_k of R = T * C int16 elements.  For a window k with p = fir->of_window[k] != ACM_FIR_NONE the source row the rest of
+ * the call sees - the energies, the SNR gains, the combine - is F_k instead of S_k.  With h, ntaps, d = delay and s = shift of
+ * fir->responses[p], on unbounded integers, channel by channel:
+ *   x[i]   = channel ch of frame i of S_k for 0 <= i < T (planar: element ch * T + i; interleaved: i * C + ch), 0 elsewhere
+ *   acc[j] = sum over t in [0, ntaps) of h[t] * x[j + d - t]                                0 <= j < T
+ *   y[j]   = clamp((acc[j] + (s ? 1 << (s - 1) : 0)) >> s, -32768, 32767)                   (the shift arithmetic; it saturates)
+ * F_k has the layout of S_k, and both channels of a stereo row get the same response.  The row is T frames whatever the crop
+ * delivered: the tail of a short crop rings on into the zeros behind it, and what would fall behind frame T is cut.  d is the tap
+ * that lands on the input's own position (the direct path).  A response is taken only if sum |h[t]| <= 65535: then |acc| < 2^31 and
+ * a 32-bit accumulator is exact - acm_dense_fir_check is the one text of that check.  {h = [1], s = 0, d = 0} is the identity, and a
+ * row of zeros stays a row of zeros.  The SNR energies are those of F_k: the noise is set against the reverberant speech.
+ *
+ * ACMHIP_ERR_ARG before anything is written: anything acm_batch_decode_windows_overlay refuses; responses == NULL or of_window ==
+ * NULL with nresp > 0; nresp > 65536; reserved != 0; an entry of of_window >= nresp that is not ACM_FIR_NONE; a response that fails
+ * acm_dense_fir_check (ntaps 0 or above 32768, delay >= ntaps, shift > 30, reserved != 0, sum |h| above 65535, taps == NULL); more
+ * than 2^22 taps in the responses some window names, together.
+ *
+ * With fir == NULL, nresp == 0 or every entry ACM_FIR_NONE the call makes exactly the launches of acm_batch_decode_windows_overlay
+ * over the same tables.  Else the source arena holds nwin + nfilt rows, F of the i-th filtered window in row nwin + i; one launch of
+ * acm_dense_fir between the gather launch and the energy launch writes those rows, and the row table that is uploaded names them
+ * where it named a filtered window - the caller's records keep their own a and b.  Responses no window names are not uploaded.
+ * timing->kernel_s spans synthesis through the combine.
+ * ---------------------------------------------------------------------- */
+#define ACM_FIR_NONE 0xFFFFFFFFu
+typedef struct acm_fir_response {
+	const int16_t *taps;             /* h[0 .. ntaps), host memory */
+	uint32_t ntaps;                  /* 1 .. 32768 */
+	uint32_t delay;                  /* d < ntaps: the tap that lands on the input's own position */
+	uint32_t shift;                  /* s, 0 .. 30 */
+	uint32_t reserved;               /* 0 */
+} acm_fir_response;
+typedef struct acm_fir_opts {
+	const acm_fir_response *responses;
+	size_t nresp;                    /* <= 65536 */
+	const uint32_t *of_window;       /* nwin entries: a response number, or ACM_FIR_NONE */
+	uint64_t reserved;               /* 0 */
+} acm_fir_opts;
+
+int  acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+					  acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+					  const acm_fir_opts *fir, acm_overlay_row *rows, size_t nrows, acm_window_timing *timing);
+/* ACMHIP_OK for a response the call takes, else ACMHIP_ERR_ARG.  No device is needed */
+int  acm_dense_fir_check(const acm_fir_response *r);
+
+/* ------------------------------------------------------------------------
  * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs
  * before its first crop.  acm_index_file parses a whole file to get it, decoding every filler index and dropping it; the device
  * only WALKS the stream (acm_index_scan_wave, csrc/acm_parse.hip: one stream per wavefront, the walk of acm_batch_decode's device

@@ -259,7 +259,8 @@ class GpuDecoder:
         return d_pcm.reshape(-1)[:need].view(shape), delivered, statuses
 
 
-    def crop_overlay(self, files, windows, rows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None):
+    def crop_overlay(self, files, windows, rows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None,
+                     responses=None, reverb=None):
         """crop_batch with volume perturbation and an overlay at a signal-to-noise ratio in the same call
         (acm_batch_decode_windows_overlay).  windows, frames, channels, planar, index, mix, rate and speed are crop_batch's and define
         the SOURCE rows - what crop_batch would return, kept in memory of the decoder's own.  rows: one Overlay per row of the batch:
@@ -268,7 +269,14 @@ class GpuDecoder:
         -> (batch [len(rows), channels, frames] (planar) or [len(rows), frames, channels], gains, frames_delivered, statuses): gains[r]
         is (g, energy_a, energy_b), the Q12 gain b got and the sums of squares it was made from; frames_delivered and statuses are
         the WINDOWS', as crop_batch reports them.  The result is defined on integers (include/acm_hip.h), float32 is the int16 result
-        times 2^-15; out as in crop_batch."""
+        times 2^-15; out as in crop_batch.
+        responses, reverb (acm_batch_decode_windows_overlay_fir): a list of Response, and per window the number of the one its source
+        row is convolved with before anything else is made from it - energies included, so the noise is set against the reverberant
+        speech - or None for a window that stays dry.  The row keeps its length: a crop's tail rings on into the zeros behind it."""
+        if reverb is not None and responses is None:
+            raise ValueError("GpuDecoder.crop_overlay: reverb needs responses")
+        if reverb is not None and len(reverb) != len(windows):
+            raise ValueError("GpuDecoder.crop_overlay: reverb has %d entries for %d windows" % (len(reverb), len(windows)))
         torch = self.torch
         files = [_load(f) for f in files]
         if index is None:
@@ -293,10 +301,14 @@ class GpuDecoder:
         table = np.zeros(nr, dtype=capi.OVERLAY_ROW_DT)
         if nr:
             table.view(np.uint32).reshape(nr, -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
-        statuses, words, _, gains, self.timing = capi.batch_decode_windows_overlay(
+        call, fir = capi.batch_decode_windows_overlay, {}
+        if responses is not None:
+            call = capi.batch_decode_windows_overlay_fir
+            fir = dict(responses=[r.record for r in responses], of_window=reverb if reverb is not None else [None] * n)
+        statuses, words, _, gains, self.timing = call(
             self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], table,
             d_pcm.data_ptr(), d_pcm.numel(), frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse,
-            f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed)
+            f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed, **fir)
         delivered = [w // c for w, c in zip(words, per)]
         if speed is not None:
             delivered = [capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1)) if d else 0 for d, w, sp in zip(delivered, windows, speed)]
@@ -332,6 +344,44 @@ class Overlay:
     def record(self):
         """(a, b, vol, snr, gain) of acm_overlay_row, b None where nothing is laid over the row"""
         return (self.raw[0], self.b) + self.raw[2:]
+
+
+class Response:
+    """one impulse response of GpuDecoder.crop_overlay(responses=): h, a float array, quantised to what acm_fir_response holds -
+    int16 taps q = nearbyint(h * 2^s) (float64, ties to even) with the largest shift s <= 30 at which max |q| <= 32767 and
+    sum |q| <= 65535, so that a 32-bit accumulator is exact.  delay: the tap that lands on the input's own position - the direct
+    path -, argmax |h| by default.  ValueError where no s >= 0 fits (sum |h| beyond 65535)."""
+
+    def __init__(self, h, delay=None):
+        h = np.asarray(h, dtype=np.float64).reshape(-1)
+        if h.size == 0 or h.size > capi.FIR_MAX_TAPS or not np.isfinite(h).all():
+            raise ValueError("Response: 1 .. %d finite taps" % capi.FIR_MAX_TAPS)
+        delay = int(np.argmax(np.abs(h))) if delay is None else int(delay)
+        for s in range(capi.FIR_MAX_SHIFT, -1, -1):
+            q = np.rint(h * 2.0 ** s)
+            if np.abs(q).max() <= 32767 and np.abs(q).sum() <= capi.FIR_MAX_L1:
+                break
+        else:
+            raise ValueError("Response: sum |h| = %g does not fit %d at any shift" % (np.abs(h).sum(), capi.FIR_MAX_L1))
+        self._set(q.astype(np.int16), delay, s)
+
+    def _set(self, taps, delay, shift):
+        if not 0 <= delay < taps.size:
+            raise ValueError("Response: delay %d of %d taps" % (delay, taps.size))
+        self.taps, self.delay, self.shift = taps, delay, shift
+        self.record = (taps, delay, shift)      # as capi.fir_opts takes them
+
+    @classmethod
+    def raw(cls, taps, delay, shift):
+        """a Response of integers as they are: int16 taps, delay, shift - what acm_dense_fir_check does not take is a ValueError"""
+        r = cls.__new__(cls)
+        t = np.asarray(taps)
+        if t.ndim != 1 or t.size == 0 or (t != np.clip(np.rint(t), -32768, 32767)).any():
+            raise ValueError("Response.raw: int16 taps")
+        r._set(t.astype(np.int16), int(delay), int(shift))
+        if capi.dense_fir_check(r.taps, r.delay, r.shift) != 0:
+            raise ValueError("Response.raw: a response acm_dense_fir_check does not take")
+        return r
 
 
 def source_frames(frames, rate_in, rate_out, speed=(1, 1)):

@@ -165,6 +165,21 @@ OVERLAY_NONE = 0xFFFFFFFF       # OverlayRow.b: nothing is laid over the row
 OVERLAY_G_MAX = 32768           # the largest Q12 gain of b
 
 
+class FirResponse(C.Structure):
+    _fields_ = [("taps", C.c_void_p), ("ntaps", C.c_uint32), ("delay", C.c_uint32), ("shift", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FirOpts(C.Structure):
+    _fields_ = [("responses", C.POINTER(FirResponse)), ("nresp", C.c_size_t), ("of_window", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+FIR_RESPONSE_DT = np.dtype([("taps", "<u8"), ("ntaps", "<u4"), ("delay", "<u4"), ("shift", "<u4"), ("reserved", "<u4")])   # acm_fir_response as a numpy record
+FIR_NONE = 0xFFFFFFFF           # FirOpts.of_window[k]: window k is not filtered
+FIR_MAX_TAPS = 32768            # of one response
+FIR_MAX_L1 = 65535              # sum |h[t]| of a response at most
+FIR_MAX_SHIFT = 30
+
+
 class BatchIndexOut(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("max_blocks", C.c_size_t), ("blocks", C.c_uint32), ("end_status", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_uint32)]
@@ -206,7 +221,7 @@ ACMHIP_SYMBOLS = [
     "acmhip_plan_launch_f32", "acmhip_host_synth_f32",
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
     "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
-    "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain",
+    "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain", "acm_batch_decode_windows_overlay_fir", "acm_dense_fir_check",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info", "acmhip_device_set_launch_caps",
 ]
@@ -320,6 +335,11 @@ def lib():
                                                        C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(OverlayRow), sz, C.POINTER(WindowTiming)]
         L.acm_dense_overlay_gain.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
         L.acm_dense_overlay_gain.restype = C.c_uint32
+    if hasattr(L, "acm_batch_decode_windows_overlay_fir"):
+        L.acm_batch_decode_windows_overlay_fir.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                                           C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(FirOpts), C.POINTER(OverlayRow), sz,
+                                                           C.POINTER(WindowTiming)]
+        L.acm_dense_fir_check.argtypes = [C.POINTER(FirResponse)]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -1231,7 +1251,7 @@ def dense_overlay_gain(energy_a, energy_b, snr):
 
 def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                  fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False):
+                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False, _fir=None):
     """acm_batch_decode_windows_overlay: the windows are the SOURCE rows of batch_decode_windows_dense (every argument it has means the
     same), and d_pcm receives len(rows) output rows of frames * channels samples, row r at sample r * frames * channels.  rows: tuples
     (a, b, vol, snr, gain) of acm_overlay_row's inputs - b None for ACM_OVERLAY_NONE - or 6-tuples that end in `reserved`, or an array
@@ -1239,10 +1259,12 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
     (tests of the refusals: nrows is then what the call is told).  Returns (statuses, words, offsets, gains, WindowTiming): statuses and words are the windows', offsets their
     (dev_off, slot_off, slot_words), gains (g, energy_a, energy_b) per output row - or, with result_table=True (a million rows), the call's own copy of the row table as
     the library left it, an OVERLAY_ROW_DT array whose gain, energy_a and energy_b fields hold them.  check=False: the return code as a sixth element
-    instead of an exception."""
+    instead of an exception.  _fir: batch_decode_windows_overlay_fir's - the call goes to acm_batch_decode_windows_overlay_fir with it."""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
+    name = "acm_batch_decode_windows_overlay" if _fir is None else "acm_batch_decode_windows_overlay_fir"
+    extra = () if _fir is None else (C.byref(_fir[0]) if _fir[0] is not None else None,)
     if dense_flags is None:
         dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
             (DENSE_SPEED if speeds is not None else 0)
@@ -1260,17 +1282,64 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
             table[r] = (a, OVERLAY_NONE if b is None else b, vol, snr, gain, rows[r][5] if len(rows[r]) > 5 else 0, 0, 0)
     tm = WindowTiming()
     _fill(dev)
-    rc = lib().acm_batch_decode_windows_overlay(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
-                                                C.byref(dense) if dense is not None else None,
-                                                C.cast(table.ctypes.data, C.POINTER(OverlayRow)) if rows is not None else None,
-                                                nr if nrows is None else nrows, C.byref(tm))
+    rc = getattr(lib(), name)(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
+                              C.byref(dense) if dense is not None else None, *extra,
+                              C.cast(table.ctypes.data, C.POINTER(OverlayRow)) if rows is not None else None,
+                              nr if nrows is None else nrows, C.byref(tm))
     if check:
-        _check(rc, "acm_batch_decode_windows_overlay")
+        _check(rc, name)
     res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)],
            [(int(wins[k].dev_off), int(wins[k].slot_off), int(wins[k].slot_words)) for k in range(nw)],
            table[:nr] if result_table else list(zip(table["gain"][:nr].tolist(), table["energy_a"][:nr].tolist(), table["energy_b"][:nr].tolist())),
            tm)
     return res if check else res + (rc,)
+
+
+def fir_response(taps, delay, shift, reserved=0):
+    """(FirResponse, the int16 array it points into) of h = taps (None: a null pointer), d = delay, s = shift"""
+    h = None if taps is None else np.ascontiguousarray(taps, dtype="<i2")
+    return FirResponse(h.ctypes.data if h is not None and h.size else None, h.size if h is not None else 1, delay, shift, reserved), h
+
+
+def dense_fir_check(taps, delay, shift, reserved=0, ntaps=None):
+    """acm_dense_fir_check: 0 for a response acm_batch_decode_windows_overlay_fir takes, else ERR_ARG.  ntaps (tests): the count the
+    library is told instead of len(taps)"""
+    r, keep = fir_response(taps, delay, shift, reserved)
+    if ntaps is not None:
+        r.ntaps = ntaps
+    return int(lib().acm_dense_fir_check(C.byref(r)))
+
+
+def fir_opts(responses, of_window, nresp=None, reserved=0):
+    """(FirOpts, what it points into) of responses = [(taps, delay, shift[, reserved])] - or an array of FIR_RESPONSE_DT records that
+    point at taps the caller keeps alive - and of_window = a response number or None per window (or a uint32 array, FIR_NONE for None).
+    Either may be None for a null pointer; nresp (tests): the count the library is told"""
+    keep = []
+    table = None
+    if isinstance(responses, np.ndarray):
+        table = np.ascontiguousarray(responses, dtype=FIR_RESPONSE_DT)
+    elif responses is not None:
+        table = np.zeros(max(len(responses), 1), dtype=FIR_RESPONSE_DT)
+        for p, r in enumerate(responses):
+            rec, h = fir_response(*r)
+            keep.append(h)
+            table[p] = (rec.taps or 0, rec.ntaps, rec.delay, rec.shift, rec.reserved)
+    of = None
+    if of_window is not None:
+        of = of_window if isinstance(of_window, np.ndarray) else np.array([FIR_NONE if p is None else p for p in of_window] or [FIR_NONE], dtype="<u4")
+        of = np.ascontiguousarray(of, dtype="<u4")
+    n = (len(responses) if responses is not None else 0) if nresp is None else nresp
+    o = FirOpts(C.cast(table.ctypes.data, C.POINTER(FirResponse)) if table is not None else None, n, of.ctypes.data if of is not None else None, reserved)
+    return o, (table, of, keep)
+
+
+def batch_decode_windows_overlay_fir(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, responses=None, of_window=None, nresp=None,
+                                     fir_reserved=0, no_fir=False, **kw):
+    """acm_batch_decode_windows_overlay_fir: batch_decode_windows_overlay (every other argument and what is returned are its) with
+    window k convolved with responses[of_window[k]] - (taps, delay, shift) of include/acm_hip.h - before the rows are made from it;
+    of_window[k] None: not filtered.  no_fir: no acm_fir_opts at all; nresp, fir_reserved (tests of the refusals): as fir_opts takes them"""
+    o, keep = (None, None) if no_fir else fir_opts(responses, of_window, nresp, fir_reserved)
+    return batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, _fir=(o, keep), **kw)
 
 
 # --------------------------------------------------------------------------- the block index of a batch

@@ -25,6 +25,9 @@
  * acm_batch_decode_windows_overlay is the dense run with its gather launch aimed at the handle's source arena instead of the caller's
  * tensor, and two launches of acm_dense_overlay.hip behind it that make the caller's rows from those: which source rows get an
  * energy and where the tables sit is acm_overlay_layout.cpp's.
+ *
+ * acm_batch_decode_windows_overlay_fir is that run with one launch of acm_dense_fir.hip between the gather launch and the energy
+ * launch: the windows acm_fir_layout.cpp lists are filtered into rows behind the source rows, and the overlay's tables name those.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -35,6 +38,7 @@
 #include "acm_batch_common.h"
 #include "acm_dense_layout.h"
 #include "acm_device.h"
+#include "acm_fir_layout.h"
 #include "acm_hip.h"
 #include "acm_overlay_layout.h"
 #include "acm_stage.h"
@@ -51,9 +55,9 @@ class WinRun {
 public:
 	WinRun(acmhip_device *dev_, const acm_batch_item *items_, acm_batch_window *wins_, const acm_batch_opts &opts_,
 	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseLayout *dense_ = nullptr,
-	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr)
+	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr, const FirLayout *fir_ = nullptr)
 		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), dense(dense_), dense_out(dense_out_),
-		  overlay(overlay_), overlay_rows(overlay_rows_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
+		  overlay(overlay_), overlay_rows(overlay_rows_), fir(fir_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
 		  pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
 	{
 		for (size_t k : L.act)
@@ -82,10 +86,13 @@ private:
 	int upload_slices(const std::vector<size_t> &ids);
 	void collect(PlanStreams &ps);
 	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, behind them a dense call's row table, and behind that an
-	 * overlay call's tables */
+	 * overlay call's tables, and behind those the taps and the rows of its filter pass */
 	size_t overlay_off() const { return (size_t)round_up(dense->table_off(L) + dense->table_bytes(), 64); }
+	size_t fir_off() const { return (size_t)round_up(overlay_off() + overlay->table_bytes(), 64); }
 	size_t jobs_bytes() const
 	{
+		if (fir)
+			return fir_off() + fir->table_bytes();
 		return overlay ? overlay_off() + overlay->table_bytes() : dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes();
 	}
 	int combine_rows();
@@ -103,6 +110,7 @@ private:
 	void *const dense_out;                  /* ... and its output tensor */
 	const OverlayLayout *const overlay;     /* an overlay call (a dense call whose rows go to the source arena), else null */
 	acm_overlay_row *const overlay_rows;    /* ... and the caller's row table, for what comes back */
+	const FirLayout *const fir;             /* an overlay call some of whose windows are filtered, else null */
 	const hipStream_t st;
 	const bool out_f32, keep_on_device;
 	const size_t pcm_unit;
@@ -324,6 +332,13 @@ int WinRun::synthesise_and_gather()
 		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + overlay_off(), up, overlay->upload_bytes(), hipMemcpyHostToDevice, st));
 		tm.h2d_bytes += overlay->upload_bytes();
 	}
+	if (fir) {
+		uint8_t *up = h_jobs + fir_off();
+		memcpy(up, fir->taps.data(), fir->taps_bytes());
+		memcpy(up + fir->rows_off(), fir->rows.data(), fir->rows.size() * sizeof(AcmFirRow));
+		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + fir_off(), up, fir->table_bytes(), hipMemcpyHostToDevice, st));
+		tm.h2d_bytes += fir->table_bytes();
+	}
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
@@ -385,12 +400,20 @@ int WinRun::synthesise_and_gather()
 }
 
 /* an overlay call, behind the gather launch that wrote the source rows: the row table and the list of rows to sum went up with the
- * dense tables; the energies are zeroed and summed, and the combine launch writes the caller's tensor and a result per row */
+ * dense tables; the filtered rows are made first, where the call has any; the energies are zeroed and summed, and the combine launch
+ * writes the caller's tensor and a result per row */
 int WinRun::combine_rows()
 {
 	const size_t at = overlay_off();
 	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	uint64_t *d_energy = reinterpret_cast<uint64_t *>(d_jobs + at + overlay->energy_off());
+	if (fir) {
+		const uint8_t *d_fir = d_jobs + fir_off();
+		const int e = acmk_launch_dense_fir(d_src, reinterpret_cast<const AcmFirRow *>(d_fir + fir->rows_off()), fir->nfilt(),
+						    reinterpret_cast<const uint32_t *>(d_fir), dense->frames, dense->channels, dense->planar, caps.dense_grid, st);
+		if (e != 0)
+			return acmhip_report_hip(e, "acmk_launch_dense_fir");
+	}
 	if (!overlay->marked.empty()) {
 		ACM_HIP_TRY(hipMemsetAsync(d_energy, 0, overlay->energy_bytes(), st));
 		const int e = acmk_launch_dense_energy(d_src, reinterpret_cast<const uint32_t *>(d_jobs + at + overlay->marked_off()), overlay->marked.size(),
@@ -525,10 +548,10 @@ static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_
 }
 
 /* the dense call without its wall clock; with_overlay: acm_batch_decode_windows_overlay - the windows are the sources of the nrows rows of
- * `rows`, which are what opts->d_pcm receives */
+ * `rows`, which are what opts->d_pcm receives; fir: acm_batch_decode_windows_overlay_fir's responses, else null */
 static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
 				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm, bool with_overlay = false,
-				acm_overlay_row *rows = nullptr, size_t nrows = 0)
+				acm_overlay_row *rows = nullptr, size_t nrows = 0, const acm_fir_opts *fir = nullptr)
 {
 	Prelude pre;
 	ACM_TRY(pre.begin(dev, items, n, index, wins, nwin, opts_in));
@@ -549,6 +572,14 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 		acmhip_set_error_text("acm_batch_decode_windows_overlay: a row table the call does not take (include/acm_hip.h)");
 		return ACMHIP_ERR_ARG;
 	}
+	FirLayout F;
+	if (with_overlay && fir) {
+		if (acm_fir_prepare(fir, nwin, &F) != ACMHIP_OK) {
+			acmhip_set_error_text("acm_batch_decode_windows_overlay_fir: responses the call does not take (include/acm_hip.h)");
+			return ACMHIP_ERR_ARG;
+		}
+		acm_fir_remap(F, &O);
+	}
 	WindowLayout layout;
 	ACM_TRY(acm_window_layout(its.data(), n, D.wins.data(), nwin, D.inner, &layout, &pool));
 	for (size_t k = 0; k < nwin; k++) {
@@ -561,7 +592,7 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 		return ACMHIP_OK;
 
 	const auto t_hdr = clk::now();
-	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows);
+	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows, F.nfilt() ? &F : nullptr);
 	ACM_TRY(run.fetch_arenas(t_hdr));
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
@@ -580,6 +611,14 @@ extern "C" int acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_ba
 						acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
 {
 	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows); });
+}
+
+extern "C" int acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+						    acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
+						    const acm_fir_opts *fir, acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
+{
+	return timed(timing,
+		     [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows, fir); });
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,

@@ -144,6 +144,15 @@ struct AcmOverlayRow {
 struct AcmOverlayResult {
 	uint64_t gain, energy_a, energy_b;
 };
+/* acm_batch_decode_windows_overlay_fir (acm_dense_fir.hip): row dst of the source arena is row src filtered, channel by channel:
+ * y[j] = clamp((sum over u < nblk * ACM_FIR_TAP_BLOCK of g[u] * x[j + lead + u] + half) >> shift), g the response reversed and
+ * zero-padded to whole tap blocks (acm_fir_layout.cpp), as pairs of int16 from dword taps_off of the call's taps on; lead <= 0 */
+#define ACM_FIR_TAP_BLOCK 64u
+struct AcmFirRow {
+	uint32_t src, dst, taps_off, nblk;
+	int32_t lead;
+	uint32_t shift;
+};
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -376,6 +385,11 @@ int acmk_launch_dense_energy(const int16_t *d_src, const uint32_t *d_marked, uin
 			     void *stream);
 int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayRow *d_rows, const uint64_t *d_energy, AcmOverlayResult *d_res, uint64_t nrows,
 			      void *d_out, uint64_t row_len, int f32, uint32_t dense_grid, void *stream);
+/* acm_dense_fir.hip, between the two: rows d_rows[i].dst of d_src written from rows d_rows[i].src (other rows, so nothing is read that
+ * the launch writes), every channel of frames samples filtered by the row's response out of d_taps (16-byte aligned).  Reads and
+ * writes samples of those rows alone, element by element or as whole aligned lines inside a row.  Nothing allocated, nothing waited for */
+int acmk_launch_dense_fir(int16_t *d_src, const AcmFirRow *d_rows, uint64_t nfilt, const uint32_t *d_taps, uint64_t frames, uint32_t channels,
+			  int planar, uint32_t dense_grid, void *stream);
 #ifdef __cplusplus
 }
 #endif
