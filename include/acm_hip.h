@@ -929,6 +929,86 @@ int  acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const acm_batch_it
 int  acm_dense_fir_check(const acm_fir_response *r);
 
 /* ------------------------------------------------------------------------
+ * Mel filterbank features from dense crop batches (csrc/acm_batch_windows.cpp over csrc/acm_feat_layout.cpp, kernels:
+ * csrc/acm_dense_feat.hip): the speech front end - framing, window, DFT, power, mel filterbank - as part of the call that builds the
+ * batch, so that the waveform never leaves the handle.  A call of its own beside acm_batch_decode_windows_overlay_fir, which is
+ * untouched.
+ *
+ * Windows, opts, dense, fir, rows and everything reported for them (rows[], wins[], timing) mean what they mean to
+ * acm_batch_decode_windows_overlay_fir and define nrows output rows Y_r of T int16 frames: exactly the int16 rows that call would
+ * write.  They go into an arena of the handle's own ("D_FEAT" of acmhip_device_arena_info, filled with 0xA5 in fill mode like the
+ * source arena), not to opts->d_pcm.  dense->channels must be 1 (ACM_DENSE_MIX makes mono rows of stereo files).  opts->d_pcm receives
+ * float32 features whatever ACM_BATCH_PCM_F32 says, and opts->d_pcm_words counts float32 elements.
+ *
+ * With N = n_fft = 2^n, H = hop, B = n_mels, w = window, c = cs of `bank`, on unbounded integers, for a row x = Y_r with x[i] = 0
+ * outside [0, T):
+ *   frames    F = 1 + T / H with ACM_FEAT_CENTER (the division floors), else F = T >= N ? 1 + (T - N) / H : 0 (acm_feat_frames)
+ *   start     frame f starts at s = f * H - (CENTER ? N / 2 : 0).  What lies outside the row is ZERO: torch.stft's
+ *             pad_mode="constant", not its default "reflect"
+ *   window    xw[t] = (x[s + t] * w[t] + 16384) >> 15, the shift arithmetic; w <= 32639 makes |xw| <= 32639, whose two signed
+ *             bytes (v = 256 * hi + lo, lo the signed low byte) both fit int8
+ *   DFT       for k in [0, N / 2]:  Re[k] =  sum over t of xw[t] * c[(k * t) mod N]
+ *                                   Im[k] = -sum over t of xw[t] * c[(k * t + 3 N / 4) mod N]
+ *   scaling   q = n - 1:  A = (Re + (1 << (q - 1))) >> q, Bv likewise from Im; |A|, |Bv| <= 2^30
+ *   power     P[k] = A^2 + Bv^2 < 2^62
+ *   mel       E[b] = sum over k in [mel_first[b], mel_first[b] + mel_count[b]) of mel_w[mel_off[b] + k - mel_first[b]] * P[k] < 2^89
+ *   output    y = trunc24(E) * 2^-(75 - 2 n): trunc24 keeps the 24 leading bits of E and clears the rest, so y is an exact float32,
+ *             needs no rounding mode and does not depend on the order of any sum
+ * With the tables acm_feat_design makes, y is (32639 / 32768)^2 times - 0.034 dB below - the power mel spectrogram of x / 32768 under
+ * a window of peak 1, up to quantisation.  The logarithm stays with the caller: one elementwise operation on a tensor half the size
+ * of the waveform, and a float log would not be bit-exact.
+ *
+ * Element (r, b, f) is at (r * B + b) * F + f, with ACM_FEAT_TIME_MAJOR at (r * F + f) * B + b.  Every element of [0, nrows * B * F)
+ * is written and nothing outside; F == 0 or nrows == 0 writes nothing and is ACMHIP_OK.
+ *
+ * ACMHIP_ERR_ARG before anything is written: anything acm_batch_decode_windows_overlay_fir refuses; dense->channels != 1; a bank
+ * acm_feat_bank_check refuses (bank or a table NULL, n_fft not 128, 256, 512, 1024 or 2048, hop 0 or above N, n_mels 0 or above
+ * 128, unknown flags, reserved != 0, a window value outside [0, 32639], a cs value outside [-16384, 16384], a band reaching past bin
+ * N / 2, a weight above 32768); opts->d_pcm_words < nrows * B * F.
+ *
+ * The run is acm_batch_decode_windows_overlay_fir's up to its combine launch, which writes int16 into the feature arena; then
+ * acm_feat_twiddle builds the DFT's B operand from c - N x 2 * 16 * (N / 32 + 1) signed bytes twice, hi and lo, in the lane order of
+ * v_mfma_i32_16x16x64_i8 - and acm_dense_feat makes the features: 16 frames of a row per workgroup, four matrix products
+ * (hi.hi, hi.lo, lo.hi, lo.lo) per 16 x 16 tile, joined in 64 bits.  timing->kernel_s spans synthesis through the feature launch.
+ * ---------------------------------------------------------------------- */
+#define ACM_FEAT_CENTER     1u          /* frame f is centred on sample f * H; else it starts there and only whole frames count */
+#define ACM_FEAT_TIME_MAJOR 2u          /* [row][frame][band] instead of [row][band][frame] */
+#define ACM_FEAT_MAX_MELS   128u
+#define ACM_FEAT_WINDOW_MAX 32639       /* 0x7F7F: then both signed bytes of a windowed sample fit int8 */
+#define ACM_FEAT_CS_ONE     16384       /* c[m] stands for 16384 cos(2 pi m / N) */
+#define ACM_FEAT_W_ONE      32768u      /* a mel weight of 1 (Q15) */
+typedef struct acm_feat_bank {
+	uint32_t n_fft;                  /* N: 128, 256, 512, 1024 or 2048; n = log2 N */
+	uint32_t hop;                    /* H: 1 .. N */
+	uint32_t n_mels;                 /* B: 1 .. 128 */
+	uint32_t flags;                  /* ACM_FEAT_* */
+	const int16_t *window;           /* w[N], 0 .. 32639 */
+	const int16_t *cs;               /* c[N], -16384 .. 16384 */
+	const uint16_t *mel_first, *mel_count;   /* per band: bins [first, first + count), inside [0, N / 2]; count 0 allowed */
+	const uint32_t *mel_off;         /* per band: where its weights start in mel_w */
+	const uint16_t *mel_w;           /* weights, 0 .. 32768 (Q15) */
+	uint64_t reserved;               /* 0 */
+} acm_feat_bank;
+
+int  acm_batch_decode_windows_features(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+				       acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+				       const acm_fir_opts *fir, const acm_feat_bank *bank, acm_overlay_row *rows, size_t nrows, acm_window_timing *timing);
+/* ACMHIP_OK for a bank the call takes, else ACMHIP_ERR_ARG: the one text of that check.  No device is needed */
+int  acm_feat_bank_check(const acm_feat_bank *bank);
+/* F of a row of T frames (only n_fft, hop and flags of the bank are read; 0 for a NULL bank or a hop of 0).  No device is needed */
+uint64_t acm_feat_frames(uint64_t T, const acm_feat_bank *bank);
+/* The tables of a mel spectrogram, written into the caller's storage: window[n_fft] - a periodic Hann of win_length <= n_fft samples
+ * centred in n_fft, zeros around it, w = nearbyint(32639 * hann) -, cs[n_fft] - nearbyint(16384 * cos(2 pi m / N)) -, and n_mels
+ * triangles between f_min and f_max (Hz, 0 <= f_min < f_max <= rate / 2) on the HTK mel scale 2595 log10(1 + f / 700), no area
+ * normalisation, mel_w = nearbyint(32768 * weight), a band's range being its non-zero weights; mel_off[b] is the sum of the counts
+ * in front of band b.  *n_weights receives the number of weights, whatever else is given.  Any of the table pointers may be NULL
+ * (nothing is written there): a first call with all of them NULL reports the size of mel_w, as acm_dense_resample_taps does for its
+ * taps.  ACMHIP_ERR_ARG for arguments out of range, or weights_cap < *n_weights with mel_w given.  No device is needed */
+int  acm_feat_design(uint32_t rate, uint32_t n_fft, uint32_t win_length, uint32_t hop, uint32_t n_mels, double f_min, double f_max, uint32_t flags,
+		     int16_t *window, int16_t *cs, uint16_t *mel_first, uint16_t *mel_count, uint32_t *mel_off, uint16_t *mel_w, size_t weights_cap,
+		     size_t *n_weights);
+
+/* ------------------------------------------------------------------------
  * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs
  * before its first crop.  acm_index_file parses a whole file to get it, decoding every filler index and dropping it; the device
  * only WALKS the stream (acm_index_scan_wave, csrc/acm_parse.hip: one stream per wavefront, the walk of acm_batch_decode's device

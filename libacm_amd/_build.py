@@ -54,11 +54,12 @@ HIP_SOURCES = ["acm_kernels.hip", "acm_kernels_f32.hip", "acm_parse.hip", "acm_h
                "acm_host_synth.cpp", "acm_plan_cut.cpp", "acm_stage.cpp", "acm_batch_windows.cpp", "acm_batch_layout.cpp", "acm_index_layout.cpp",
                "acm_batch_index.cpp", "acm_window_layout.cpp", "acm_dense_layout.cpp", "acm_dense.hip", "acm_dense_mix.hip", "acm_kernel_geo.cpp",
                "acm_resample_layout.cpp", "acm_dense_resample.hip", "acm_dense_speed.hip", "acm_overlay_layout.cpp", "acm_dense_overlay.hip",
-               "acm_fir_layout.cpp", "acm_dense_fir.hip"]
+               "acm_fir_layout.cpp", "acm_dense_fir.hip", "acm_feat_layout.cpp", "acm_dense_feat.hip"]
 # plain C++ (CPU-dispatched AVX2 inside; the device-free planner; the host stagers; the device-free layouts of the batch calls; the kernels'
 # launch geometry and every query about it): no device pass
 HOST_ONLY = {"acm_host_synth.cpp", "acm_plan_cut.cpp", "acm_stage.cpp", "acm_batch_layout.cpp", "acm_index_layout.cpp", "acm_window_layout.cpp",
-             "acm_dense_layout.cpp", "acm_kernel_geo.cpp", "acm_resample_layout.cpp", "acm_overlay_layout.cpp", "acm_fir_layout.cpp"}
+             "acm_dense_layout.cpp", "acm_kernel_geo.cpp", "acm_resample_layout.cpp", "acm_overlay_layout.cpp", "acm_fir_layout.cpp",
+             "acm_feat_layout.cpp"}
 INCLUDES = {"acm_kernels_f32.hip": ["acm_kernels.hip"]}      # the float32 builds: acm_kernels.hip compiled once more
 
 

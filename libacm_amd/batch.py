@@ -316,6 +316,104 @@ class GpuDecoder:
             delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
         return d_pcm.reshape(-1)[:need].view(shape), gains, delivered, statuses
 
+    def crop_features(self, files, windows, frames, bank, rows=None, index=None, out=None, mix=False, rate=None, speed=None, responses=None,
+                      reverb=None):
+        """mel filterbank features of the batch crop_overlay would make, in the same call (acm_batch_decode_windows_features): the
+        waveform - mono, int16, `frames` samples a row - stays in memory of the decoder's own and only the features are written.
+        windows, frames, index, mix, rate, speed, responses and reverb are crop_overlay's; rows: one Overlay per row, by default
+        Overlay(k) for every window k; bank: a MelBank.
+        -> (feats, gains, frames_delivered, statuses): feats float32 [len(rows), n_mels, F] - [len(rows), F, n_mels] for a time-major
+        bank - with F = bank.frames(frames), whatever the decoder's dtype; the rest as crop_overlay returns it.  The features are
+        defined on integers (include/acm_hip.h): (32639 / 32768)^2 times the power mel spectrogram of the row / 32768, frames padded
+        with zeros; the logarithm is the caller's.  out as in crop_overlay, but float32."""
+        if reverb is not None and responses is None:
+            raise ValueError("GpuDecoder.crop_features: reverb needs responses")
+        if reverb is not None and len(reverb) != len(windows):
+            raise ValueError("GpuDecoder.crop_features: reverb has %d entries for %d windows" % (len(reverb), len(windows)))
+        torch = self.torch
+        files = [_load(f) for f in files]
+        if index is None:
+            index = self.build_index(files)
+        n = len(windows)
+        if rows is None:
+            rows = [Overlay(k) for k in range(n)]
+        nr = len(rows)
+        per = [1] * n
+        if mix:
+            own = self._header_channels(files, index)
+            per = [own[w[0]] or 1 if w[0] < len(files) else 1 for w in windows]
+        if speed is not None and rate is None:
+            raise ValueError("GpuDecoder.crop_features: speed needs rate")
+        if rate is not None:
+            rates = self._header_rates(files, index)
+        F = bank.frames(frames)
+        shape = (nr, F, bank.n_mels) if bank.time_major else (nr, bank.n_mels, F)
+        need = nr * bank.n_mels * F
+        if out is not None and out.dtype != torch.float32:
+            raise ValueError("GpuDecoder.crop_features: out is %s, the features are float32" % (out.dtype,))
+        fits = out is not None and out.numel() >= need and out.is_contiguous()
+        d_out = out if fits else torch.empty(max(need, 1), dtype=torch.float32, device="cuda:%d" % self.ordinal)
+        torch.cuda.current_stream().synchronize()
+        table = np.zeros(nr, dtype=capi.OVERLAY_ROW_DT)
+        if nr:
+            table.view(np.uint32).reshape(nr, -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
+        fir = {}
+        if responses is not None:
+            fir = dict(responses=[r.record for r in responses], of_window=reverb if reverb is not None else [None] * n)
+        statuses, words, _, gains, self.timing = capi.batch_decode_windows_features(
+            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], table,
+            d_out.data_ptr(), d_out.numel(), frames, bank.record, channels=1, planar=True, fmt=self.fmt, parse=self.parse,
+            f32=False, mix=mix, rate=rate, speeds=speed, **fir)
+        delivered = [w // c for w, c in zip(words, per)]
+        if speed is not None:
+            delivered = [capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1)) if d else 0 for d, w, sp in zip(delivered, windows, speed)]
+        elif rate is not None:
+            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
+        return d_out.reshape(-1)[:need].view(shape), gains, delivered, statuses
+
+
+class MelBank:
+    """the tables of GpuDecoder.crop_features (acm_feat_bank): a periodic Hann window of win_length samples (n_fft by default) centred
+    in n_fft, the DFT's cosines and n_mels HTK mel triangles from f_min to f_max (rate / 2 by default), quantised by acm_feat_design.
+    center: frame f is centred on sample f * hop and a row of T samples has 1 + T // hop frames, zeros outside the row (torch.stft
+    with pad_mode="constant"); else only whole frames count.  time_major: features as [row, frame, band]."""
+
+    def __init__(self, rate, n_fft=512, win_length=None, hop=160, n_mels=80, f_min=0.0, f_max=None, center=True, time_major=False):
+        flags = (capi.FEAT_CENTER if center else 0) | (capi.FEAT_TIME_MAJOR if time_major else 0)
+        tables = capi.feat_design(rate, n_fft, win_length, hop, n_mels, f_min, f_max, flags)
+        self._set(n_fft, hop, n_mels, flags, *tables)
+
+    def _set(self, n_fft, hop, n_mels, flags, window, cs, mel_first, mel_count, mel_off, mel_w):
+        self.n_fft, self.hop, self.n_mels, self.flags = n_fft, hop, n_mels, flags
+        self.center, self.time_major = bool(flags & capi.FEAT_CENTER), bool(flags & capi.FEAT_TIME_MAJOR)
+        self.window, self.cs, self.mel_first, self.mel_count, self.mel_off, self.mel_w = window, cs, mel_first, mel_count, mel_off, mel_w
+        self.record = (n_fft, hop, n_mels, flags, window, cs, mel_first, mel_count, mel_off, mel_w)    # as capi.feat_bank takes them
+
+    @classmethod
+    def raw(cls, n_fft, hop, window, cs, mel_first, mel_count, mel_off, mel_w, center=True, time_major=False):
+        """a MelBank of integer tables as they are (include/acm_hip.h has their ranges); n_mels is len(mel_first).  What
+        acm_feat_bank_check does not take is a ValueError"""
+        def table(a, dt, lo, hi):
+            a = np.asarray(a)
+            if a.ndim != 1 or (a.size and ((a != np.rint(a)).any() or a.min() < lo or a.max() > hi)):
+                raise ValueError("MelBank.raw: a table of integers in [%d, %d]" % (lo, hi))
+            return a.astype(dt)
+        b = cls.__new__(cls)
+        flags = (capi.FEAT_CENTER if center else 0) | (capi.FEAT_TIME_MAJOR if time_major else 0)
+        b._set(int(n_fft), int(hop), len(mel_first), flags, table(window, "<i2", -32768, 32767), table(cs, "<i2", -32768, 32767),
+               table(mel_first, "<u2", 0, 65535), table(mel_count, "<u2", 0, 65535), table(mel_off, "<u4", 0, 2 ** 32 - 1),
+               table(mel_w, "<u2", 0, 65535))
+        if b.window.size != b.n_fft or b.cs.size != b.n_fft or not b.mel_count.size == b.mel_off.size == b.n_mels or \
+                (b.n_mels and int(np.where(b.mel_count > 0, b.mel_off.astype(np.int64) + b.mel_count, 0).max()) > b.mel_w.size):
+            raise ValueError("MelBank.raw: tables of n_fft, n_fft, n_mels, n_mels, n_mels entries, and every band's weights")
+        if capi.feat_bank_check(*b.record) != 0:
+            raise ValueError("MelBank.raw: a bank acm_feat_bank_check does not take")
+        return b
+
+    def frames(self, T):
+        """F: the frames of a row of T samples"""
+        return capi.feat_frames(T, self.n_fft, self.hop, self.flags)
+
 
 def snr_q16(db):
     """a signal-to-noise ratio in dB as acm_overlay_row.snr: the power ratio in Q16, 1 .. 2^32 - 1"""

@@ -180,6 +180,19 @@ FIR_MAX_L1 = 65535              # sum |h[t]| of a response at most
 FIR_MAX_SHIFT = 30
 
 
+class FeatBank(C.Structure):
+    _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("n_mels", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_void_p), ("cs", C.c_void_p),
+                ("mel_first", C.c_void_p), ("mel_count", C.c_void_p), ("mel_off", C.c_void_p), ("mel_w", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+FEAT_CENTER = 1                 # FeatBank.flags: frame f is centred on sample f * hop
+FEAT_TIME_MAJOR = 2             # ... and the features are [row][frame][band]
+FEAT_MAX_MELS = 128
+FEAT_WINDOW_MAX = 32639         # the window's peak: both signed bytes of a windowed sample fit int8
+FEAT_CS_ONE = 16384
+FEAT_W_ONE = 32768
+
+
 class BatchIndexOut(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("max_blocks", C.c_size_t), ("blocks", C.c_uint32), ("end_status", C.c_int32), ("status", C.c_int32),
                 ("reserved", C.c_uint32)]
@@ -222,6 +235,7 @@ ACMHIP_SYMBOLS = [
     "acm_index_file", "acm_stage_window", "acm_batch_window_pcm_words", "acm_batch_decode_windows", "acm_batch_decode_windows_dense",
     "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
     "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain", "acm_batch_decode_windows_overlay_fir", "acm_dense_fir_check",
+    "acm_batch_decode_windows_features", "acm_feat_bank_check", "acm_feat_frames", "acm_feat_design",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info", "acmhip_device_set_launch_caps",
 ]
@@ -340,6 +354,14 @@ def lib():
                                                            C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(FirOpts), C.POINTER(OverlayRow), sz,
                                                            C.POINTER(WindowTiming)]
         L.acm_dense_fir_check.argtypes = [C.POINTER(FirResponse)]
+    if hasattr(L, "acm_batch_decode_windows_features"):
+        L.acm_batch_decode_windows_features.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                                        C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(FirOpts), C.POINTER(FeatBank),
+                                                        C.POINTER(OverlayRow), sz, C.POINTER(WindowTiming)]
+        L.acm_feat_bank_check.argtypes = [C.POINTER(FeatBank)]
+        L.acm_feat_frames.argtypes = [C.c_uint64, C.POINTER(FeatBank)]
+        L.acm_feat_frames.restype = C.c_uint64
+        L.acm_feat_design.argtypes = [C.c_uint32] * 5 + [C.c_double, C.c_double, C.c_uint32] + [vp] * 6 + [sz, C.POINTER(sz)]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -1251,7 +1273,7 @@ def dense_overlay_gain(energy_a, energy_b, snr):
 
 def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                  fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False, _fir=None):
+                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False, _fir=None, _feat=None):
     """acm_batch_decode_windows_overlay: the windows are the SOURCE rows of batch_decode_windows_dense (every argument it has means the
     same), and d_pcm receives len(rows) output rows of frames * channels samples, row r at sample r * frames * channels.  rows: tuples
     (a, b, vol, snr, gain) of acm_overlay_row's inputs - b None for ACM_OVERLAY_NONE - or 6-tuples that end in `reserved`, or an array
@@ -1265,6 +1287,9 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
     opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
     name = "acm_batch_decode_windows_overlay" if _fir is None else "acm_batch_decode_windows_overlay_fir"
     extra = () if _fir is None else (C.byref(_fir[0]) if _fir[0] is not None else None,)
+    if _feat is not None:               # batch_decode_windows_features': (FeatBank or None, what it points into)
+        name = "acm_batch_decode_windows_features"
+        extra = (extra or (None,)) + (C.byref(_feat[0]) if _feat[0] is not None else None,)
     if dense_flags is None:
         dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
             (DENSE_SPEED if speeds is not None else 0)
@@ -1340,6 +1365,57 @@ def batch_decode_windows_overlay_fir(dev, files, index, windows, rows, d_pcm, d_
     of_window[k] None: not filtered.  no_fir: no acm_fir_opts at all; nresp, fir_reserved (tests of the refusals): as fir_opts takes them"""
     o, keep = (None, None) if no_fir else fir_opts(responses, of_window, nresp, fir_reserved)
     return batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, _fir=(o, keep), **kw)
+
+
+def feat_bank(n_fft, hop, n_mels, flags, window, cs, mel_first, mel_count, mel_off, mel_w, reserved=0):
+    """(FeatBank, the arrays it points into) of acm_feat_bank's fields; a table given as None is a null pointer"""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dtype=dt)
+    keep = (arr(window, "<i2"), arr(cs, "<i2"), arr(mel_first, "<u2"), arr(mel_count, "<u2"), arr(mel_off, "<u4"), arr(mel_w, "<u2"))
+    # an empty table still needs a pointer: the library reads none of it
+    ptr = [None if a is None else (a if a.size else np.zeros(1, a.dtype)) for a in keep]
+    return FeatBank(n_fft, hop, n_mels, flags, *[None if a is None else a.ctypes.data for a in ptr], reserved), (keep, ptr)
+
+
+def feat_bank_check(*args, **kw):
+    """acm_feat_bank_check over feat_bank's arguments: 0 for a bank acm_batch_decode_windows_features takes, else ERR_ARG"""
+    b, keep = feat_bank(*args, **kw)
+    return int(lib().acm_feat_bank_check(C.byref(b)))
+
+
+def feat_frames(T, n_fft, hop, flags):
+    """acm_feat_frames: the frames F of a row of T samples"""
+    b = FeatBank(n_fft, hop, 1, flags)
+    return int(lib().acm_feat_frames(T, C.byref(b)))
+
+
+def feat_design(rate, n_fft=512, win_length=None, hop=160, n_mels=80, f_min=0.0, f_max=None, flags=FEAT_CENTER):
+    """acm_feat_design -> (window int16 [n_fft], cs int16 [n_fft], mel_first uint16 [n_mels], mel_count, mel_off uint32, mel_w uint16):
+    a periodic Hann of win_length (n_fft by default) centred in n_fft, the cosines, HTK mel triangles from f_min to f_max (rate / 2 by
+    default).  ValueError for arguments the library does not take"""
+    win_length = n_fft if win_length is None else win_length
+    f_max = rate / 2.0 if f_max is None else f_max
+    L = lib()
+    nw = C.c_size_t(0)
+    args = (rate, n_fft, win_length, hop, n_mels, float(f_min), float(f_max), flags)
+    if L.acm_feat_design(*args, None, None, None, None, None, None, 0, C.byref(nw)) != 0:
+        raise ValueError("acm_feat_design: rate %r, n_fft %r, win_length %r, hop %r, n_mels %r, f_min %r, f_max %r, flags %r" % args)
+    window, cs = np.zeros(n_fft, "<i2"), np.zeros(n_fft, "<i2")
+    first, count, off = np.zeros(n_mels, "<u2"), np.zeros(n_mels, "<u2"), np.zeros(n_mels, "<u4")
+    w = np.zeros(max(nw.value, 1), "<u2")
+    _check(L.acm_feat_design(*args, window.ctypes.data, cs.ctypes.data, first.ctypes.data, count.ctypes.data, off.ctypes.data, w.ctypes.data,
+                             nw.value, C.byref(nw)), "acm_feat_design")
+    return window, cs, first, count, off, w[:nw.value]
+
+
+def batch_decode_windows_features(dev, files, index, windows, rows, d_out, d_out_words, frames, bank, responses=None, of_window=None, no_bank=False,
+                                  **kw):
+    """acm_batch_decode_windows_features: batch_decode_windows_overlay_fir (every other argument and what is returned are its; channels
+    stays 1) whose int16 rows stay in the handle, d_out receiving the float32 mel features of them, d_out_words float32 elements.
+    bank: feat_bank's arguments as a tuple or a dict.  responses None: no acm_fir_opts.  no_bank (tests): a null bank"""
+    o, keep = (None, None) if responses is None else fir_opts(responses, of_window, kw.pop("nresp", None), kw.pop("fir_reserved", 0))
+    b, keep_b = (None, None) if no_bank else feat_bank(**bank) if isinstance(bank, dict) else feat_bank(*bank)
+    return batch_decode_windows_overlay(dev, files, index, windows, rows, d_out, d_out_words, frames, _fir=(o, keep), _feat=(b, keep_b), **kw)
 
 
 # --------------------------------------------------------------------------- the block index of a batch

@@ -28,6 +28,10 @@
  *
  * acm_batch_decode_windows_overlay_fir is that run with one launch of acm_dense_fir.hip between the gather launch and the energy
  * launch: the windows acm_fir_layout.cpp lists are filtered into rows behind the source rows, and the overlay's tables name those.
+ *
+ * acm_batch_decode_windows_features is that run with its combine launch aimed at the handle's feature arena, int16, and two launches
+ * of acm_dense_feat.hip behind it that make the caller's float32 features from those rows: the bank's check, its tables as they are
+ * uploaded and the arena's layout are acm_feat_layout.cpp's.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -38,6 +42,7 @@
 #include "acm_batch_common.h"
 #include "acm_dense_layout.h"
 #include "acm_device.h"
+#include "acm_feat_layout.h"
 #include "acm_fir_layout.h"
 #include "acm_hip.h"
 #include "acm_overlay_layout.h"
@@ -55,9 +60,10 @@ class WinRun {
 public:
 	WinRun(acmhip_device *dev_, const acm_batch_item *items_, acm_batch_window *wins_, const acm_batch_opts &opts_,
 	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseLayout *dense_ = nullptr,
-	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr, const FirLayout *fir_ = nullptr)
+	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr, const FirLayout *fir_ = nullptr,
+	       const FeatLayout *feat_ = nullptr)
 		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), dense(dense_), dense_out(dense_out_),
-		  overlay(overlay_), overlay_rows(overlay_rows_), fir(fir_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
+		  overlay(overlay_), overlay_rows(overlay_rows_), fir(fir_), feat(feat_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
 		  pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
 	{
 		for (size_t k : L.act)
@@ -86,16 +92,20 @@ private:
 	int upload_slices(const std::vector<size_t> &ids);
 	void collect(PlanStreams &ps);
 	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, behind them a dense call's row table, and behind that an
-	 * overlay call's tables, and behind those the taps and the rows of its filter pass */
+	 * overlay call's tables, and behind those the taps and the rows of its filter pass, and behind those a features call's bank */
 	size_t overlay_off() const { return (size_t)round_up(dense->table_off(L) + dense->table_bytes(), 64); }
 	size_t fir_off() const { return (size_t)round_up(overlay_off() + overlay->table_bytes(), 64); }
+	size_t feat_off() const { return (size_t)round_up(fir ? fir_off() + fir->table_bytes() : overlay_off() + overlay->table_bytes(), 64); }
 	size_t jobs_bytes() const
 	{
+		if (feat)
+			return feat_off() + feat->table_bytes();
 		if (fir)
 			return fir_off() + fir->table_bytes();
 		return overlay ? overlay_off() + overlay->table_bytes() : dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes();
 	}
 	int combine_rows();
+	int make_features();
 
 	ArenaLock lock;
 	acmhip_device *const dev;
@@ -111,6 +121,7 @@ private:
 	const OverlayLayout *const overlay;     /* an overlay call (a dense call whose rows go to the source arena), else null */
 	acm_overlay_row *const overlay_rows;    /* ... and the caller's row table, for what comes back */
 	const FirLayout *const fir;             /* an overlay call some of whose windows are filtered, else null */
+	const FeatLayout *const feat;           /* an overlay call whose rows go to the feature arena and are framed there, else null */
 	const hipStream_t st;
 	const bool out_f32, keep_on_device;
 	const size_t pcm_unit;
@@ -124,6 +135,7 @@ private:
 	uint8_t *h_files = nullptr, *d_files = nullptr, *h_jobs = nullptr, *d_jobs = nullptr;
 	uint32_t *d_colpos = nullptr;
 	int16_t *d_src = nullptr;               /* the source rows of an overlay call */
+	uint8_t *d_feat = nullptr;              /* the output rows of a features call, and the DFT's operand behind them */
 };
 
 /* Arenas (they live in the device handle and are reused by the next call) and events.  Needs nothing but the layout */
@@ -150,6 +162,8 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, dense->pcm_arena_words(L.pcm_total) * sizeof(int16_t), (void **)&d_pcm));
 	if (overlay)
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_SRC, overlay->src_arena_words() * sizeof(int16_t), (void **)&d_src));
+	if (feat)
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_FEAT, feat->arena_bytes(), (void **)&d_feat));
 	if (dense || !L.dev_ids.empty()) {
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes(), (void **)&h_jobs));
 		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes(), (void **)&d_jobs));
@@ -339,6 +353,11 @@ int WinRun::synthesise_and_gather()
 		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + fir_off(), up, fir->table_bytes(), hipMemcpyHostToDevice, st));
 		tm.h2d_bytes += fir->table_bytes();
 	}
+	if (feat) {
+		feat->pack(h_jobs + feat_off());
+		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + feat_off(), h_jobs + feat_off(), feat->table_bytes(), hipMemcpyHostToDevice, st));
+		tm.h2d_bytes += feat->table_bytes();
+	}
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
@@ -375,6 +394,8 @@ int WinRun::synthesise_and_gather()
 		return acmhip_report_hip(e, name);
 	if (overlay)
 		ACM_TRY(combine_rows());
+	if (feat)
+		ACM_TRY(make_features());
 	ACM_HIP_TRY(hipEventRecord(ev[3], st));
 	const bool results = overlay && !overlay->rows.empty();
 	const size_t res_at = results ? overlay_off() + overlay->result_off() : 0;
@@ -422,9 +443,36 @@ int WinRun::combine_rows()
 			return acmhip_report_hip(e, "acmk_launch_dense_energy");
 	}
 	const int e = acmk_launch_dense_overlay(d_src, reinterpret_cast<const AcmOverlayRow *>(d_jobs + at), d_energy,
-						reinterpret_cast<AcmOverlayResult *>(d_jobs + at + overlay->result_off()), overlay->rows.size(), dense_out,
-						overlay->row_words, dense->f32, caps.dense_grid, st);
+						reinterpret_cast<AcmOverlayResult *>(d_jobs + at + overlay->result_off()), overlay->rows.size(),
+						feat ? d_feat : dense_out, overlay->row_words, feat ? false : dense->f32, caps.dense_grid, st);
 	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_overlay") : ACMHIP_OK;
+}
+
+/* a features call, behind the combine launch that wrote the int16 rows into the feature arena: the bank's tables went up with the
+ * others; the DFT's operand is made of the cosines behind the rows, and the feature launch writes the caller's tensor */
+int WinRun::make_features()
+{
+	if (feat->out_words == 0)
+		return ACMHIP_OK;
+	const uint8_t *tab = d_jobs + feat_off();
+	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
+	uint8_t *d_twiddle = d_feat + feat->twiddle_off();
+	int e = acmk_launch_feat_twiddle(reinterpret_cast<const int16_t *>(tab + feat->cs_off()), feat->bank.n_fft, d_twiddle, st);
+	if (e != 0)
+		return acmhip_report_hip(e, "acmk_launch_feat_twiddle");
+	AcmFeatDesc d{};
+	d.n_fft = feat->bank.n_fft;
+	d.hop = feat->bank.hop;
+	d.n_mels = feat->bank.n_mels;
+	d.flags = feat->bank.flags;
+	d.window = reinterpret_cast<const int16_t *>(tab + feat->window_off());
+	d.mel_first = reinterpret_cast<const uint16_t *>(tab + feat->first_off());
+	d.mel_count = reinterpret_cast<const uint16_t *>(tab + feat->count_off());
+	d.mel_off = reinterpret_cast<const uint32_t *>(tab + feat->off_off());
+	d.mel_w = reinterpret_cast<const uint16_t *>(tab + feat->w_off());
+	d.twiddle = d_twiddle;
+	e = acmk_launch_dense_feat(reinterpret_cast<const int16_t *>(d_feat), feat->nrows, feat->T, &d, static_cast<float *>(dense_out), caps.dense_grid, st);
+	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_feat") : ACMHIP_OK;
 }
 
 /* headers, and whether every index is one its file can have - before anything derived from it is used */
@@ -548,10 +596,12 @@ static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_
 }
 
 /* the dense call without its wall clock; with_overlay: acm_batch_decode_windows_overlay - the windows are the sources of the nrows rows of
- * `rows`, which are what opts->d_pcm receives; fir: acm_batch_decode_windows_overlay_fir's responses, else null */
+ * `rows`, which are what opts->d_pcm receives; fir: acm_batch_decode_windows_overlay_fir's responses, else null; with_feat:
+ * acm_batch_decode_windows_features - the rows go to the feature arena, int16, and opts->d_pcm receives `bank`'s features of them */
 static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
 				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm, bool with_overlay = false,
-				acm_overlay_row *rows = nullptr, size_t nrows = 0, const acm_fir_opts *fir = nullptr)
+				acm_overlay_row *rows = nullptr, size_t nrows = 0, const acm_fir_opts *fir = nullptr, bool with_feat = false,
+				const acm_feat_bank *bank = nullptr)
 {
 	Prelude pre;
 	ACM_TRY(pre.begin(dev, items, n, index, wins, nwin, opts_in));
@@ -568,7 +618,8 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 		return ACMHIP_ERR_ARG;
 	}
 	OverlayLayout O;
-	if (with_overlay && acm_overlay_prepare(rows, nrows, nwin, D.row_words, opts.d_pcm_words, &O) != ACMHIP_OK) {
+	/* ... and of a features call against the features of those rows, by its own layout again */
+	if (with_overlay && acm_overlay_prepare(rows, nrows, nwin, D.row_words, with_feat ? ~0ull : opts.d_pcm_words, &O) != ACMHIP_OK) {
 		acmhip_set_error_text("acm_batch_decode_windows_overlay: a row table the call does not take (include/acm_hip.h)");
 		return ACMHIP_ERR_ARG;
 	}
@@ -579,6 +630,11 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 			return ACMHIP_ERR_ARG;
 		}
 		acm_fir_remap(F, &O);
+	}
+	FeatLayout M;
+	if (with_feat && acm_feat_prepare(bank, dense->channels, D.frames, nrows, opts.d_pcm_words, &M) != ACMHIP_OK) {
+		acmhip_set_error_text("acm_batch_decode_windows_features: a bank or a tensor the call does not take (include/acm_hip.h)");
+		return ACMHIP_ERR_ARG;
 	}
 	WindowLayout layout;
 	ACM_TRY(acm_window_layout(its.data(), n, D.wins.data(), nwin, D.inner, &layout, &pool));
@@ -592,7 +648,8 @@ static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items,
 		return ACMHIP_OK;
 
 	const auto t_hdr = clk::now();
-	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows, F.nfilt() ? &F : nullptr);
+	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows, F.nfilt() ? &F : nullptr,
+		   with_feat ? &M : nullptr);
 	ACM_TRY(run.fetch_arenas(t_hdr));
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
@@ -619,6 +676,16 @@ extern "C" int acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const ac
 {
 	return timed(timing,
 		     [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows, fir); });
+}
+
+extern "C" int acm_batch_decode_windows_features(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+						 acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
+						 const acm_fir_opts *fir, const acm_feat_bank *bank, acm_overlay_row *rows, size_t nrows,
+						 acm_window_timing *timing)
+{
+	return timed(timing, [&](acm_window_timing &tm) {
+		return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows, fir, true, bank);
+	});
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,

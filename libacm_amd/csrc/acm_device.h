@@ -153,6 +153,16 @@ struct AcmFirRow {
 	int32_t lead;
 	uint32_t shift;
 };
+/* acm_batch_decode_windows_features (acm_dense_feat.hip): the bank as the feature kernel reads it - device pointers to the uploaded
+ * tables (acm_feat_layout.h: the window on a multiple of 16 bytes) and to the DFT's B operand acm_feat_twiddle made of cs */
+struct AcmFeatDesc {
+	uint32_t n_fft, hop, n_mels, flags;
+	const int16_t *window;
+	const uint16_t *mel_first, *mel_count;
+	const uint32_t *mel_off;
+	const uint16_t *mel_w;
+	const void *twiddle;
+};
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
 #define ACM_K1_MIN_LEVEL 5
@@ -195,6 +205,8 @@ enum {
 	ACM_ARENA_D_MARKS, ACM_ARENA_H_MARKS,           /* the marks of a batch index build's two groups (acm_batch_index.cpp), or of a decode that hands
 	                                                   the index out (acm_batch_decode_indexed: hdr_total of them), on the device and pinned */
 	ACM_ARENA_D_SRC,                                /* the source rows of acm_batch_decode_windows_overlay: int16 PCM, nwin rows of a dense call */
+	ACM_ARENA_D_FEAT,                               /* acm_batch_decode_windows_features: the int16 rows its combine launch writes, and behind
+	                                                   them the DFT's B operand (acm_feat_layout.h) */
 	ACM_ARENA_SLOTS
 };
 /* is this slot pinned host memory (else device memory)? */
@@ -390,6 +402,14 @@ int acmk_launch_dense_overlay(const int16_t *d_src, const AcmOverlayRow *d_rows,
  * writes samples of those rows alone, element by element or as whole aligned lines inside a row.  Nothing allocated, nothing waited for */
 int acmk_launch_dense_fir(int16_t *d_src, const AcmFirRow *d_rows, uint64_t nfilt, const uint32_t *d_taps, uint64_t frames, uint32_t channels,
 			  int planar, uint32_t dense_grid, void *stream);
+/* acm_dense_feat.hip, behind the combine launch of a features call.  acmk_launch_feat_twiddle: the B operand of an n_fft-point DFT,
+ * acm_feat_twiddle_bytes(n_fft) bytes at d_twiddle (16-byte aligned), from the n_fft cosines at d_cs.  acmk_launch_dense_feat: the
+ * features of nrows rows of `frames` int16 samples at d_rows into d_out, float32, nrows * n_mels * F elements in the layout the
+ * bank's flags name; reads samples of those rows alone, element by element, and writes those elements alone.  Nothing allocated,
+ * nothing waited for */
+int acmk_launch_feat_twiddle(const int16_t *d_cs, uint32_t n_fft, void *d_twiddle, void *stream);
+int acmk_launch_dense_feat(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const struct AcmFeatDesc *desc, float *d_out, uint32_t dense_grid,
+			   void *stream);
 #ifdef __cplusplus
 }
 #endif

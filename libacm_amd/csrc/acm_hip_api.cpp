@@ -247,11 +247,11 @@ namespace {
 const char *const g_slot_names[ACM_ARENA_SLOTS] = {
 	"H_IDX", "H_HDR", "H_PCM", "H_FILES", "H_JOBS", "H_PKBLOB", "H_PKCHUNK",
 	"D_IDX", "D_HDR", "D_PCM", "D_FILES", "D_COLPOS", "D_JOBS", "D_STAGE",
-	"D_PKBLOB", "D_PKCHUNK", "D_BLKOFF", "D_MARKS", "H_MARKS", "D_SRC",
+	"D_PKBLOB", "D_PKCHUNK", "D_BLKOFF", "D_MARKS", "H_MARKS", "D_SRC", "D_FEAT",
 };
 
 /* What the fill mode leaves in a slot (acmhip_device_set_fill):
- *   D_PCM, H_PCM, D_SRC   0xA5 - output only (D_SRC holds the PCM rows an overlay call combines: a row nobody wrote is visibly wrong): nothing reads a sample back, and the pattern is the one the arena-contract tests poison with;
+ *   D_PCM, H_PCM, D_SRC, D_FEAT   0xA5 - output only (D_FEAT holds the rows a features call frames, and behind them the DFT operand its own launch writes in full; D_SRC holds the PCM rows an overlay call combines: a row nobody wrote is visibly wrong): nothing reads a sample back, and the pattern is the one the arena-contract tests poison with;
  *   D_IDX, H_IDX   0x5A (index 0x5A5A) - the staged int16 indices are operands and nothing else: the parser's column kernel and the host
  *                  stagers only store them, the synthesis kernels multiply them by the block's val (value = idx * val) and the packers
  *                  compare them with class bounds; no kernel forms an address, an LDS offset or a trip count from one, so a row nobody
@@ -267,6 +267,7 @@ int fill_byte(int slot)
 	case ACM_ARENA_D_PCM:
 	case ACM_ARENA_H_PCM:
 	case ACM_ARENA_D_SRC:
+	case ACM_ARENA_D_FEAT:
 		return 0xA5;
 	case ACM_ARENA_D_IDX:
 	case ACM_ARENA_H_IDX:
