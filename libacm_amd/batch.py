@@ -201,6 +201,67 @@ class GpuDecoder:
             kept = self._rates = (index, [found.get(f) for f in range(len(files))])
         return kept[1]
 
+    def _sources(self, name, files, windows, channels, index, mix, rate, speed, responses=None, reverb=None):
+        """what the three crop_* methods (`name` is the one that asks) do with their source windows before the call: the checks of
+        speed and reverb, the files loaded, the index, the samples per frame of every window's file - its own header's with mix (a
+        file without one is checked as the batch's kind) -, the header rates where the call resamples, the windows in samples and the
+        filter's keywords.  -> (files, index, per, rates, scaled windows, fir keywords)"""
+        if reverb is not None and responses is None:
+            raise ValueError("GpuDecoder.%s: reverb needs responses" % name)
+        if reverb is not None and len(reverb) != len(windows):
+            raise ValueError("GpuDecoder.%s: reverb has %d entries for %d windows" % (name, len(reverb), len(windows)))
+        files = [_load(f) for f in files]
+        if index is None:
+            index = self.build_index(files)
+        per = [channels] * len(windows)
+        if mix:
+            own = self._header_channels(files, index)
+            per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
+        if speed is not None and rate is None:
+            raise ValueError("GpuDecoder.%s: speed needs rate" % name)
+        rates = self._header_rates(files, index) if rate is not None else None
+        fir = {}
+        if responses is not None:
+            fir = dict(responses=[r.record for r in responses], of_window=reverb if reverb is not None else [None] * len(windows))
+        return files, index, per, rates, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], fir
+
+    def _output(self, out, need, dtype, mismatch):
+        """the flat tensor a call writes `need` elements of `dtype` into: `out` where it is contiguous and large enough, else a new
+        one; torch's stream is drained, since a block the caching allocator hands out may still be in use by work queued on it"""
+        if out is not None and out.dtype != dtype:
+            raise ValueError(mismatch % (out.dtype,))
+        fits = out is not None and out.numel() >= need and out.is_contiguous()
+        d_out = out if fits else self.torch.empty(max(need, 1), dtype=dtype, device="cuda:%d" % self.ordinal)
+        self.torch.cuda.current_stream().synchronize()
+        return d_out
+
+    @staticmethod
+    def _row_table(rows):
+        """the overlay row table in one piece: an Overlay has made its record when it was built"""
+        table = np.zeros(len(rows), dtype=capi.OVERLAY_ROW_DT)
+        if len(rows):
+            table.view(np.uint32).reshape(len(rows), -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
+        return table
+
+    @staticmethod
+    def _delivered(words, per, windows, rates, rate, speed):
+        """frames every row got, from the samples its window delivered: the window's own frames, or the output frames of a row that
+        is resampled (a row that got frames is of a file with a rate the filter takes)"""
+        delivered = [w // c for w, c in zip(words, per)]
+        if speed is not None:
+            # (a batch has a handful of distinct (frames, rate, speed): each is asked of the library once)
+            known = {}
+            for k, (d, w, sp) in enumerate(zip(delivered, windows, speed)):
+                if d:
+                    sp = tuple(sp) if sp else (1, 1)
+                    key = (d, rates[w[0]], sp)
+                    if key not in known:
+                        known[key] = capi.dense_speed_frames(d, rates[w[0]], rate, sp)
+                    delivered[k] = known[key]
+        elif rate is not None:
+            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
+        return delivered
+
     def crop_batch(self, files, windows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None):
         """Random-access crops as one batch tensor: windows = (file_no, first_frame, n_frames) triples with n_frames <= frames, index as
         for crop().  -> (batch, frames_delivered, statuses): batch is a tensor of this decoder's dtype shaped [N, channels, frames]
@@ -220,44 +281,16 @@ class GpuDecoder:
         speed (ACM_DENSE_SPEED, with rate): a (num, den) pair per window, or None for 1/1 - window k is played at num / den (11/10:
         faster, fewer frames), which is a resampling of its own; any ratio down to an eighth is taken, the odd ones by a filter that
         interpolates between prototype phases.  source_frames(..., speed=) says how long a window fits a row."""
-        torch = self.torch
-        files = [_load(f) for f in files]
-        if index is None:
-            index = self.build_index(files)
+        files, index, per, rates, scaled, _ = self._sources("crop_batch", files, windows, channels, index, mix, rate, speed)
         n = len(windows)
-        # samples per frame of every window's file: its own header's with mix (a file without one is checked as the batch's kind)
-        per = [channels] * n
-        if mix:
-            own = self._header_channels(files, index)
-            per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
-        if speed is not None and rate is None:
-            raise ValueError("GpuDecoder.crop_batch: speed needs rate")
-        if rate is not None:
-            rates = self._header_rates(files, index)
         shape = (n, channels, frames) if planar else (n, frames, channels)
         need = n * channels * frames
-        if out is not None and out.dtype != self.dtype:
-            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
-        fits = out is not None and out.numel() >= need and out.is_contiguous()
-        d_pcm = out if fits else torch.empty(max(need, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
-        torch.cuda.current_stream().synchronize()
+        d_pcm = self._output(out, need, self.dtype, "GpuDecoder: out is %%s, the decoder writes %s" % (self.dtype,))
         statuses, words, self.timing = capi.batch_decode_windows_dense(
-            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], d_pcm.data_ptr(), d_pcm.numel(),
-            frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse, f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed)
+            self.dev, files, index, scaled, d_pcm.data_ptr(), d_pcm.numel(), frames, channels=channels, planar=planar, fmt=self.fmt,
+            parse=self.parse, f32=self.dtype == self.torch.float32, mix=mix, rate=rate, speeds=speed)
         # the call returns with its stream drained: the batch is complete and visible to torch's streams
-        delivered = [w // c for w, c in zip(words, per)]
-        if speed is not None:
-            # (a batch has a handful of distinct (frames, rate, speed): each is asked of the library once)
-            known = {}
-            for k, (d, w, sp) in enumerate(zip(delivered, windows, speed)):
-                key = (d, rates[w[0]], sp)
-                if d and key not in known:
-                    known[key] = capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1))
-                delivered[k] = known[key] if d else 0
-        elif rate is not None:      # a row that got frames is of a file with a rate the filter takes
-            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
-        return d_pcm.reshape(-1)[:need].view(shape), delivered, statuses
-
+        return d_pcm.reshape(-1)[:need].view(shape), self._delivered(words, per, windows, rates, rate, speed), statuses
 
     def crop_overlay(self, files, windows, rows, frames, channels=1, planar=True, index=None, out=None, mix=False, rate=None, speed=None,
                      responses=None, reverb=None):
@@ -273,48 +306,16 @@ class GpuDecoder:
         responses, reverb (acm_batch_decode_windows_overlay_fir): a list of Response, and per window the number of the one its source
         row is convolved with before anything else is made from it - energies included, so the noise is set against the reverberant
         speech - or None for a window that stays dry.  The row keeps its length: a crop's tail rings on into the zeros behind it."""
-        if reverb is not None and responses is None:
-            raise ValueError("GpuDecoder.crop_overlay: reverb needs responses")
-        if reverb is not None and len(reverb) != len(windows):
-            raise ValueError("GpuDecoder.crop_overlay: reverb has %d entries for %d windows" % (len(reverb), len(windows)))
-        torch = self.torch
-        files = [_load(f) for f in files]
-        if index is None:
-            index = self.build_index(files)
-        n, nr = len(windows), len(rows)
-        per = [channels] * n
-        if mix:
-            own = self._header_channels(files, index)
-            per = [own[w[0]] or channels if w[0] < len(files) else channels for w in windows]
-        if speed is not None and rate is None:
-            raise ValueError("GpuDecoder.crop_overlay: speed needs rate")
-        if rate is not None:
-            rates = self._header_rates(files, index)
+        files, index, per, rates, scaled, fir = self._sources("crop_overlay", files, windows, channels, index, mix, rate, speed, responses, reverb)
+        nr = len(rows)
         shape = (nr, channels, frames) if planar else (nr, frames, channels)
         need = nr * channels * frames
-        if out is not None and out.dtype != self.dtype:
-            raise ValueError("GpuDecoder: out is %s, the decoder writes %s" % (out.dtype, self.dtype))
-        fits = out is not None and out.numel() >= need and out.is_contiguous()
-        d_pcm = out if fits else torch.empty(max(need, 1), dtype=self.dtype, device="cuda:%d" % self.ordinal)
-        torch.cuda.current_stream().synchronize()
-        # the row table in one piece: an Overlay has made its record when it was built
-        table = np.zeros(nr, dtype=capi.OVERLAY_ROW_DT)
-        if nr:
-            table.view(np.uint32).reshape(nr, -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
-        call, fir = capi.batch_decode_windows_overlay, {}
-        if responses is not None:
-            call = capi.batch_decode_windows_overlay_fir
-            fir = dict(responses=[r.record for r in responses], of_window=reverb if reverb is not None else [None] * n)
+        d_pcm = self._output(out, need, self.dtype, "GpuDecoder: out is %%s, the decoder writes %s" % (self.dtype,))
+        call = capi.batch_decode_windows_overlay_fir if responses is not None else capi.batch_decode_windows_overlay
         statuses, words, _, gains, self.timing = call(
-            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], table,
-            d_pcm.data_ptr(), d_pcm.numel(), frames, channels=channels, planar=planar, fmt=self.fmt, parse=self.parse,
-            f32=self.dtype == torch.float32, mix=mix, rate=rate, speeds=speed, **fir)
-        delivered = [w // c for w, c in zip(words, per)]
-        if speed is not None:
-            delivered = [capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1)) if d else 0 for d, w, sp in zip(delivered, windows, speed)]
-        elif rate is not None:
-            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
-        return d_pcm.reshape(-1)[:need].view(shape), gains, delivered, statuses
+            self.dev, files, index, scaled, self._row_table(rows), d_pcm.data_ptr(), d_pcm.numel(), frames, channels=channels, planar=planar,
+            fmt=self.fmt, parse=self.parse, f32=self.dtype == self.torch.float32, mix=mix, rate=rate, speeds=speed, **fir)
+        return d_pcm.reshape(-1)[:need].view(shape), gains, self._delivered(words, per, windows, rates, rate, speed), statuses
 
     def crop_features(self, files, windows, frames, bank, rows=None, index=None, out=None, mix=False, rate=None, speed=None, responses=None,
                       reverb=None):
@@ -326,50 +327,18 @@ class GpuDecoder:
         bank - with F = bank.frames(frames), whatever the decoder's dtype; the rest as crop_overlay returns it.  The features are
         defined on integers (include/acm_hip.h): (32639 / 32768)^2 times the power mel spectrogram of the row / 32768, frames padded
         with zeros; the logarithm is the caller's.  out as in crop_overlay, but float32."""
-        if reverb is not None and responses is None:
-            raise ValueError("GpuDecoder.crop_features: reverb needs responses")
-        if reverb is not None and len(reverb) != len(windows):
-            raise ValueError("GpuDecoder.crop_features: reverb has %d entries for %d windows" % (len(reverb), len(windows)))
-        torch = self.torch
-        files = [_load(f) for f in files]
-        if index is None:
-            index = self.build_index(files)
-        n = len(windows)
+        files, index, per, rates, scaled, fir = self._sources("crop_features", files, windows, 1, index, mix, rate, speed, responses, reverb)
         if rows is None:
-            rows = [Overlay(k) for k in range(n)]
+            rows = [Overlay(k) for k in range(len(windows))]
         nr = len(rows)
-        per = [1] * n
-        if mix:
-            own = self._header_channels(files, index)
-            per = [own[w[0]] or 1 if w[0] < len(files) else 1 for w in windows]
-        if speed is not None and rate is None:
-            raise ValueError("GpuDecoder.crop_features: speed needs rate")
-        if rate is not None:
-            rates = self._header_rates(files, index)
         F = bank.frames(frames)
         shape = (nr, F, bank.n_mels) if bank.time_major else (nr, bank.n_mels, F)
         need = nr * bank.n_mels * F
-        if out is not None and out.dtype != torch.float32:
-            raise ValueError("GpuDecoder.crop_features: out is %s, the features are float32" % (out.dtype,))
-        fits = out is not None and out.numel() >= need and out.is_contiguous()
-        d_out = out if fits else torch.empty(max(need, 1), dtype=torch.float32, device="cuda:%d" % self.ordinal)
-        torch.cuda.current_stream().synchronize()
-        table = np.zeros(nr, dtype=capi.OVERLAY_ROW_DT)
-        if nr:
-            table.view(np.uint32).reshape(nr, -1)[:, :5] = np.array([r.raw for r in rows], dtype=np.uint32)
-        fir = {}
-        if responses is not None:
-            fir = dict(responses=[r.record for r in responses], of_window=reverb if reverb is not None else [None] * n)
+        d_out = self._output(out, need, self.torch.float32, "GpuDecoder.crop_features: out is %s, the features are float32")
         statuses, words, _, gains, self.timing = capi.batch_decode_windows_features(
-            self.dev, files, index, [(f, first * c, count * c) for (f, first, count), c in zip(windows, per)], table,
-            d_out.data_ptr(), d_out.numel(), frames, bank.record, channels=1, planar=True, fmt=self.fmt, parse=self.parse,
-            f32=False, mix=mix, rate=rate, speeds=speed, **fir)
-        delivered = [w // c for w, c in zip(words, per)]
-        if speed is not None:
-            delivered = [capi.dense_speed_frames(d, rates[w[0]], rate, sp or (1, 1)) if d else 0 for d, w, sp in zip(delivered, windows, speed)]
-        elif rate is not None:
-            delivered = [capi.dense_resampled_frames(d, rates[w[0]], rate) if d else 0 for d, w in zip(delivered, windows)]
-        return d_out.reshape(-1)[:need].view(shape), gains, delivered, statuses
+            self.dev, files, index, scaled, self._row_table(rows), d_out.data_ptr(), d_out.numel(), frames, bank.record, channels=1, planar=True,
+            fmt=self.fmt, parse=self.parse, f32=False, mix=mix, rate=rate, speeds=speed, **fir)
+        return d_out.reshape(-1)[:need].view(shape), gains, self._delivered(words, per, windows, rates, rate, speed), statuses
 
 
 class MelBank:

@@ -1176,12 +1176,15 @@ def _window_tables(files, index, windows, force_chans=0):
         ix[i].marks = m.ctypes.data
         ix[i].blocks = m.size - 1
         ix[i].end_status = end
+    return bufs, items, ix, _windows(windows), keep
+
+
+def _windows(windows):
+    """the acm_batch_window table of (file_no, first_word, max_words) triples"""
     wins = (BatchWindow * max(len(windows), 1))()
     for k, (f, first, count) in enumerate(windows):
-        wins[k].item = f
-        wins[k].first_word = first
-        wins[k].max_words = count
-    return bufs, items, ix, wins, keep
+        wins[k].item, wins[k].first_word, wins[k].max_words = f, first, count
+    return wins
 
 
 def _end_status(buf, marks, force_chans=0):
@@ -1193,10 +1196,7 @@ def _end_status(buf, marks, force_chans=0):
 def batch_window_pcm_words(files, windows, force_chans=0):
     """samples of device memory batch_decode_windows_device needs for these windows at most"""
     bufs, items = _batch_items(files)
-    wins = (BatchWindow * max(len(windows), 1))()
-    for k, (f, first, count) in enumerate(windows):
-        wins[k].item, wins[k].first_word, wins[k].max_words = f, first, count
-    return int(lib().acm_batch_window_pcm_words(items, len(files), wins, len(windows), force_chans))
+    return int(lib().acm_batch_window_pcm_words(items, len(files), _windows(windows), len(windows), force_chans))
 
 
 def batch_decode_windows(dev, files, index, windows, force_chans=0, fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, caps=None):
@@ -1248,14 +1248,8 @@ def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, f
     own answer to a missing handle."""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
-    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
-    if dense_flags is None:
-        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
-            (DENSE_SPEED if speeds is not None else 0)
-    for k, sp in enumerate(speeds or ()):
-        if sp is not None:
-            wins[k].reserved = sp[0] << 16 | sp[1]
-    dense = None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
+    opts, dense = _dense_options(wins, d_pcm, d_pcm_words, frames, channels, planar, force_chans, fmt, threads, flags, parse, f32, batch_flags,
+                                 dense_flags, mix, rate, speeds)
     tm = WindowTiming()
     _fill(dev)
     rc = lib().acm_batch_decode_windows_dense(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
@@ -1266,6 +1260,20 @@ def batch_decode_windows_dense(dev, files, index, windows, d_pcm, d_pcm_words, f
     return res if check else res + (rc,)
 
 
+def _dense_options(wins, d_pcm, d_pcm_words, frames, channels, planar, force_chans, fmt, threads, flags, parse, f32, batch_flags, dense_flags, mix,
+                   rate, speeds):
+    """what every call of the dense family begins with, from batch_decode_windows_dense's arguments: the BatchOpts, the DenseOpts (None
+    with frames None), and the speeds in wins[k].reserved"""
+    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
+    if dense_flags is None:
+        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
+            (DENSE_SPEED if speeds is not None else 0)
+    for k, sp in enumerate(speeds or ()):
+        if sp is not None:
+            wins[k].reserved = sp[0] << 16 | sp[1]
+    return opts, None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
+
+
 def dense_overlay_gain(energy_a, energy_b, snr):
     """acm_dense_overlay_gain: the Q12 gain of b that makes the power ratio a : b what snr (Q16) asks for, from the rows' sums of squares"""
     return int(lib().acm_dense_overlay_gain(energy_a, energy_b, snr))
@@ -1273,7 +1281,7 @@ def dense_overlay_gain(energy_a, energy_b, snr):
 
 def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
                                  fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None,
-                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False, _fir=None, _feat=None):
+                                 check=True, mix=False, rate=None, speeds=None, nrows=None, result_table=False):
     """acm_batch_decode_windows_overlay: the windows are the SOURCE rows of batch_decode_windows_dense (every argument it has means the
     same), and d_pcm receives len(rows) output rows of frames * channels samples, row r at sample r * frames * channels.  rows: tuples
     (a, b, vol, snr, gain) of acm_overlay_row's inputs - b None for ACM_OVERLAY_NONE - or 6-tuples that end in `reserved`, or an array
@@ -1281,22 +1289,21 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
     (tests of the refusals: nrows is then what the call is told).  Returns (statuses, words, offsets, gains, WindowTiming): statuses and words are the windows', offsets their
     (dev_off, slot_off, slot_words), gains (g, energy_a, energy_b) per output row - or, with result_table=True (a million rows), the call's own copy of the row table as
     the library left it, an OVERLAY_ROW_DT array whose gain, energy_a and energy_b fields hold them.  check=False: the return code as a sixth element
-    instead of an exception.  _fir: batch_decode_windows_overlay_fir's - the call goes to acm_batch_decode_windows_overlay_fir with it."""
+    instead of an exception."""
+    return _overlay_call("acm_batch_decode_windows_overlay", (), dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=channels,
+                         planar=planar, force_chans=force_chans, fmt=fmt, threads=threads, flags=flags, parse=parse, f32=f32, batch_flags=batch_flags,
+                         dense_flags=dense_flags, check=check, mix=mix, rate=rate, speeds=speeds, nrows=nrows, result_table=result_table)
+
+
+def _overlay_call(name, extra, dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, channels=1, planar=False, force_chans=0,
+                  fmt=FMT_S16LE, threads=0, flags=PLAN_AUTO, parse=PARSE_HOST, f32=False, batch_flags=0, dense_flags=None, check=True, mix=False,
+                  rate=None, speeds=None, nrows=None, result_table=False):
+    """one call of the overlay family: the entry point `name` of the library with the pointers `extra` - ctypes structures or None, as
+    the entry point takes them between the dense options and the row table.  The rest is batch_decode_windows_overlay's"""
     bufs, items, ix, wins, keep = _window_tables(files, index, windows, force_chans)
     nw = len(windows)
-    opts = BatchOpts(force_chans, fmt, threads, flags | PLAN_EXTRA, parse, batch_flags | (BATCH_PCM_F32 if f32 else 0), d_pcm, d_pcm_words)
-    name = "acm_batch_decode_windows_overlay" if _fir is None else "acm_batch_decode_windows_overlay_fir"
-    extra = () if _fir is None else (C.byref(_fir[0]) if _fir[0] is not None else None,)
-    if _feat is not None:               # batch_decode_windows_features': (FeatBank or None, what it points into)
-        name = "acm_batch_decode_windows_features"
-        extra = (extra or (None,)) + (C.byref(_feat[0]) if _feat[0] is not None else None,)
-    if dense_flags is None:
-        dense_flags = (DENSE_PLANAR if planar else 0) | (DENSE_MIX if mix else 0) | (DENSE_RESAMPLE if rate is not None else 0) | \
-            (DENSE_SPEED if speeds is not None else 0)
-    for k, sp in enumerate(speeds or ()):
-        if sp is not None:
-            wins[k].reserved = sp[0] << 16 | sp[1]
-    dense = None if frames is None else DenseOpts(frames, channels, dense_flags, rate or 0)
+    opts, dense = _dense_options(wins, d_pcm, d_pcm_words, frames, channels, planar, force_chans, fmt, threads, flags, parse, f32, batch_flags,
+                                 dense_flags, mix, rate, speeds)
     nr = len(rows) if rows is not None else 0
     if isinstance(rows, np.ndarray):
         table = np.array(rows, dtype=OVERLAY_ROW_DT, ndmin=1)
@@ -1305,12 +1312,14 @@ def batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_
         for r in range(nr):
             a, b, vol, snr, gain = rows[r][:5]
             table[r] = (a, OVERLAY_NONE if b is None else b, vol, snr, gain, rows[r][5] if len(rows[r]) > 5 else 0, 0, 0)
+    entry = {"acm_batch_decode_windows_overlay": lib().acm_batch_decode_windows_overlay,
+             "acm_batch_decode_windows_overlay_fir": lib().acm_batch_decode_windows_overlay_fir,
+             "acm_batch_decode_windows_features": lib().acm_batch_decode_windows_features}[name]
     tm = WindowTiming()
     _fill(dev)
-    rc = getattr(lib(), name)(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts),
-                              C.byref(dense) if dense is not None else None, *extra,
-                              C.cast(table.ctypes.data, C.POINTER(OverlayRow)) if rows is not None else None,
-                              nr if nrows is None else nrows, C.byref(tm))
+    rc = entry(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts), C.byref(dense) if dense is not None else None,
+               *[C.byref(e) if e is not None else None for e in extra],
+               C.cast(table.ctypes.data, C.POINTER(OverlayRow)) if rows is not None else None, nr if nrows is None else nrows, C.byref(tm))
     if check:
         _check(rc, name)
     res = ([int(wins[k].status) for k in range(nw)], [int(wins[k].words) for k in range(nw)],
@@ -1364,7 +1373,7 @@ def batch_decode_windows_overlay_fir(dev, files, index, windows, rows, d_pcm, d_
     window k convolved with responses[of_window[k]] - (taps, delay, shift) of include/acm_hip.h - before the rows are made from it;
     of_window[k] None: not filtered.  no_fir: no acm_fir_opts at all; nresp, fir_reserved (tests of the refusals): as fir_opts takes them"""
     o, keep = (None, None) if no_fir else fir_opts(responses, of_window, nresp, fir_reserved)
-    return batch_decode_windows_overlay(dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, _fir=(o, keep), **kw)
+    return _overlay_call("acm_batch_decode_windows_overlay_fir", (o,), dev, files, index, windows, rows, d_pcm, d_pcm_words, frames, **kw)
 
 
 def feat_bank(n_fft, hop, n_mels, flags, window, cs, mel_first, mel_count, mel_off, mel_w, reserved=0):
@@ -1415,7 +1424,7 @@ def batch_decode_windows_features(dev, files, index, windows, rows, d_out, d_out
     bank: feat_bank's arguments as a tuple or a dict.  responses None: no acm_fir_opts.  no_bank (tests): a null bank"""
     o, keep = (None, None) if responses is None else fir_opts(responses, of_window, kw.pop("nresp", None), kw.pop("fir_reserved", 0))
     b, keep_b = (None, None) if no_bank else feat_bank(**bank) if isinstance(bank, dict) else feat_bank(*bank)
-    return batch_decode_windows_overlay(dev, files, index, windows, rows, d_out, d_out_words, frames, _fir=(o, keep), _feat=(b, keep_b), **kw)
+    return _overlay_call("acm_batch_decode_windows_features", (o, b), dev, files, index, windows, rows, d_out, d_out_words, frames, **kw)
 
 
 # --------------------------------------------------------------------------- the block index of a batch

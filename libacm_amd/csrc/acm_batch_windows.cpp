@@ -32,6 +32,11 @@
  * acm_batch_decode_windows_features is that run with its combine launch aimed at the handle's feature arena, int16, and two launches
  * of acm_dense_feat.hip behind it that make the caller's float32 features from those rows: the bank's check, its tables as they are
  * uploaded and the arena's layout are acm_feat_layout.cpp's.
+ *
+ * Which of these a call is, the layouts of its parts, where their tables sit in the H_JOBS / D_JOBS arenas and the bytes that go up
+ * are acm_dense_call.h's (DenseCall): the five entry points say what was asked (DenseAsk), one decode_windows_dense builds the call,
+ * and the driver reads offsets off its map and uploads the spans it packs.  What stays here is the device: arenas, copies, events
+ * and the launchers - the switch over the gather kernels is the one place that knows them.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -40,12 +45,9 @@
 #include <vector>
 
 #include "acm_batch_common.h"
-#include "acm_dense_layout.h"
+#include "acm_dense_call.h"
 #include "acm_device.h"
-#include "acm_feat_layout.h"
-#include "acm_fir_layout.h"
 #include "acm_hip.h"
-#include "acm_overlay_layout.h"
 #include "acm_stage.h"
 #include "acm_window_layout.h"
 #include "libacm.h"
@@ -59,12 +61,11 @@ using namespace acmbatch;
 class WinRun {
 public:
 	WinRun(acmhip_device *dev_, const acm_batch_item *items_, acm_batch_window *wins_, const acm_batch_opts &opts_,
-	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseLayout *dense_ = nullptr,
-	       void *dense_out_ = nullptr, const OverlayLayout *overlay_ = nullptr, acm_overlay_row *overlay_rows_ = nullptr, const FirLayout *fir_ = nullptr,
-	       const FeatLayout *feat_ = nullptr)
-		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), dense(dense_), dense_out(dense_out_),
-		  overlay(overlay_), overlay_rows(overlay_rows_), fir(fir_), feat(feat_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0), keep_on_device(opts_.d_pcm != nullptr),
-		  pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
+	       const std::vector<WindowItem> &its_, const WindowLayout &L_, Pool &pool_, acm_window_timing &tm_, const DenseCall *call_, void *dense_out_,
+	       acm_overlay_row *overlay_rows_)
+		: lock(dev_), dev(dev_), items(items_), wins(wins_), opts(opts_), its(its_), L(L_), pool(pool_), tm(tm_), call(call_), dense_out(dense_out_),
+		  overlay_rows(overlay_rows_), st((hipStream_t)acmhip_device_stream(dev_)), out_f32((opts_.flags & ACM_BATCH_PCM_F32) != 0),
+		  keep_on_device(opts_.d_pcm != nullptr), pcm_unit(out_f32 ? sizeof(float) : sizeof(int16_t)), live(L_.slots.size())
 	{
 		for (size_t k : L.act)
 			live[k].active = true;
@@ -91,21 +92,10 @@ private:
 	void stage_on_host(const std::vector<size_t> &ids);
 	int upload_slices(const std::vector<size_t> &ids);
 	void collect(PlanStreams &ps);
-	/* the H_JOBS / D_JOBS arenas: the device parser's tables and results, behind them a dense call's row table, and behind that an
-	 * overlay call's tables, and behind those the taps and the rows of its filter pass, and behind those a features call's bank */
-	size_t overlay_off() const { return (size_t)round_up(dense->table_off(L) + dense->table_bytes(), 64); }
-	size_t fir_off() const { return (size_t)round_up(overlay_off() + overlay->table_bytes(), 64); }
-	size_t feat_off() const { return (size_t)round_up(fir ? fir_off() + fir->table_bytes() : overlay_off() + overlay->table_bytes(), 64); }
-	size_t jobs_bytes() const
-	{
-		if (feat)
-			return feat_off() + feat->table_bytes();
-		if (fir)
-			return fir_off() + fir->table_bytes();
-		return overlay ? overlay_off() + overlay->table_bytes() : dense ? dense->table_off(L) + dense->table_bytes() : L.job_arena_bytes();
-	}
+	int launch_gather(const DenseLaunch &gather);
 	int combine_rows();
 	int make_features();
+	void read_timers(bool d2h);
 
 	ArenaLock lock;
 	acmhip_device *const dev;
@@ -116,12 +106,9 @@ private:
 	const WindowLayout &L;
 	Pool &pool;
 	acm_window_timing &tm;
-	const DenseLayout *const dense;         /* a dense call (then opts are its inner ones: int16 rows, no caller memory), else null */
-	void *const dense_out;                  /* ... and its output tensor */
-	const OverlayLayout *const overlay;     /* an overlay call (a dense call whose rows go to the source arena), else null */
-	acm_overlay_row *const overlay_rows;    /* ... and the caller's row table, for what comes back */
-	const FirLayout *const fir;             /* an overlay call some of whose windows are filtered, else null */
-	const FeatLayout *const feat;           /* an overlay call whose rows go to the feature arena and are framed there, else null */
+	const DenseCall *const call;            /* a call of the dense family (then opts are its inner ones: int16 rows, no caller memory), else null */
+	void *const dense_out;                  /* ... its output tensor */
+	acm_overlay_row *const overlay_rows;    /* ... and the caller's row table, for what comes back of an overlay call */
 	const hipStream_t st;
 	const bool out_f32, keep_on_device;
 	const size_t pcm_unit;
@@ -148,7 +135,7 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 			ACM_TRY(host_arenas(dev, L.idx_total, L.hdr_total, &h_idx, &h_hdr));
 		if (keep_on_device) {
 			d_pcm = static_cast<int16_t *>(opts.d_pcm);
-		} else if (!dense) {
+		} else if (!call) {
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, L.pcm_total * pcm_unit, (void **)&d_pcm));
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_PCM, L.pcm_total * pcm_unit, (void **)&h_pcm));
 		}
@@ -158,17 +145,18 @@ int WinRun::fetch_arenas(clk::time_point t_hdr)
 			ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_COLPOS, L.cols_total * sizeof(uint32_t), (void **)&d_colpos));
 		}
 	}
-	if (dense)              /* the intermediate PCM; a call without a window to decode still writes every row */
-		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, dense->pcm_arena_words(L.pcm_total) * sizeof(int16_t), (void **)&d_pcm));
-	if (overlay)
-		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_SRC, overlay->src_arena_words() * sizeof(int16_t), (void **)&d_src));
-	if (feat)
-		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_FEAT, feat->arena_bytes(), (void **)&d_feat));
-	if (dense || !L.dev_ids.empty()) {
-		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes(), (void **)&h_jobs));
-		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes(), (void **)&d_jobs));
+	if (call)               /* the intermediate PCM; a call without a window to decode still writes every row */
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_PCM, call->D.pcm_arena_words(L.pcm_total) * sizeof(int16_t), (void **)&d_pcm));
+	if (call && call->overlay())
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_SRC, call->O.src_arena_words() * sizeof(int16_t), (void **)&d_src));
+	if (call && call->feat())
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_FEAT, call->M.arena_bytes(), (void **)&d_feat));
+	if (call || !L.dev_ids.empty()) {
+		const size_t jobs_bytes = call ? call->map.total : L.job_arena_bytes();
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_H_JOBS, jobs_bytes, (void **)&h_jobs));
+		ACM_TRY(acmhip_arena_get(dev, ACM_ARENA_D_JOBS, jobs_bytes, (void **)&d_jobs));
 	}
-	if (dense || !L.act.empty())
+	if (call || !L.act.empty())
 		ACM_TRY(make_events(ev, 6));
 	t_alloc = clk::now();
 	tm.alloc_s = secs(t_hdr, t_alloc);
@@ -310,13 +298,7 @@ int WinRun::synthesise_and_deliver()
 		ACM_HIP_TRY(hipEventRecord(ev[5], st));
 	}
 	ACM_HIP_TRY(hipStreamSynchronize(st));
-	float ms = 0;
-	if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-		tm.h2d_s = ms * 1e-3;
-	if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
-		tm.kernel_s = ms * 1e-3;
-	if (!keep_on_device && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
-		tm.d2h_s = ms * 1e-3;
+	read_timers(!keep_on_device);
 	if (!keep_on_device)
 		pool.run(L.act.size(), [&](size_t a) {
 			const acm_batch_window &w = wins[L.act[a]];
@@ -326,98 +308,95 @@ int WinRun::synthesise_and_deliver()
 	return ACMHIP_OK;
 }
 
-/* a dense call: the same plan into the handle's PCM arena, then the row table - what staging left of every window - up through the jobs
- * arena and one launch that writes every row of the caller's tensor.  Nothing comes back but the timings */
+/* the events of a call whose stream is drained: the upload of the parse (where one was timed), the kernels, and the copy back where the
+ * call made one */
+void WinRun::read_timers(bool d2h)
+{
+	float ms = 0;
+	if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+		tm.h2d_s = ms * 1e-3;
+	if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
+		tm.kernel_s = ms * 1e-3;
+	if (d2h && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
+		tm.d2h_s = ms * 1e-3;
+}
+
+/* a dense call: the same plan into the handle's PCM arena, then the tables - what staging left of every window - up through the jobs
+ * arena and one launch that writes every row of the caller's tensor, or the launches of an overlay or a features call behind it.
+ * Nothing comes back but the timings and an overlay call's row results */
 int WinRun::synthesise_and_gather()
 {
 	PlanStreams ps;
 	collect(ps);
 	if (!ps.descs.empty())
 		ACM_TRY(acmhip_plan_create(dev, ps.descs.data(), ps.descs.size(), ps.patches.data(), ps.patches.size(), opts.plan_flags, &plan));
-	const size_t at = dense->table_off(L);
-	/* what staging left decides the kernel and how much of the tables it reads (acm_dense_layout.cpp) */
-	const DenseLaunch gather = acm_dense_tables(*dense, L.slots.data(), wins, h_jobs + at);
-	ACM_HIP_TRY(hipMemcpyAsync(d_jobs + at, h_jobs + at, gather.bytes, hipMemcpyHostToDevice, st));
-	tm.h2d_bytes += gather.bytes;
-	if (overlay && overlay->upload_bytes()) {
-		uint8_t *up = h_jobs + overlay_off();
-		memcpy(up, overlay->rows.data(), overlay->rows_bytes());
-		memcpy(up + overlay->marked_off(), overlay->marked.data(), overlay->marked.size() * sizeof(uint32_t));
-		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + overlay_off(), up, overlay->upload_bytes(), hipMemcpyHostToDevice, st));
-		tm.h2d_bytes += overlay->upload_bytes();
-	}
-	if (fir) {
-		uint8_t *up = h_jobs + fir_off();
-		memcpy(up, fir->taps.data(), fir->taps_bytes());
-		memcpy(up + fir->rows_off(), fir->rows.data(), fir->rows.size() * sizeof(AcmFirRow));
-		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + fir_off(), up, fir->table_bytes(), hipMemcpyHostToDevice, st));
-		tm.h2d_bytes += fir->table_bytes();
-	}
-	if (feat) {
-		feat->pack(h_jobs + feat_off());
-		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + feat_off(), h_jobs + feat_off(), feat->table_bytes(), hipMemcpyHostToDevice, st));
-		tm.h2d_bytes += feat->table_bytes();
+	const DensePacked packed = call->pack(h_jobs, L.slots.data(), wins);
+	for (size_t i = 0; i < packed.nspan; i++) {
+		const JobsSpan &up = packed.span[i];
+		ACM_HIP_TRY(hipMemcpyAsync(d_jobs + up.off, h_jobs + up.off, up.bytes, hipMemcpyHostToDevice, st));
+		tm.h2d_bytes += up.bytes;
 	}
 	ACM_HIP_TRY(hipEventRecord(ev[2], st));
 	if (plan)
 		ACM_TRY(launch_plan(plan, false, d_idx, d_hdr, d_pcm, ACMHIP_FMT_S16LE));
-	const AcmDenseRow *d_rows = reinterpret_cast<const AcmDenseRow *>(d_jobs + at);
-	const void *d_second = d_jobs + at + dense->resample_off();
-	const int16_t *d_taps = reinterpret_cast<const int16_t *>(d_jobs + at + dense->taps_off());
-	/* an overlay call: the same launch writes the source rows, int16, and the caller's tensor is combine_rows' */
-	void *const rows_out = overlay ? d_src : dense_out;
-	const bool rows_f32 = overlay ? false : dense->f32;
+	ACM_TRY(launch_gather(packed.gather));
+	if (call->overlay())
+		ACM_TRY(combine_rows());
+	if (call->feat())
+		ACM_TRY(make_features());
+	ACM_HIP_TRY(hipEventRecord(ev[3], st));
+	const bool results = call->overlay() && !call->O.rows.empty();
+	const size_t res_at = call->map.overlay + call->O.result_off();
+	if (results) {
+		ACM_HIP_TRY(hipEventRecord(ev[4], st));
+		ACM_HIP_TRY(hipMemcpyAsync(h_jobs + res_at, d_jobs + res_at, call->O.result_bytes(), hipMemcpyDeviceToHost, st));
+		ACM_HIP_TRY(hipEventRecord(ev[5], st));
+	}
+	ACM_HIP_TRY(hipStreamSynchronize(st));
+	read_timers(results);
+	if (results) {
+		const AcmOverlayResult *res = reinterpret_cast<const AcmOverlayResult *>(h_jobs + res_at);
+		for (size_t r = 0; r < call->O.rows.size(); r++)
+			acm_overlay_report(res[r], &overlay_rows[r]);
+	}
+	return ACMHIP_OK;
+}
+
+/* the gather launch, by the kernel the tables were packed for.  An overlay call: the same launch writes the source rows, int16, and
+ * the caller's tensor is combine_rows' */
+int WinRun::launch_gather(const DenseLaunch &gather)
+{
+	const DenseLayout &D = call->D;
+	const uint8_t *tab = d_jobs + call->map.dense;
+	const AcmDenseRow *d_rows = reinterpret_cast<const AcmDenseRow *>(tab);
+	const void *d_second = tab + D.resample_off();
+	const int16_t *d_taps = reinterpret_cast<const int16_t *>(tab + D.taps_off());
+	void *const rows_out = call->overlay() ? d_src : dense_out;
+	const bool rows_f32 = call->overlay() ? false : D.f32;
 	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	int e = 0;
 	const char *name = nullptr;
 	switch (gather.kernel) {
 	case DENSE_SPEED:
 		name = "acmk_launch_dense_speed";
-		e = acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out, dense->frames,
-					    dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		e = acmk_launch_dense_speed(d_pcm, d_rows, static_cast<const AcmSpeedRow *>(d_second), d_taps, L.slots.size(), rows_out, D.frames, D.channels,
+					    D.planar, rows_f32, caps.dense_grid, st);
 		break;
 	case DENSE_RESAMPLE:
 		name = "acmk_launch_dense_resample";
-		e = acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out, dense->frames,
-					       dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		e = acmk_launch_dense_resample(d_pcm, d_rows, static_cast<const AcmResampleRow *>(d_second), d_taps, L.slots.size(), rows_out, D.frames,
+					       D.channels, D.planar, rows_f32, caps.dense_grid, st);
 		break;
 	case DENSE_MIXED:
 		name = "acmk_launch_dense_mixed";
-		e = acmk_launch_dense_mixed(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		e = acmk_launch_dense_mixed(d_pcm, d_rows, L.slots.size(), rows_out, D.frames, D.channels, D.planar, rows_f32, caps.dense_grid, st);
 		break;
 	case DENSE_PLAIN:
 		name = "acmk_launch_dense_rows";
-		e = acmk_launch_dense_rows(d_pcm, d_rows, L.slots.size(), rows_out, dense->frames, dense->channels, dense->planar, rows_f32, caps.dense_grid, st);
+		e = acmk_launch_dense_rows(d_pcm, d_rows, L.slots.size(), rows_out, D.frames, D.channels, D.planar, rows_f32, caps.dense_grid, st);
 		break;
 	}
-	if (e != 0)
-		return acmhip_report_hip(e, name);
-	if (overlay)
-		ACM_TRY(combine_rows());
-	if (feat)
-		ACM_TRY(make_features());
-	ACM_HIP_TRY(hipEventRecord(ev[3], st));
-	const bool results = overlay && !overlay->rows.empty();
-	const size_t res_at = results ? overlay_off() + overlay->result_off() : 0;
-	if (results) {
-		ACM_HIP_TRY(hipEventRecord(ev[4], st));
-		ACM_HIP_TRY(hipMemcpyAsync(h_jobs + res_at, d_jobs + res_at, overlay->result_bytes(), hipMemcpyDeviceToHost, st));
-		ACM_HIP_TRY(hipEventRecord(ev[5], st));
-	}
-	ACM_HIP_TRY(hipStreamSynchronize(st));
-	float ms = 0;
-	if (timed_h2d && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-		tm.h2d_s = ms * 1e-3;
-	if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
-		tm.kernel_s = ms * 1e-3;
-	if (results) {
-		if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
-			tm.d2h_s = ms * 1e-3;
-		const AcmOverlayResult *res = reinterpret_cast<const AcmOverlayResult *>(h_jobs + res_at);
-		for (size_t r = 0; r < overlay->rows.size(); r++)
-			acm_overlay_report(res[r], &overlay_rows[r]);
-	}
-	return ACMHIP_OK;
+	return e != 0 ? acmhip_report_hip(e, name) : ACMHIP_OK;
 }
 
 /* an overlay call, behind the gather launch that wrote the source rows: the row table and the list of rows to sum went up with the
@@ -425,11 +404,14 @@ int WinRun::synthesise_and_gather()
  * writes the caller's tensor and a result per row */
 int WinRun::combine_rows()
 {
-	const size_t at = overlay_off();
+	const DenseLayout *const dense = &call->D;
+	const OverlayLayout *const overlay = &call->O;
+	const FirLayout *const fir = call->fir();
+	const size_t at = call->map.overlay;
 	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	uint64_t *d_energy = reinterpret_cast<uint64_t *>(d_jobs + at + overlay->energy_off());
 	if (fir) {
-		const uint8_t *d_fir = d_jobs + fir_off();
+		const uint8_t *d_fir = d_jobs + call->map.fir;
 		const int e = acmk_launch_dense_fir(d_src, reinterpret_cast<const AcmFirRow *>(d_fir + fir->rows_off()), fir->nfilt(),
 						    reinterpret_cast<const uint32_t *>(d_fir), dense->frames, dense->channels, dense->planar, caps.dense_grid, st);
 		if (e != 0)
@@ -444,7 +426,7 @@ int WinRun::combine_rows()
 	}
 	const int e = acmk_launch_dense_overlay(d_src, reinterpret_cast<const AcmOverlayRow *>(d_jobs + at), d_energy,
 						reinterpret_cast<AcmOverlayResult *>(d_jobs + at + overlay->result_off()), overlay->rows.size(),
-						feat ? d_feat : dense_out, overlay->row_words, feat ? false : dense->f32, caps.dense_grid, st);
+						call->feat() ? d_feat : dense_out, overlay->row_words, call->feat() ? false : dense->f32, caps.dense_grid, st);
 	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_overlay") : ACMHIP_OK;
 }
 
@@ -452,9 +434,10 @@ int WinRun::combine_rows()
  * others; the DFT's operand is made of the cosines behind the rows, and the feature launch writes the caller's tensor */
 int WinRun::make_features()
 {
+	const FeatLayout *const feat = &call->M;
 	if (feat->out_words == 0)
 		return ACMHIP_OK;
-	const uint8_t *tab = d_jobs + feat_off();
+	const uint8_t *tab = d_jobs + call->map.feat;
 	const acmhip_launch_caps caps = acmhip_device_launch_caps(dev);
 	uint8_t *d_twiddle = d_feat + feat->twiddle_off();
 	int e = acmk_launch_feat_twiddle(reinterpret_cast<const int16_t *>(tab + feat->cs_off()), feat->bank.n_fft, d_twiddle, st);
@@ -588,68 +571,42 @@ static int decode_windows(acmhip_device *dev, const acm_batch_item *items, size_
 	tm.blocks_parsed = layout.blocks_parsed;
 
 	const auto t_hdr = clk::now();
-	WinRun run(dev, items, wins, opts, its, layout, pool, tm);
+	WinRun run(dev, items, wins, opts, its, layout, pool, tm, nullptr, nullptr, nullptr);
 	ACM_TRY(run.fetch_arenas(t_hdr));
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
 	return run.synthesise_and_deliver();
 }
 
-/* the dense call without its wall clock; with_overlay: acm_batch_decode_windows_overlay - the windows are the sources of the nrows rows of
- * `rows`, which are what opts->d_pcm receives; fir: acm_batch_decode_windows_overlay_fir's responses, else null; with_feat:
- * acm_batch_decode_windows_features - the rows go to the feature arena, int16, and opts->d_pcm receives `bank`'s features of them */
+/* a call of the dense family without its wall clock: what `ask` says of it, acm_dense_call.h describes */
 static int decode_windows_dense(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
-				size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense, acm_window_timing &tm, bool with_overlay = false,
-				acm_overlay_row *rows = nullptr, size_t nrows = 0, const acm_fir_opts *fir = nullptr, bool with_feat = false,
-				const acm_feat_bank *bank = nullptr)
+				size_t nwin, const acm_batch_opts *opts_in, const DenseAsk &ask, acm_window_timing &tm)
 {
 	Prelude pre;
 	ACM_TRY(pre.begin(dev, items, n, index, wins, nwin, opts_in));
-	const acm_batch_opts &opts = pre.opts;
 	const std::vector<WindowItem> &its = pre.its;
 	Pool &pool = *pre.pool;
-	DenseLayout D;
-	/* the room behind d_pcm is measured against the output rows of an overlay call, by its own layout */
-	acm_batch_opts asked = opts;
-	if (with_overlay)
-		asked.d_pcm_words = ~0ull;
-	if (acm_dense_prepare(its.data(), n, wins, nwin, asked, dense, &D) != ACMHIP_OK) {
-		acmhip_set_error_text("acm_batch_decode_windows_dense: a call the dense writer does not take (include/acm_hip.h)");
+	DenseCall call;
+	const char *why = nullptr;
+	if (acm_dense_call(its.data(), n, wins, nwin, pre.opts, ask, &call, &why) != ACMHIP_OK) {
+		acmhip_set_error_text(why);
 		return ACMHIP_ERR_ARG;
 	}
-	OverlayLayout O;
-	/* ... and of a features call against the features of those rows, by its own layout again */
-	if (with_overlay && acm_overlay_prepare(rows, nrows, nwin, D.row_words, with_feat ? ~0ull : opts.d_pcm_words, &O) != ACMHIP_OK) {
-		acmhip_set_error_text("acm_batch_decode_windows_overlay: a row table the call does not take (include/acm_hip.h)");
-		return ACMHIP_ERR_ARG;
-	}
-	FirLayout F;
-	if (with_overlay && fir) {
-		if (acm_fir_prepare(fir, nwin, &F) != ACMHIP_OK) {
-			acmhip_set_error_text("acm_batch_decode_windows_overlay_fir: responses the call does not take (include/acm_hip.h)");
-			return ACMHIP_ERR_ARG;
-		}
-		acm_fir_remap(F, &O);
-	}
-	FeatLayout M;
-	if (with_feat && acm_feat_prepare(bank, dense->channels, D.frames, nrows, opts.d_pcm_words, &M) != ACMHIP_OK) {
-		acmhip_set_error_text("acm_batch_decode_windows_features: a bank or a tensor the call does not take (include/acm_hip.h)");
-		return ACMHIP_ERR_ARG;
-	}
+	const DenseLayout &D = call.D;
 	WindowLayout layout;
 	ACM_TRY(acm_window_layout(its.data(), n, D.wins.data(), nwin, D.inner, &layout, &pool));
 	for (size_t k = 0; k < nwin; k++) {
 		acm_dense_report(D, layout.slots[k], k, &wins[k]);
-		if (with_overlay)               /* nothing of d_pcm belongs to a window */
+		if (call.overlay())             /* nothing of d_pcm belongs to a window */
 			wins[k].dev_off = wins[k].slot_off = wins[k].slot_words = 0;
 	}
 	tm.blocks_parsed = layout.blocks_parsed;
 	if (!nwin)
 		return ACMHIP_OK;
+	call.place(layout.job_arena_bytes());
 
 	const auto t_hdr = clk::now();
-	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &D, opts.d_pcm, with_overlay ? &O : nullptr, rows, F.nfilt() ? &F : nullptr,
-		   with_feat ? &M : nullptr);
+	WinRun run(dev, items, wins, D.inner, its, layout, pool, tm, &call, pre.opts.d_pcm, ask.rows);
 	ACM_TRY(run.fetch_arenas(t_hdr));
 	if (!layout.act.empty())
 		ACM_TRY(layout.dev_parse ? run.parse_on_device() : run.parse_on_host());
@@ -660,22 +617,24 @@ extern "C" int acm_batch_decode_windows_dense(acmhip_device *dev, const acm_batc
 					      acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 					      acm_window_timing *timing)
 {
-	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm); });
+	const DenseAsk ask{ DENSE_ROWS, dense, nullptr, 0, nullptr, nullptr };
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
 }
 
 extern "C" int acm_batch_decode_windows_overlay(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 						acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 						acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
 {
-	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows); });
+	const DenseAsk ask{ DENSE_OVERLAY, dense, rows, nrows, nullptr, nullptr };
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
 }
 
 extern "C" int acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 						    acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 						    const acm_fir_opts *fir, acm_overlay_row *rows, size_t nrows, acm_window_timing *timing)
 {
-	return timed(timing,
-		     [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows, fir); });
+	const DenseAsk ask{ DENSE_OVERLAY, dense, rows, nrows, fir, nullptr };
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
 }
 
 extern "C" int acm_batch_decode_windows_features(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
@@ -683,9 +642,8 @@ extern "C" int acm_batch_decode_windows_features(acmhip_device *dev, const acm_b
 						 const acm_fir_opts *fir, const acm_feat_bank *bank, acm_overlay_row *rows, size_t nrows,
 						 acm_window_timing *timing)
 {
-	return timed(timing, [&](acm_window_timing &tm) {
-		return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, dense, tm, true, rows, nrows, fir, true, bank);
-	});
+	const DenseAsk ask{ DENSE_FEATURES, dense, rows, nrows, fir, bank };
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,

@@ -8,6 +8,8 @@
 
 #include <string.h>
 
+#include "acm_dense_call.h"     /* DenseLayout::table_off: the jobs-arena map */
+
 namespace acmbatch {
 
 int acm_dense_prepare(const WindowItem *items, size_t n, const acm_batch_window *wins, size_t nwin, const acm_batch_opts &opts,

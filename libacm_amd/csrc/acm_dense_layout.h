@@ -47,8 +47,8 @@ struct DenseLayout {
 	}
 	acm_batch_opts inner{};                 /* the options of the windowed decode underneath: int16 rows into the handle's own arena */
 	uint64_t pcm_arena_words(uint64_t pcm_total) const { return pcm_total + ACM_DENSE_PCM_SLACK; }
-	/* the row table travels behind the device parser's tables in the H_JOBS / D_JOBS arenas */
-	size_t table_off(const WindowLayout &L) const { return (size_t)round_up(L.job_arena_bytes(), 64); }
+	/* the row table travels behind the device parser's tables in the H_JOBS / D_JOBS arenas: where, the map of acm_dense_call.h says */
+	size_t table_off(const WindowLayout &L) const;
 	/* ... and, where a window may be resampled, the second table and the ratios' taps behind it, each from a multiple of 16 bytes on */
 	size_t row_table_bytes() const { return wins.size() * sizeof(AcmDenseRow); }
 	size_t resample_off() const { return row_table_bytes(); }
