@@ -955,8 +955,8 @@ int  acm_dense_fir_check(const acm_fir_response *r);
  *   output    y = trunc24(E) * 2^-(75 - 2 n): trunc24 keeps the 24 leading bits of E and clears the rest, so y is an exact float32,
  *             needs no rounding mode and does not depend on the order of any sum
  * With the tables acm_feat_design makes, y is (32639 / 32768)^2 times - 0.034 dB below - the power mel spectrogram of x / 32768 under
- * a window of peak 1, up to quantisation.  The logarithm stays with the caller: one elementwise operation on a tensor half the size
- * of the waveform, and a float log would not be bit-exact.
+ * a window of peak 1, up to quantisation.  This call writes the linear feature; acm_batch_decode_windows_logmel (below) writes its
+ * logarithm, an integer one - a float log would not be bit-exact -, floored, clamped to the row's maximum and scaled, in the same run.
  *
  * Element (r, b, f) is at (r * B + b) * F + f, with ACM_FEAT_TIME_MAJOR at (r * F + f) * B + b.  Every element of [0, nrows * B * F)
  * is written and nothing outside; F == 0 or nrows == 0 writes nothing and is ACMHIP_OK.
@@ -1007,6 +1007,61 @@ uint64_t acm_feat_frames(uint64_t T, const acm_feat_bank *bank);
 int  acm_feat_design(uint32_t rate, uint32_t n_fft, uint32_t win_length, uint32_t hop, uint32_t n_mels, double f_min, double f_max, uint32_t flags,
 		     int16_t *window, int16_t *cs, uint16_t *mel_first, uint16_t *mel_count, uint32_t *mel_off, uint16_t *mel_w, size_t weights_cap,
 		     size_t *n_weights);
+
+/* ------------------------------------------------------------------------
+ * Log-mel features (csrc/acm_batch_windows.cpp over csrc/acm_feat_layout.cpp, kernels: csrc/acm_dense_feat.hip):
+ * acm_batch_decode_windows_features with the logarithm, a floor, the clamp to a row's maximum and an affine scale behind it - what
+ * log10 / clamp / amax / maximum / (x + 4) / 4 of the usual recipes do in five launches more.  A call of its own beside
+ * acm_batch_decode_windows_features, which is untouched; every argument but `log` means what it means there.
+ *
+ * The contract continues that call's, on unbounded integers: rows, frames, window, DFT, power, E[b], n = log2 N, the layouts and the
+ * refusals are unchanged, and only its `output` line is replaced:
+ *   mantissa  for E >= 1: p the position of E's leading bit, m in [2^23, 2^24) E's 24 leading bits (what trunc24 keeps; for p < 23
+ *             they are shifted left)
+ *   fraction  frac(m): x = m; sixteen times x = x * x, then bit = 1 and x >>= 24 if x >= 2^47, else bit = 0 and x >>= 23; frac is
+ *             the sixteen bits, the first the highest.  x stays in [2^23, 2^24), frac is monotone in m, frac(2^23) = 0,
+ *             frac(2^24 - 1) = 65535 and 0 <= 65536 * log2(m / 2^23) - frac(m) < 1.009 (all 2^23 mantissas: tests/test_dense_logmel.py)
+ *   log       L = (p - (75 - 2 n)) * 65536 + frac(m): log2 of the linear feature y in Q16.  E = 0 gives L = floor_q16; then
+ *             L = max(L, floor_q16)
+ *   top       with ACM_FEAT_LOG_TOP: M_r = the maximum of L over all B * F elements of row r, and L = max(L, M_r - top_q16)
+ *   scale     V = (((int64) L * mul_q24 + 2^23) >> 24) + offset_q16, the shift arithmetic
+ *   output    the float32 V * 2^-16: |V| < 2^24 (acm_feat_log_check), so it is exact, needs no rounding mode and does not depend
+ *             on the order of any sum or of the maximum
+ * mul_q24 = 2^24 * c gives c * log2 y: c = ln 2 the natural logarithm, log10 2 the decimal one, 10 log10 2 decibels; the Whisper
+ * recipe - log10, floor 1e-10, the maximum less 8, (x + 4) / 4 - is floor_q16 = nearbyint(65536 * log2(1e-10)), top_q16 =
+ * nearbyint(65536 * 8 / log10 2), mul_q24 = nearbyint(2^24 * log10 2 / 4), offset_q16 = 65536.
+ *
+ * Every element of [0, nrows * B * F) is written and nothing outside; F == 0 or nrows == 0 writes nothing and is ACMHIP_OK.
+ *
+ * ACMHIP_ERR_ARG before anything is written: everything acm_batch_decode_windows_features refuses; log NULL; what acm_feat_log_check
+ * refuses: unknown flags, reserved != 0, floor_q16 outside [-64 * 65536, 64 * 65536], mul_q24 outside [1, 2^28], top_q16 above
+ * 128 * 65536 or not 0 without ACM_FEAT_LOG_TOP, or a setting whose |V| could reach 2^24 - with Lb = max(62 * 65536, |floor_q16|),
+ * the largest |L| of any bank (p in [0, 88], n in [7, 11]), it requires ((Lb * mul_q24) >> 24) + |offset_q16| + 1 < 2^24.
+ *
+ * The run is acm_batch_decode_windows_features' with the logarithm in the feature kernel's last step, where E is in registers.
+ * Without ACM_FEAT_LOG_TOP that is all, and the store is the final float.  With it the kernel stores L, a wavefront reduces its
+ * maximum and adds it with one atomic maximum to a table of the handle's own (nrows int32 behind the DFT's operand in "D_FEAT", reset
+ * by every call), and acm_feat_log_finish goes over the tensor once more, in place.  Nothing more is uploaded than for a features call.
+ * ---------------------------------------------------------------------- */
+#define ACM_FEAT_LOG_TOP       1u                       /* clamp to the row's maximum less top_q16 */
+#define ACM_FEAT_LOG_FLOOR_MAX (64 * 65536)
+#define ACM_FEAT_LOG_MUL_MAX   (1u << 28)
+#define ACM_FEAT_LOG_TOP_MAX   (128u * 65536u)
+typedef struct acm_feat_log {
+	uint32_t flags;                  /* ACM_FEAT_LOG_TOP or 0 */
+	int32_t  floor_q16;              /* the least L, log2 in Q16: -64 * 65536 .. 64 * 65536 */
+	uint32_t mul_q24;                /* 1 .. 2^28 */
+	int32_t  offset_q16;
+	uint32_t top_q16;                /* 0 .. 128 * 65536; 0 without ACM_FEAT_LOG_TOP */
+	uint32_t reserved;               /* 0 */
+} acm_feat_log;
+
+int  acm_batch_decode_windows_logmel(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+				     acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts, const acm_dense_opts *dense,
+				     const acm_fir_opts *fir, const acm_feat_bank *bank, const acm_feat_log *log, acm_overlay_row *rows, size_t nrows,
+				     acm_window_timing *timing);
+/* ACMHIP_OK for a bank and a scale the call takes, else ACMHIP_ERR_ARG: the one text of that check.  No device is needed */
+int  acm_feat_log_check(const acm_feat_bank *bank, const acm_feat_log *log);
 
 /* ------------------------------------------------------------------------
  * Batch index build (csrc/acm_batch_index.cpp): the block index of many files in one call - what acm_batch_decode_windows needs

@@ -16,6 +16,7 @@ libacm_hip.so, device memory owned by torch); tests on CPU-only machines inject 
 sharding, scatter and gather are exercised with world_size > 1.
 """
 import heapq
+import math
 import os
 
 import numpy as np
@@ -318,7 +319,7 @@ class GpuDecoder:
         return d_pcm.reshape(-1)[:need].view(shape), gains, self._delivered(words, per, windows, rates, rate, speed), statuses
 
     def crop_features(self, files, windows, frames, bank, rows=None, index=None, out=None, mix=False, rate=None, speed=None, responses=None,
-                      reverb=None):
+                      reverb=None, log=None):
         """mel filterbank features of the batch crop_overlay would make, in the same call (acm_batch_decode_windows_features): the
         waveform - mono, int16, `frames` samples a row - stays in memory of the decoder's own and only the features are written.
         windows, frames, index, mix, rate, speed, responses and reverb are crop_overlay's; rows: one Overlay per row, by default
@@ -326,7 +327,11 @@ class GpuDecoder:
         -> (feats, gains, frames_delivered, statuses): feats float32 [len(rows), n_mels, F] - [len(rows), F, n_mels] for a time-major
         bank - with F = bank.frames(frames), whatever the decoder's dtype; the rest as crop_overlay returns it.  The features are
         defined on integers (include/acm_hip.h): (32639 / 32768)^2 times the power mel spectrogram of the row / 32768, frames padded
-        with zeros; the logarithm is the caller's.  out as in crop_overlay, but float32."""
+        with zeros.  out as in crop_overlay, but float32.
+        log (acm_batch_decode_windows_logmel): a LogScale - feats is then the logarithm of those features, floored, clamped to the
+        row's maximum where the scale has a top, and scaled, still defined on integers and made in the same call:
+        log=LogScale.whisper() is log10, clamp(min=1e-10), maximum(amax - 8), (x + 4) / 4.  A scale the library does not take is a
+        ValueError."""
         files, index, per, rates, scaled, fir = self._sources("crop_features", files, windows, 1, index, mix, rate, speed, responses, reverb)
         if rows is None:
             rows = [Overlay(k) for k in range(len(windows))]
@@ -335,6 +340,10 @@ class GpuDecoder:
         shape = (nr, F, bank.n_mels) if bank.time_major else (nr, bank.n_mels, F)
         need = nr * bank.n_mels * F
         d_out = self._output(out, need, self.torch.float32, "GpuDecoder.crop_features: out is %s, the features are float32")
+        if log is not None:
+            if capi.feat_log_check(bank.record, log.record) != 0:
+                raise ValueError("GpuDecoder.crop_features: a LogScale acm_feat_log_check does not take: %r" % (log.record,))
+            fir = dict(fir, log=capi.feat_log(*log.record))
         statuses, words, _, gains, self.timing = capi.batch_decode_windows_features(
             self.dev, files, index, scaled, self._row_table(rows), d_out.data_ptr(), d_out.numel(), frames, bank.record, channels=1, planar=True,
             fmt=self.fmt, parse=self.parse, f32=False, mix=mix, rate=rate, speeds=speed, **fir)
@@ -382,6 +391,46 @@ class MelBank:
     def frames(self, T):
         """F: the frames of a row of T samples"""
         return capi.feat_frames(T, self.n_fft, self.hop, self.flags)
+
+
+class LogScale:
+    """the logarithm GpuDecoder.crop_features(log=) ends with (acm_feat_log): post_mul * log(max(y, floor)) + post_add of the linear
+    feature y, log being ln, log2, log10 or - "db" - 10 log10; with top, nothing more than `top` (in the logarithm's own unit, before
+    post_mul) below the largest value of its row.  The library works on log2 y in Q16: mul_q24 = nearbyint(2^24 * c * post_mul) with
+    c = 1, ln 2, log10 2 or 10 log10 2, floor_q16 = nearbyint(65536 * log2(floor)), top_q16 = nearbyint(65536 * top / c), offset_q16 =
+    nearbyint(65536 * post_add)."""
+    KINDS = {"log2": 1.0, "ln": math.log(2.0), "log10": math.log10(2.0), "db": 10.0 * math.log10(2.0)}
+
+    def __init__(self, kind="ln", floor=1e-10, top=None, post_mul=1.0, post_add=0.0):
+        if kind not in self.KINDS:
+            raise ValueError("LogScale: kind is one of %s" % ", ".join(sorted(self.KINDS)))
+        if not floor > 0 or (top is not None and top < 0):
+            raise ValueError("LogScale: a floor above 0 and a top of 0 or more")
+        c = self.KINDS[kind]
+        self._set(capi.FEAT_LOG_TOP if top is not None else 0, int(np.rint(65536 * math.log2(floor))), int(np.rint(2.0 ** 24 * c * post_mul)),
+                  int(np.rint(65536 * post_add)), 0 if top is None else int(np.rint(65536 * top / c)))
+        self.kind = kind
+
+    def _set(self, flags, floor_q16, mul_q24, offset_q16, top_q16):
+        self.kind = None
+        self.flags, self.floor_q16, self.mul_q24, self.offset_q16, self.top_q16 = flags, floor_q16, mul_q24, offset_q16, top_q16
+        self.record = (flags, floor_q16, mul_q24, offset_q16, top_q16)          # as capi.feat_log takes them
+        for v, lo, hi in ((flags, 0, 2 ** 32 - 1), (floor_q16, -2 ** 31, 2 ** 31 - 1), (mul_q24, 0, 2 ** 32 - 1), (offset_q16, -2 ** 31, 2 ** 31 - 1),
+                          (top_q16, 0, 2 ** 32 - 1)):
+            if not lo <= v <= hi:
+                raise ValueError("LogScale: %r is no field of acm_feat_log" % (v,))
+
+    @classmethod
+    def whisper(cls):
+        """log10, floor 1e-10, the row's maximum less 8, (x + 4) / 4"""
+        return cls("log10", 1e-10, 8.0, 0.25, 1.0)
+
+    @classmethod
+    def raw(cls, floor_q16, mul_q24=1 << 24, offset_q16=0, top_q16=None):
+        """a LogScale of acm_feat_log's integer fields as they are (include/acm_hip.h has their ranges); top_q16 None: no top"""
+        g = cls.__new__(cls)
+        g._set(capi.FEAT_LOG_TOP if top_q16 is not None else 0, int(floor_q16), int(mul_q24), int(offset_q16), 0 if top_q16 is None else int(top_q16))
+        return g
 
 
 def snr_q16(db):

@@ -185,6 +185,12 @@ class FeatBank(C.Structure):
                 ("mel_first", C.c_void_p), ("mel_count", C.c_void_p), ("mel_off", C.c_void_p), ("mel_w", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class FeatLog(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("floor_q16", C.c_int32), ("mul_q24", C.c_uint32), ("offset_q16", C.c_int32), ("top_q16", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+FEAT_LOG_TOP = 1                # FeatLog.flags: clamp to the row's maximum less top_q16
 FEAT_CENTER = 1                 # FeatBank.flags: frame f is centred on sample f * hop
 FEAT_TIME_MAJOR = 2             # ... and the features are [row][frame][band]
 FEAT_MAX_MELS = 128
@@ -236,6 +242,7 @@ ACMHIP_SYMBOLS = [
     "acm_dense_resampled_frames", "acm_dense_resample_taps", "acm_dense_speed_frames", "acm_dense_speed_taps",
     "acm_batch_decode_windows_overlay", "acm_dense_overlay_gain", "acm_batch_decode_windows_overlay_fir", "acm_dense_fir_check",
     "acm_batch_decode_windows_features", "acm_feat_bank_check", "acm_feat_frames", "acm_feat_design",
+    "acm_batch_decode_windows_logmel", "acm_feat_log_check",
     "acm_batch_index_blocks", "acm_batch_index_files", "acm_batch_decode_indexed", "acm_batch_prestaged_index",
     "acmhip_device_set_fill", "acmhip_device_arena_info", "acmhip_device_set_launch_caps",
 ]
@@ -362,6 +369,11 @@ def lib():
         L.acm_feat_frames.argtypes = [C.c_uint64, C.POINTER(FeatBank)]
         L.acm_feat_frames.restype = C.c_uint64
         L.acm_feat_design.argtypes = [C.c_uint32] * 5 + [C.c_double, C.c_double, C.c_uint32] + [vp] * 6 + [sz, C.POINTER(sz)]
+    if hasattr(L, "acm_batch_decode_windows_logmel"):
+        L.acm_batch_decode_windows_logmel.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndex), C.POINTER(BatchWindow), sz,
+                                                      C.POINTER(BatchOpts), C.POINTER(DenseOpts), C.POINTER(FirOpts), C.POINTER(FeatBank),
+                                                      C.POINTER(FeatLog), C.POINTER(OverlayRow), sz, C.POINTER(WindowTiming)]
+        L.acm_feat_log_check.argtypes = [C.POINTER(FeatBank), C.POINTER(FeatLog)]
     L.acm_batch_index_blocks.argtypes = [C.POINTER(BatchItem), sz, C.c_int, vp]
     L.acm_batch_index_blocks.restype = C.c_uint64
     L.acm_batch_index_files.argtypes = [vp, C.POINTER(BatchItem), sz, C.POINTER(BatchIndexOut), C.POINTER(IndexOpts), C.POINTER(IndexTiming)]
@@ -1314,7 +1326,8 @@ def _overlay_call(name, extra, dev, files, index, windows, rows, d_pcm, d_pcm_wo
             table[r] = (a, OVERLAY_NONE if b is None else b, vol, snr, gain, rows[r][5] if len(rows[r]) > 5 else 0, 0, 0)
     entry = {"acm_batch_decode_windows_overlay": lib().acm_batch_decode_windows_overlay,
              "acm_batch_decode_windows_overlay_fir": lib().acm_batch_decode_windows_overlay_fir,
-             "acm_batch_decode_windows_features": lib().acm_batch_decode_windows_features}[name]
+             "acm_batch_decode_windows_features": lib().acm_batch_decode_windows_features,
+             "acm_batch_decode_windows_logmel": lib().acm_batch_decode_windows_logmel}[name]
     tm = WindowTiming()
     _fill(dev)
     rc = entry(dev.h if dev is not None else None, items, len(files), ix, wins, nw, C.byref(opts), C.byref(dense) if dense is not None else None,
@@ -1417,14 +1430,37 @@ def feat_design(rate, n_fft=512, win_length=None, hop=160, n_mels=80, f_min=0.0,
     return window, cs, first, count, off, w[:nw.value]
 
 
+def feat_log(flags=0, floor_q16=0, mul_q24=1 << 24, offset_q16=0, top_q16=0, reserved=0):
+    """FeatLog of acm_feat_log's fields"""
+    return FeatLog(flags, floor_q16, mul_q24, offset_q16, top_q16, reserved)
+
+
+def feat_log_check(bank, log):
+    """acm_feat_log_check: 0 for a bank - feat_bank's arguments as a tuple or a dict - and a scale - feat_log's, or None for a null
+    pointer - that acm_batch_decode_windows_logmel takes, else ERR_ARG"""
+    b, keep = feat_bank(**bank) if isinstance(bank, dict) else feat_bank(*bank)
+    g = None if log is None else feat_log(**log) if isinstance(log, dict) else feat_log(*log)
+    return int(lib().acm_feat_log_check(C.byref(b), C.byref(g) if g is not None else None))
+
+
 def batch_decode_windows_features(dev, files, index, windows, rows, d_out, d_out_words, frames, bank, responses=None, of_window=None, no_bank=False,
-                                  **kw):
+                                  log=None, **kw):
     """acm_batch_decode_windows_features: batch_decode_windows_overlay_fir (every other argument and what is returned are its; channels
     stays 1) whose int16 rows stay in the handle, d_out receiving the float32 mel features of them, d_out_words float32 elements.
-    bank: feat_bank's arguments as a tuple or a dict.  responses None: no acm_fir_opts.  no_bank (tests): a null bank"""
+    bank: feat_bank's arguments as a tuple or a dict.  responses None: no acm_fir_opts.  no_bank (tests): a null bank.
+    log (batch_decode_windows_logmel): the entry point is acm_batch_decode_windows_logmel and takes this FeatLog, or for False none"""
     o, keep = (None, None) if responses is None else fir_opts(responses, of_window, kw.pop("nresp", None), kw.pop("fir_reserved", 0))
     b, keep_b = (None, None) if no_bank else feat_bank(**bank) if isinstance(bank, dict) else feat_bank(*bank)
-    return _overlay_call("acm_batch_decode_windows_features", (o, b), dev, files, index, windows, rows, d_out, d_out_words, frames, **kw)
+    name, extra = ("acm_batch_decode_windows_features", (o, b)) if log is None else ("acm_batch_decode_windows_logmel", (o, b, log or None))
+    return _overlay_call(name, extra, dev, files, index, windows, rows, d_out, d_out_words, frames, **kw)
+
+
+def batch_decode_windows_logmel(dev, files, index, windows, rows, d_out, d_out_words, frames, bank, log, **kw):
+    """acm_batch_decode_windows_logmel: batch_decode_windows_features (every other argument and what is returned are its) with d_out
+    receiving the logarithm of the features, floored, clamped and scaled by log: feat_log's arguments as a tuple or a dict, or None
+    (tests) for a null pointer"""
+    g = False if log is None else feat_log(**log) if isinstance(log, dict) else feat_log(*log)
+    return batch_decode_windows_features(dev, files, index, windows, rows, d_out, d_out_words, frames, bank, log=g, **kw)
 
 
 # --------------------------------------------------------------------------- the block index of a batch

@@ -454,8 +454,19 @@ int WinRun::make_features()
 	d.mel_off = reinterpret_cast<const uint32_t *>(tab + feat->off_off());
 	d.mel_w = reinterpret_cast<const uint16_t *>(tab + feat->w_off());
 	d.twiddle = d_twiddle;
-	e = acmk_launch_dense_feat(reinterpret_cast<const int16_t *>(d_feat), feat->nrows, feat->T, &d, static_cast<float *>(dense_out), caps.dense_grid, st);
-	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_feat") : ACMHIP_OK;
+	if (!feat->has_log) {
+		e = acmk_launch_dense_feat(reinterpret_cast<const int16_t *>(d_feat), feat->nrows, feat->T, &d, static_cast<float *>(dense_out), caps.dense_grid, st);
+		return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_feat") : ACMHIP_OK;
+	}
+	/* a logmel call: the scale goes with the launch, and the rows' maxima have their place behind the operand */
+	d.log_flags = feat->log.flags;
+	d.floor_q16 = feat->log.floor_q16;
+	d.mul_q24 = feat->log.mul_q24;
+	d.offset_q16 = feat->log.offset_q16;
+	d.top_q16 = feat->log.top_q16;
+	d.rowmax = feat->top() ? reinterpret_cast<int32_t *>(d_feat + feat->rowmax_off()) : nullptr;
+	e = acmk_launch_dense_logmel(reinterpret_cast<const int16_t *>(d_feat), feat->nrows, feat->T, &d, static_cast<float *>(dense_out), caps.dense_grid, st);
+	return e != 0 ? acmhip_report_hip(e, "acmk_launch_dense_logmel") : ACMHIP_OK;
 }
 
 /* headers, and whether every index is one its file can have - before anything derived from it is used */
@@ -637,13 +648,33 @@ extern "C" int acm_batch_decode_windows_overlay_fir(acmhip_device *dev, const ac
 	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
 }
 
+/* the two calls that end in features: `ask` is a features call's, with or without a scale */
+static int decode_windows_features(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index, acm_batch_window *wins,
+				   size_t nwin, const acm_batch_opts *opts_in, const DenseAsk &ask, acm_window_timing *timing)
+{
+	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
+}
+
 extern "C" int acm_batch_decode_windows_features(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
 						 acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
 						 const acm_fir_opts *fir, const acm_feat_bank *bank, acm_overlay_row *rows, size_t nrows,
 						 acm_window_timing *timing)
 {
 	const DenseAsk ask{ DENSE_FEATURES, dense, rows, nrows, fir, bank };
-	return timed(timing, [&](acm_window_timing &tm) { return decode_windows_dense(dev, items, n, index, wins, nwin, opts_in, ask, tm); });
+	return decode_windows_features(dev, items, n, index, wins, nwin, opts_in, ask, timing);
+}
+
+extern "C" int acm_batch_decode_windows_logmel(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,
+					       acm_batch_window *wins, size_t nwin, const acm_batch_opts *opts_in, const acm_dense_opts *dense,
+					       const acm_fir_opts *fir, const acm_feat_bank *bank, const acm_feat_log *log, acm_overlay_row *rows, size_t nrows,
+					       acm_window_timing *timing)
+{
+	if (!log) {
+		acmhip_set_error_text("acm_batch_decode_windows_logmel: log is NULL (include/acm_hip.h)");
+		return ACMHIP_ERR_ARG;
+	}
+	const DenseAsk ask{ DENSE_FEATURES, dense, rows, nrows, fir, bank, log };
+	return decode_windows_features(dev, items, n, index, wins, nwin, opts_in, ask, timing);
 }
 
 extern "C" int acm_batch_decode_windows(acmhip_device *dev, const acm_batch_item *items, size_t n, const acm_batch_index *index,

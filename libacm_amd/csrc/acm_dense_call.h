@@ -1,5 +1,5 @@
 /*
- * acm_dense_call.h - one call of the dense family (acm_batch_decode_windows_dense, _overlay, _overlay_fir, _features) described
+ * acm_dense_call.h - one call of the dense family (acm_batch_decode_windows_dense, _overlay, _overlay_fir, _features, _logmel) described
  * without a device: what the caller asked for (DenseAsk), the layouts of its parts in the order the entry points refuse in
  * (acm_dense_call), where their tables sit in the H_JOBS / D_JOBS arenas (acm_jobs_map - the `base` the layout headers speak of),
  * and the bytes that go up (DenseCall::pack).  Internal.  Nothing here knows a device (tests/test_dense_call.py,
@@ -30,6 +30,7 @@ struct DenseAsk {
 	size_t nrows;
 	const acm_fir_opts *fir;        /* the responses, or null */
 	const acm_feat_bank *bank;      /* DENSE_FEATURES: the bank (a null one is refused); else null */
+	const acm_feat_log *log = nullptr;      /* DENSE_FEATURES of acm_batch_decode_windows_logmel: the scale; else null */
 };
 
 /* The H_JOBS / D_JOBS arenas of a dense call: the device parser's tables and results (WindowLayout::job_arena_bytes()), behind them
@@ -137,7 +138,10 @@ inline int acm_dense_call(const WindowItem *items, size_t n, const acm_batch_win
 		acm_fir_remap(c.F, &c.O);
 	}
 	*why = "acm_batch_decode_windows_features: a bank or a tensor the call does not take (include/acm_hip.h)";
-	if (feat && acm_feat_prepare(ask.bank, ask.dense->channels, c.D.frames, ask.nrows, opts.d_pcm_words, &c.M) != ACMHIP_OK)
+	if (feat && !ask.log && acm_feat_prepare(ask.bank, ask.dense->channels, c.D.frames, ask.nrows, opts.d_pcm_words, &c.M) != ACMHIP_OK)
+		return ACMHIP_ERR_ARG;
+	*why = "acm_batch_decode_windows_logmel: a bank, a scale or a tensor the call does not take (include/acm_hip.h)";
+	if (feat && ask.log && acm_feat_prepare(ask.bank, ask.log, ask.dense->channels, c.D.frames, ask.nrows, opts.d_pcm_words, &c.M) != ACMHIP_OK)
 		return ACMHIP_ERR_ARG;
 	*why = nullptr;
 	return ACMHIP_OK;

@@ -24,7 +24,12 @@
  *                   squares and P as two 32-bit limbs into 2 KB of LDS per wavefront; behind a barrier all 256 lanes run the mel
  *                   stage over those 64 bins - a lane owns one frame and up to 8 bands and adds w * P_hi and w * P_lo to two
  *                   uint64 sums per band, both below 2^58 - so P of all bins is never resident.  trunc24 and the store end the
- *                   item: lanes along f for the default layout, along b for ACM_FEAT_TIME_MAJOR.
+ *                   item: lanes along f for the default layout, along b for ACM_FEAT_TIME_MAJOR.  Built three times over: for
+ *                   acm_batch_decode_windows_logmel the item ends with the integer logarithm of the sums instead
+ *                   (acm_feat_log_q16), scaled to the final float, or - with ACM_FEAT_LOG_TOP - stored as it is, its maximum over
+ *                   the wavefront going into the row's entry of a table with one vector atomic.
+ * acm_feat_log_finish  behind such a launch: every word of the tensor once more, in place - the clamp to the row's maximum, the scale,
+ *                   the float.
  */
 #include <hip/hip_runtime.h>
 
@@ -66,8 +71,12 @@ __global__ __launch_bounds__(FEAT_BLOCK) void acm_feat_twiddle(const int16_t *__
 	at[64] = i32x4{ (int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3] };
 }
 
-/* N: n_fft; TM: ACM_FEAT_TIME_MAJOR */
-template <int N, bool TM>
+/* what the feature kernel ends an item with: the linear feature (acm_batch_decode_windows_features); of
+ * acm_batch_decode_windows_logmel the final float, or with ACM_FEAT_LOG_TOP L itself and the row's maximum */
+enum { FEAT_LINEAR = 0, FEAT_LOG = 1, FEAT_LOG_TOP = 2 };
+
+/* N: n_fft; TM: ACM_FEAT_TIME_MAJOR; LOG: FEAT_* */
+template <int N, bool TM, int LOG>
 __global__ __launch_bounds__(FEAT_BLOCK) void acm_dense_feat(const int16_t *__restrict__ rows, const AcmFeatDesc d, uint32_t *__restrict__ out, uint64_t T,
 							      uint64_t F, uint64_t tiles, uint64_t nwork)
 {
@@ -175,25 +184,85 @@ __global__ __launch_bounds__(FEAT_BLOCK) void acm_dense_feat(const int16_t *__re
 		static_assert(NG * FEAT_WAVES * 16 >= BINS, "the groups of bin tiles cover every bin");
 
 		const uint64_t frame = f0 + mf;
+		int32_t top = INT32_MIN;                        /* of this lane's L: below every floor */
 		if (frame < F) {
 #pragma unroll
 			for (int j = 0; j < FEAT_BANDS_PER_LANE; j++) {
 				const uint32_t b = bl + 16 * j;
-				if (b < B)
-					out[TM ? (r * F + frame) * B + b : (r * B + b) * F + frame] = acm_feat_trunc24_bits(e_hi[j], e_lo[j], LOG2N);
+				if (b < B) {
+					uint32_t v;
+					if (LOG == FEAT_LINEAR) {
+						v = acm_feat_trunc24_bits(e_hi[j], e_lo[j], LOG2N);
+					} else {
+						const int32_t l = acm_feat_log_q16(e_hi[j], e_lo[j], LOG2N, d.floor_q16);
+						top = l > top ? l : top;
+						v = LOG == FEAT_LOG_TOP ? (uint32_t)l : acm_feat_log_out(l, d.mul_q24, d.offset_q16);
+					}
+					out[TM ? (r * F + frame) * B + b : (r * B + b) * F + frame] = v;
+				}
 			}
+		}
+		if (LOG == FEAT_LOG_TOP) {
+			/* the item is of one row: the wavefront's maximum, then one vector atomic of its first lane */
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) {
+				const int32_t other = __shfl_xor(top, o, 64);
+				top = other > top ? other : top;
+			}
+			if (lane == 0 && top != INT32_MIN)
+				atomicMax(d.rowmax + r, top);
 		}
 	}
 }
 
-template <int N>
+/* the second pass of a call with ACM_FEAT_LOG_TOP, in place over the tensor's words: L clamped to its row's maximum less top_q16,
+ * scaled, as a float.  One dword per lane and trip - the tensor may start anywhere on a multiple of 4 - and the grid strides */
+__global__ __launch_bounds__(FEAT_BLOCK) void acm_feat_log_finish(uint32_t *__restrict__ out, const int32_t *__restrict__ rowmax, uint64_t total,
+								   uint64_t per_row, int32_t top_q16, uint32_t mul_q24, int32_t offset_q16)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * FEAT_BLOCK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * FEAT_BLOCK) {
+		const int32_t l = (int32_t)out[i], least = rowmax[i / per_row] - top_q16;
+		out[i] = acm_feat_log_out(l > least ? l : least, mul_q24, offset_q16);
+	}
+}
+
+template <int N, int LOG>
 int launch_feat(bool tm, dim3 grid, hipStream_t st, const int16_t *rows, const AcmFeatDesc &d, uint32_t *out, uint64_t T, uint64_t F, uint64_t tiles, uint64_t nwork)
 {
 	if (tm)
-		hipLaunchKernelGGL((acm_dense_feat<N, true>), grid, dim3(FEAT_BLOCK), 0, st, rows, d, out, T, F, tiles, nwork);
+		hipLaunchKernelGGL((acm_dense_feat<N, true, LOG>), grid, dim3(FEAT_BLOCK), 0, st, rows, d, out, T, F, tiles, nwork);
 	else
-		hipLaunchKernelGGL((acm_dense_feat<N, false>), grid, dim3(FEAT_BLOCK), 0, st, rows, d, out, T, F, tiles, nwork);
+		hipLaunchKernelGGL((acm_dense_feat<N, false, LOG>), grid, dim3(FEAT_BLOCK), 0, st, rows, d, out, T, F, tiles, nwork);
 	return (int)hipGetLastError();
+}
+
+/* the feature launch of either entry point: the geometry, the refusals and the choice of the transform's build */
+template <int LOG>
+int launch_dense_feat(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const AcmFeatDesc &d, uint32_t *out, uint32_t dense_grid, hipStream_t st)
+{
+	if (d.hop == 0 || d.hop > d.n_fft || d.n_mels == 0 || d.n_mels > ACM_FEAT_MAX_MELS || frames == 0 || frames > (1ull << 40))
+		return (int)hipErrorInvalidValue;
+	const uint64_t F = (d.flags & ACM_FEAT_CENTER) ? 1 + frames / d.hop : frames >= d.n_fft ? 1 + (frames - d.n_fft) / d.hop : 0;
+	const AcmFeatGeo g = acm_feat_geo(nrows, F, dense_grid, DENSE_MAX_GRID);
+	if (!g.ok)
+		return (int)hipErrorInvalidValue;
+	if (g.nwork == 0)
+		return 0;
+	const bool tm = (d.flags & ACM_FEAT_TIME_MAJOR) != 0;
+	switch (d.n_fft) {
+	case 128:
+		return launch_feat<128, LOG>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
+	case 256:
+		return launch_feat<256, LOG>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
+	case 512:
+		return launch_feat<512, LOG>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
+	case 1024:
+		return launch_feat<1024, LOG>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
+	case 2048:
+		return launch_feat<2048, LOG>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
+	default:
+		return (int)hipErrorInvalidValue;
+	}
 }
 
 } // namespace
@@ -211,30 +280,38 @@ extern "C" int acmk_launch_feat_twiddle(const int16_t *d_cs, uint32_t n_fft, voi
 extern "C" int acmk_launch_dense_feat(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const AcmFeatDesc *desc, float *d_out, uint32_t dense_grid,
 				      void *stream)
 {
-	const AcmFeatDesc &d = *desc;
-	if (d.hop == 0 || d.hop > d.n_fft || d.n_mels == 0 || d.n_mels > ACM_FEAT_MAX_MELS || frames == 0 || frames > (1ull << 40))
-		return (int)hipErrorInvalidValue;
-	const uint64_t F = (d.flags & ACM_FEAT_CENTER) ? 1 + frames / d.hop : frames >= d.n_fft ? 1 + (frames - d.n_fft) / d.hop : 0;
-	const AcmFeatGeo g = acm_feat_geo(nrows, F, dense_grid, DENSE_MAX_GRID);
-	if (!g.ok)
-		return (int)hipErrorInvalidValue;
-	if (g.nwork == 0)
+	return launch_dense_feat<FEAT_LINEAR>(d_rows, nrows, frames, *desc, reinterpret_cast<uint32_t *>(d_out), dense_grid, (hipStream_t)stream);
+}
+
+extern "C" int acmk_launch_feat_log_finish(float *d_out, uint64_t total, uint64_t per_row, const AcmFeatDesc *desc, uint32_t dense_grid, void *stream)
+{
+	if (total == 0)
 		return 0;
-	const bool tm = (d.flags & ACM_FEAT_TIME_MAJOR) != 0;
+	if (per_row == 0 || !desc->rowmax || desc->top_q16 > ACM_FEAT_LOG_TOP_MAX)
+		return (int)hipErrorInvalidValue;
+	const uint64_t blocks = (total + FEAT_BLOCK - 1) / FEAT_BLOCK;
+	const uint32_t cap = acm_cap_value(dense_grid, DENSE_MAX_GRID);
+	hipLaunchKernelGGL(acm_feat_log_finish, dim3((uint32_t)(blocks < cap ? blocks : cap)), dim3(FEAT_BLOCK), 0, (hipStream_t)stream,
+			   reinterpret_cast<uint32_t *>(d_out), desc->rowmax, total, per_row, (int32_t)desc->top_q16, desc->mul_q24, desc->offset_q16);
+	return (int)hipGetLastError();
+}
+
+extern "C" int acmk_launch_dense_logmel(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const AcmFeatDesc *desc, float *d_out, uint32_t dense_grid,
+					void *stream)
+{
+	const AcmFeatDesc &d = *desc;
 	const hipStream_t st = (hipStream_t)stream;
 	uint32_t *out = reinterpret_cast<uint32_t *>(d_out);
-	switch (d.n_fft) {
-	case 128:
-		return launch_feat<128>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
-	case 256:
-		return launch_feat<256>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
-	case 512:
-		return launch_feat<512>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
-	case 1024:
-		return launch_feat<1024>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
-	case 2048:
-		return launch_feat<2048>(tm, dim3(g.grid), st, d_rows, d, out, frames, F, g.tiles, g.nwork);
-	default:
+	if (!(d.log_flags & ACM_FEAT_LOG_TOP))
+		return launch_dense_feat<FEAT_LOG>(d_rows, nrows, frames, d, out, dense_grid, st);
+	if (!d.rowmax)
 		return (int)hipErrorInvalidValue;
-	}
+	/* every byte 0x80: an int32 below every L, so a maximum left by the call before never shows */
+	int e = nrows ? (int)hipMemsetAsync(d.rowmax, 0x80, nrows * sizeof(int32_t), st) : 0;
+	if (e == 0)
+		e = launch_dense_feat<FEAT_LOG_TOP>(d_rows, nrows, frames, d, out, dense_grid, st);
+	if (e != 0)
+		return e;
+	const uint64_t F = (d.flags & ACM_FEAT_CENTER) ? 1 + frames / d.hop : frames >= d.n_fft ? 1 + (frames - d.n_fft) / d.hop : 0;
+	return acmk_launch_feat_log_finish(d_out, nrows * d.n_mels * F, (uint64_t)d.n_mels * F, desc, dense_grid, stream);
 }

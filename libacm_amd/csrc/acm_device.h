@@ -162,6 +162,14 @@ struct AcmFeatDesc {
 	const uint32_t *mel_off;
 	const uint16_t *mel_w;
 	const void *twiddle;
+	/* acm_batch_decode_windows_logmel (acmk_launch_dense_logmel; acmk_launch_dense_feat reads none of it): acm_feat_log's fields, and
+	 * with ACM_FEAT_LOG_TOP the rows' maxima, nrows int32 the launcher resets */
+	uint32_t log_flags;
+	int32_t floor_q16;
+	uint32_t mul_q24;
+	int32_t offset_q16;
+	uint32_t top_q16;
+	int32_t *rowmax;
 };
 
 /* levels the fused tile kernel covers; its tile geometry, like every kernel's, is owned by acm_kernel_geo.h (acmk_fused_tile_rows) */
@@ -410,6 +418,13 @@ int acmk_launch_dense_fir(int16_t *d_src, const AcmFirRow *d_rows, uint64_t nfil
 int acmk_launch_feat_twiddle(const int16_t *d_cs, uint32_t n_fft, void *d_twiddle, void *stream);
 int acmk_launch_dense_feat(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const struct AcmFeatDesc *desc, float *d_out, uint32_t dense_grid,
 			   void *stream);
+/* acmk_launch_dense_logmel: the same with the output line of acm_batch_decode_windows_logmel, by desc's log fields (checked by the
+ * caller: acm_feat_log_check).  Without ACM_FEAT_LOG_TOP one launch; with it desc->rowmax is reset on the stream, the feature launch
+ * writes L and the rows' maxima, and acmk_launch_feat_log_finish - elements [0, total) of d_out in place, element i of row i / per_row
+ * - makes the floats.  Writes those elements and that table alone */
+int acmk_launch_dense_logmel(const int16_t *d_rows, uint64_t nrows, uint64_t frames, const struct AcmFeatDesc *desc, float *d_out, uint32_t dense_grid,
+			     void *stream);
+int acmk_launch_feat_log_finish(float *d_out, uint64_t total, uint64_t per_row, const struct AcmFeatDesc *desc, uint32_t dense_grid, void *stream);
 #ifdef __cplusplus
 }
 #endif

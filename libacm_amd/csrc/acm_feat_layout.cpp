@@ -37,6 +37,19 @@ extern "C" int acm_feat_bank_check(const acm_feat_bank *b)
 	return ACMHIP_OK;
 }
 
+extern "C" int acm_feat_log_check(const acm_feat_bank *b, const acm_feat_log *g)
+{
+	if (acm_feat_bank_check(b) != ACMHIP_OK || !g || (g->flags & ~ACM_FEAT_LOG_TOP) != 0 || g->reserved != 0)
+		return ACMHIP_ERR_ARG;
+	if (g->floor_q16 < -ACM_FEAT_LOG_FLOOR_MAX || g->floor_q16 > ACM_FEAT_LOG_FLOOR_MAX || g->mul_q24 == 0 || g->mul_q24 > ACM_FEAT_LOG_MUL_MAX ||
+	    g->top_q16 > ACM_FEAT_LOG_TOP_MAX || (g->top_q16 != 0 && !(g->flags & ACM_FEAT_LOG_TOP)))
+		return ACMHIP_ERR_ARG;
+	/* |V| stays below 2^24: |L| <= Lb, the largest |log2 y| of any bank (p in [0, 88], n in [7, 11]) or the floor */
+	const int64_t fl = g->floor_q16 < 0 ? -(int64_t)g->floor_q16 : g->floor_q16, off = g->offset_q16 < 0 ? -(int64_t)g->offset_q16 : g->offset_q16;
+	const int64_t lb = fl > 62 * 65536 ? fl : 62 * 65536;
+	return ((lb * (int64_t)g->mul_q24) >> 24) + off + 1 < ((int64_t)1 << 24) ? ACMHIP_OK : ACMHIP_ERR_ARG;
+}
+
 extern "C" uint64_t acm_feat_frames(uint64_t T, const acm_feat_bank *b)
 {
 	if (!b || b->hop == 0)
@@ -132,6 +145,16 @@ int acm_feat_prepare(const acm_feat_bank *bank, uint32_t channels, uint64_t T, u
 		return ACMHIP_ERR_ARG;
 	L.out_words = nrows * per_row;
 	return d_pcm_words >= L.out_words ? ACMHIP_OK : ACMHIP_ERR_ARG;
+}
+
+int acm_feat_prepare(const acm_feat_bank *bank, const acm_feat_log *log, uint32_t channels, uint64_t T, uint64_t nrows, uint64_t d_pcm_words,
+		     FeatLayout *out)
+{
+	if (acm_feat_prepare(bank, channels, T, nrows, d_pcm_words, out) != ACMHIP_OK || acm_feat_log_check(bank, log) != ACMHIP_OK)
+		return ACMHIP_ERR_ARG;
+	out->has_log = true;
+	out->log = *log;
+	return ACMHIP_OK;
 }
 
 void FeatLayout::pack(uint8_t *dst) const

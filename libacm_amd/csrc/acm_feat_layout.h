@@ -2,7 +2,8 @@
  * acm_feat_layout.h - the device-free half of acm_batch_decode_windows_features (acm_batch_windows.cpp): whether the bank is one the
  * call takes (acm_feat_bank_check, the one text of it), the designed tables (acm_feat_design), the frame count, the byte split of the
  * DFT's operands, the join of the four matrix products, the two-limb mel sum's end (trunc24), the geometry of the feature grid and
- * the sizes of what is uploaded and of the feature arena.  Internal.  Neither this header nor acm_feat_layout.cpp knows a device
+ * the sizes of what is uploaded and of the feature arena; and of acm_batch_decode_windows_logmel: the integer logarithm of that sum
+ * (acm_feat_log_q16), its scale (acm_feat_log_out), the check of both (acm_feat_log_check) and the rows' maxima.  Internal.  Neither this header nor acm_feat_layout.cpp knows a device
  * (tests/test_dense_feat.py, tests/native/feat_layout.cpp); what is marked ACM_FEAT_HD is compiled into the kernels
  * (acm_dense_feat.hip) too, so the program without a device checks the text the device runs.
  */
@@ -41,24 +42,73 @@ ACM_FEAT_HD static inline int64_t acm_feat_join(int32_t hh, int32_t hl, int32_t 
 /* A of include/acm_hip.h from Re (or Bv from Im): q = n - 1 >= 6 */
 ACM_FEAT_HD static inline int64_t acm_feat_scale(int64_t re, uint32_t n) { return (re + ((int64_t)1 << (n - 2))) >> (n - 1); }
 
-/* y of include/acm_hip.h from the two limb sums of a band, E = s_hi * 2^32 + s_lo (s_hi = sum w * (P >> 32), s_lo = sum w * (P mod
- * 2^32), both below 2^58): the 24 leading bits of E, as a float32 with exponent - (75 - 2 n).  Nothing is rounded; E = 0 is +0.0 */
-ACM_FEAT_HD static inline uint32_t acm_feat_trunc24_bits(uint64_t s_hi, uint64_t s_lo, uint32_t n)
+/* E = s_hi * 2^32 + s_lo from the two limb sums of a band (s_hi = sum w * (P >> 32), s_lo = sum w * (P mod 2^32), both below 2^58):
+ * the position p of its leading bit, - 1 for E = 0, and *m in [2^23, 2^24) its 24 leading bits (shifted left for p < 23) */
+ACM_FEAT_HD static inline int acm_feat_lead(uint64_t s_hi, uint64_t s_lo, uint32_t *m)
 {
 	const uint64_t lo = (s_hi << 32) + s_lo;
 	const uint64_t hi = (s_hi >> 32) + (lo < s_lo ? 1u : 0u);
+	*m = 0;
 	if ((hi | lo) == 0)
-		return 0;
+		return -1;
 	const int p = hi ? 127 - __builtin_clzll(hi) : 63 - __builtin_clzll(lo);        /* the leading bit of E */
-	uint64_t m;                                                                     /* ... at bit 23 of m */
 	if (p <= 23) {
-		m = lo << (23 - p);
+		*m = (uint32_t)(lo << (23 - p));                                        /* ... at bit 23 of m */
 	} else {
 		const int sh = p - 23;
-		m = sh >= 64 ? hi >> (sh - 64) : (lo >> sh) | (hi ? hi << (64 - sh) : 0);
+		*m = (uint32_t)(sh >= 64 ? hi >> (sh - 64) : (lo >> sh) | (hi ? hi << (64 - sh) : 0)) & 0xFFFFFFu;
 	}
+	return p;
+}
+
+/* y of include/acm_hip.h from the two limb sums: the 24 leading bits of E, as a float32 with exponent - (75 - 2 n).  Nothing is
+ * rounded; E = 0 is +0.0 */
+ACM_FEAT_HD static inline uint32_t acm_feat_trunc24_bits(uint64_t s_hi, uint64_t s_lo, uint32_t n)
+{
+	uint32_t m;
+	const int p = acm_feat_lead(s_hi, s_lo, &m);
+	if (p < 0)
+		return 0;
 	const int e = p - (75 - 2 * (int)n);
-	return (uint32_t)(e + 127) << 23 | ((uint32_t)m & 0x7FFFFFu);
+	return (uint32_t)(e + 127) << 23 | (m & 0x7FFFFFu);
+}
+
+/* frac of include/acm_hip.h: the sixteen bits behind the point of log2(m / 2^23), m in [2^23, 2^24), by sixteen squarings - the
+ * square of x in [2^23, 2^24) is in [2^46, 2^48), its bit 47 is the next bit of the logarithm, and the shift keeps x in range */
+ACM_FEAT_HD static inline uint32_t acm_feat_log_frac(uint32_t m)
+{
+	uint64_t x = m;
+	uint32_t frac = 0;
+	for (int i = 0; i < 16; i++) {
+		x *= x;
+		const uint32_t bit = (uint32_t)(x >> 47);
+		x >>= 23 + bit;
+		frac = frac << 1 | bit;
+	}
+	return frac;
+}
+
+/* L of include/acm_hip.h from the two limb sums: log2 of y in Q16, (p - (75 - 2 n)) * 65536 + frac(m), E = 0 at the floor, and
+ * nothing below the floor */
+ACM_FEAT_HD static inline int32_t acm_feat_log_q16(uint64_t s_hi, uint64_t s_lo, uint32_t n, int32_t floor_q16)
+{
+	uint32_t m;
+	const int p = acm_feat_lead(s_hi, s_lo, &m);
+	if (p < 0)
+		return floor_q16;
+	const int32_t l = (p - (75 - 2 * (int)n)) * 65536 + (int32_t)acm_feat_log_frac(m);
+	return l > floor_q16 ? l : floor_q16;
+}
+
+/* the output of include/acm_hip.h from L: V = ((L * mul + 2^23) >> 24) + offset, the shift arithmetic, as the bits of the float32
+ * V * 2^-16 - exact, acm_feat_log_check keeps |V| below 2^24 */
+ACM_FEAT_HD static inline uint32_t acm_feat_log_out(int32_t l, uint32_t mul_q24, int32_t offset_q16)
+{
+	const int64_t v = (((int64_t)l * (int64_t)mul_q24 + ((int64_t)1 << 23)) >> 24) + offset_q16;
+	const float y = (float)(int32_t)v * (1.0f / 65536.0f);
+	uint32_t bits;
+	__builtin_memcpy(&bits, &y, sizeof bits);
+	return bits;
 }
 
 /* what the feature kernel is launched over: items are (row, tile of ACM_FEAT_TILE frames), the grid is capped by the handle's
@@ -107,7 +157,14 @@ struct FeatLayout {
 	size_t table_bytes() const { return up16(w_off() + n_weights * sizeof(uint16_t)); }
 	size_t rows_bytes() const { return (size_t)((nrows * T + ACM_FEAT_ROW_SLACK) * sizeof(int16_t)); }
 	size_t twiddle_off() const { return (rows_bytes() + 255) / 256 * 256; }
-	size_t arena_bytes() const { return twiddle_off() + acm_feat_twiddle_bytes(bank.n_fft); }
+	/* acm_batch_decode_windows_logmel: the scale (has_log), and with ACM_FEAT_LOG_TOP a table of the rows' maxima, nrows int32,
+	 * behind the B operand on a multiple of 256 - a call without TOP has none, and its arena ends where a features call's does */
+	bool has_log = false;
+	acm_feat_log log{};
+	bool top() const { return has_log && (log.flags & ACM_FEAT_LOG_TOP) != 0; }
+	size_t rowmax_off() const { return (twiddle_off() + acm_feat_twiddle_bytes(bank.n_fft) + 255) / 256 * 256; }
+	size_t rowmax_bytes() const { return top() ? (size_t)nrows * sizeof(int32_t) : 0; }
+	size_t arena_bytes() const { return top() ? rowmax_off() + rowmax_bytes() : twiddle_off() + acm_feat_twiddle_bytes(bank.n_fft); }
 	/* the tables as uploaded, into table_bytes() bytes at dst */
 	void pack(uint8_t *dst) const;
 	static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
@@ -116,6 +173,9 @@ struct FeatLayout {
 /* ACMHIP_OK, or ACMHIP_ERR_ARG for what include/acm_hip.h refuses of the bank, of channels or of the room behind d_pcm - then nothing
  * of `out` is to be used */
 int acm_feat_prepare(const acm_feat_bank *bank, uint32_t channels, uint64_t T, uint64_t nrows, uint64_t d_pcm_words, FeatLayout *out);
+/* ... and with `log` given, for what acm_batch_decode_windows_logmel refuses beyond that (acm_feat_log_check) */
+int acm_feat_prepare(const acm_feat_bank *bank, const acm_feat_log *log, uint32_t channels, uint64_t T, uint64_t nrows, uint64_t d_pcm_words,
+		     FeatLayout *out);
 
 } // namespace acmbatch
 #endif

@@ -37,7 +37,10 @@ def stats(t):
 
 class FeatDesc(C.Structure):
     _fields_ = [("n_fft", C.c_uint32), ("hop", C.c_uint32), ("n_mels", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_void_p),
-                ("mel_first", C.c_void_p), ("mel_count", C.c_void_p), ("mel_off", C.c_void_p), ("mel_w", C.c_void_p), ("twiddle", C.c_void_p)]
+                ("mel_first", C.c_void_p), ("mel_count", C.c_void_p), ("mel_off", C.c_void_p), ("mel_w", C.c_void_p), ("twiddle", C.c_void_p),
+                # acmk_launch_dense_logmel's (dense_logmel_probe.py); acmk_launch_dense_feat reads none of them, an older library has none
+                ("log_flags", C.c_uint32), ("floor_q16", C.c_int32), ("mul_q24", C.c_uint32), ("offset_q16", C.c_int32), ("top_q16", C.c_uint32),
+                ("rowmax", C.c_void_p)]
 
 
 def step_kernel(args):
